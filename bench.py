@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- simulation steps/s of the SPH fluid step on MI355X (BASELINE.json's metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3] [--dist cloud|lattice]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3] [--dist cloud|lattice] [--dump-outputs DIR]
 
 One "step" = one full pass of the hot path (cell sort -> density -> force -> integrate) over all
 particles, inputs resident in HBM before the timed region, no host readback inside it.  Rank 0
@@ -114,7 +114,39 @@ def parse_args():
     ap.add_argument("--cpu-steps", type=int, default=12,
                     help="CPU-restatement steps timed for cpu_baseline (~10 s of CPU work at C3 on 16 threads)")
     ap.add_argument("--breakdown", action="store_true", help="also print a per-kernel table to stderr")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the particle records the timed path computed in its last step (the state after step W+K of "
+                         "the last repetition, what ws_read_particles hands a caller, original-id order) as DIR/<field>.npy, "
+                         "float32, at most 64 MB in all (a fixed, seeded sample of particles beyond that); see dump_outputs()")
     return ap.parse_args()
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 0x5EED
+
+
+def dump_outputs(records, out_dir, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: one float32 .npy per field of the 80-byte particle records (position, density, pressure, velocity,
+    acceleration, predicted_position; original-id order) plus particle_index.npy (float64: the particle id of each row).
+    The inputs of a run are fixed by its arguments, so two builds can be compared file for file.  When all rows would
+    exceed max_bytes, a fixed, seeded sample of particle ids (sorted) is written instead: the same rows on every run."""
+    import numpy as np
+
+    n = records.shape[0]
+    per_row = records.dtype.itemsize + 8  # the fields + the float64 id
+    rows = (max_bytes - 4096) // per_row  # (4 KB for the .npy headers)
+    if n <= rows:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, rows, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    written = {"particle_index": idx.astype(np.float64)}
+    for f in records.dtype.names:
+        written[f] = np.ascontiguousarray(records[f][idx], dtype=np.float32)
+    for name, arr in written.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return {"dir": out_dir, "particles": int(n), "rows": int(idx.size), "sampled": bool(idx.size < n),
+            "bytes": int(sum(a.nbytes for a in written.values())), "arrays": sorted(written)}
 
 
 def cpu_baseline(pos, params, steps):
@@ -435,14 +467,17 @@ def main():
             elapsed = float(t.item())
         return elapsed, worker.profile()
 
-    def one_repetition():
+    def one_repetition(last):
         """A fresh trajectory: W untimed warm-up steps, EXACTLY K timed steps, then (same handle) on to step 400 and the
-        100 timed steps of the settled window."""
+        100 timed steps of the settled window.  The last repetition reads back the state after the K timed steps for
+        --dump-outputs (collective on a slab handle: every rank takes part)."""
         worker = make_worker()
         worker.profile_select(neighbour_mask)
         worker.run(args.warmup)
         elapsed, prof = timed_window(worker, args.steps)
         rep = {"elapsed": elapsed, "prof": prof, "owned": worker.num_owned() if distributed else n_global}
+        if last and args.dump_outputs:
+            rep["records"] = worker.read_vec("particles")
         done = args.warmup + args.steps
         if not args.no_settled and done <= SETTLED_FROM:
             worker.run(SETTLED_FROM - done)
@@ -452,11 +487,19 @@ def main():
 
     reps = []
     worker = None
-    for _ in range(max(1, args.reps)):
+    n_reps = max(1, args.reps)
+    for i in range(n_reps):
         if worker is not None:
             worker.close()
-        worker, rep = one_repetition()
+        worker, rep = one_repetition(i == n_reps - 1)
         reps.append(rep)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(reps[-1].pop("records"), os.path.abspath(args.dump_outputs))
+        print("dump-outputs: %d of %d particles, %.1f MB in %s" % (dumped["rows"], dumped["particles"], dumped["bytes"] / 1e6,
+                                                                   dumped["dir"]), file=sys.stderr)
+    for r in reps:
+        r.pop("records", None)
 
     def median_of(key):
         order = sorted(range(len(reps)), key=lambda i: reps[i][key])
@@ -761,6 +804,8 @@ def main():
                 "sizing": "from the demand of a few steps earlier (WS_FLAG_LAGGED_MESSAGES)" if (args.lagged_messages or args.graph) else "exact: every message at its sender's count (default)",
                 "note": "sizes in force at the end of the last timed window; DESIGN.md 6"}
         out["stats"] = stats
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if grid is not None:
             out["config"]["grid_cells"] = grid
         if not args.no_cpu_baseline and not distributed:

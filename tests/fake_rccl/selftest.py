@@ -1,10 +1,10 @@
 """Stand-alone exercise of tests/libfakerccl.so (no product code): `world` host threads, one torch stream each, all-gathers
 of alternating sizes, all-to-alls and neighbour send / recv groups with per-rank delays; every result is checked on the host.
     python3 tests/fake_rccl/selftest.py [world] [rounds]
-With four or more ranks set GPU_MAX_HW_QUEUES=8: the runtime multiplexes the streams of one priority onto four hardware
-queues, and two ranks' torch streams that share one wait for each other's spinning kernel until the stand-in's time limit
-(world 4: 3 000 bad results with the default, none with eight queues).  The product's own slab streams (two per rank, of
-different priorities, created by the library) have not collided in the 4-rank cases of tests/test_gpu_fake_rccl.py."""
+Ranks whose torch streams share a hardware queue can wait for each other's spinning kernel until the stand-in's time
+limit (world 4 on the runtime's default of four queues per priority: 3 000 bad results); each wait is bounded, so such a
+collision shows as bad results, never as a hang.  The product's own slab streams (two per rank, of different priorities,
+created by the library) are what tests/fake_rccl_worker.py exercises."""
 import ctypes as C
 import os
 import random

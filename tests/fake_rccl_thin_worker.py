@@ -1,4 +1,4 @@
-"""Child process of tests/test_gpu_fake_rccl.py::test_thin_and_thick_slabs_agree_on_the_halo_stream: eight slab handles in
+"""Developer program (tests/test_gpu_fake_rccl.py says why it is not a test): eight slab handles in
 this process on the tests' stand-in for librccl, in a container only 20 cell layers wide: the equal cuts give the slabs two
 or three layers each.  Whether the halos overlap the early kernels (and so travel on the communication stream = the
 transport's second communicator) must be decided alike on every rank: a two-layer slab deciding for itself, as until

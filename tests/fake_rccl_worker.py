@@ -1,4 +1,4 @@
-"""Child process of tests/test_gpu_fake_rccl.py: WS_RCCL_LIBRARY names the tests' stand-in for librccl (tests/fake_rccl/)
+"""Developer program (tests/test_gpu_fake_rccl.py says why it is not a test): WS_RCCL_LIBRARY names the tests' stand-in for librccl (tests/fake_rccl/)
 and the slab handles are made by the DEVELOPER build of the library (tests/libwsfluid_dev.so: the only build that honours
 that variable), so ws_rccl_transport_create binds IT -- and the library's RCCL transport (csrc/ws_rccl.cpp: peer arithmetic, segment
 order, grouped send / recv, the all-to-all and the all-gather, two communicators bound to two streams, ncclCommSplit) runs with real

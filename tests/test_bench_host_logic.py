@@ -45,3 +45,31 @@ def test_same_config_one_gpu_reads_the_committed_line():
         assert line["config"]["workload"].upper().startswith(cfg.upper())
     assert b.same_config_one_gpu("c1x2", "cloud") is None
     assert b.same_config_one_gpu("c4", "lattice") is None
+
+
+def test_dump_outputs_is_bounded_seeded_and_float(tmp_path):
+    """--dump-outputs: float32 / float64 .npy files only, at most the byte budget in all, and the same sampled rows on
+    every run (two builds are compared file for file)."""
+    import numpy as np
+
+    b = _bench()
+    from water_sandbox_amd import fluid
+
+    rec = np.zeros(5000, fluid.PARTICLE_DTYPE)
+    rec["position"][:, 0] = np.arange(5000, dtype=np.float32)
+    budget = 100_000
+    got = []
+    for d in ("a", "b"):
+        info = b.dump_outputs(rec, str(tmp_path / d), max_bytes=budget)
+        assert info["sampled"] and 0 < info["rows"] < 5000
+        files = sorted(os.listdir(tmp_path / d))
+        assert files == sorted(n + ".npy" for n in ["particle_index"] + list(fluid.PARTICLE_DTYPE.names))
+        assert sum(os.path.getsize(tmp_path / d / f) for f in files) <= budget
+        arrays = {f: np.load(tmp_path / d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        idx = arrays["particle_index.npy"]
+        assert np.array_equal(arrays["position.npy"][:, 0], idx.astype(np.float32))  # rows are the named particles
+        got.append(arrays)
+    assert all(np.array_equal(got[0][f], got[1][f]) for f in got[0])
+    small = b.dump_outputs(rec[:100], str(tmp_path / "c"), max_bytes=budget)  # fits: every particle, in id order
+    assert not small["sampled"] and np.array_equal(np.load(tmp_path / "c" / "particle_index.npy"), np.arange(100))

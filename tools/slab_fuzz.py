@@ -4,7 +4,8 @@ length per case, `world` loopback slabs on this one GPU against the single handl
 routes were used.  usage: slab_fuzz.py [cases] [seed] [exact|lagged|graph] [benign]
 (graph, round 5: the CAPTURED multi-rank step -- WS_FLAG_GRAPH | WS_FLAG_GRAPH_MULTIRANK, which travels with fixed-capacity
 messages -- through the library's RCCL transport and the tests' stand-in for librccl, 2 .. 4 slabs as host threads; needs
-WS_RCCL_LIBRARY = tests/libfakerccl.so and GPU_MAX_HW_QUEUES=24 in the environment, and uses the developer build)
+WS_RCCL_LIBRARY = tests/libfakerccl.so in the environment and a hardware queue for every stream of every slab, see
+tests/test_gpu_fake_rccl.py, and uses the developer build)
 (exact: the default sizes; lagged: WS_FLAG_LAGGED_MESSAGES; benign: gravity along x up to 20 and the benchmark clouds' particle density, 50 per unit volume, instead of up to 3 000 and up to 60 times that)"""
 import json
 import os
