@@ -385,6 +385,36 @@ ws_status ws_slab_counters(ws_handle *h, uint64_t out[4]);
 ws_status ws_read_sort_view(ws_handle *h, uint32_t *keys_by_id, uint32_t *perm,
                             uint32_t *cell_offsets);
 
+/* ---- the fluid as a field (render / probe coupling; no reference counterpart) ------------------------------------
+ * SURVEY 8(f) row 2, "readback / render coupling": what a renderer (raymarching, marching cubes, normals) or a probe
+ * ("how much fluid is here?") needs, without reading back every position (src/fluid_compute.rs:478-485) and rebuilding
+ * a neighbour search on the CPU.
+ * Density field of the particles' current POSITIONS (the state the enqueued steps leave; the uploaded positions before
+ * the first step), at the nodes of a regular grid:
+ *   node (i, j, k) = origin + (i, j, k) * spacing, each coordinate as fl(origin[a] + fl((float)i * spacing[a]))
+ *   out_density[(k * dims[1] + j) * dims[0] + i] = sum over particles p with |node - x_p| <= h of (h - d)^2 * pow2
+ *   out_gradient (3 floats per node, same order; NULL = not computed) = sum of (d - h) * pow2_der * (node - x_p) / d
+ *       (a particle at d == 0 contributes 0)
+ * x-fastest, like a 3D texture.  Waits for enqueued steps.  Slab handles: COLLECTIVE, like ws_read_positions;
+ * a rank that passes both outputs NULL only contributes.
+ * The kernels are smoothing_kernel / smoothing_kernel_derivative (assets/simulation.wgsl:93-107) with the constants
+ * ws_get_smoothing_kernel derives.  "|node - x_p| <= h" is the step's own test: with e = x_p - node,
+ * d2 = e.x*e.x + e.y*e.y + e.z*e.z, a particle counts unless d2 > (largest f32 T with sqrtf(T) <= h), and d = sqrt(d2).
+ * Arithmetic follows the handle: hardware sqrt / reciprocal by default, gradient term (node - x_p) * ((d - h) * pow2_der
+ * * rcp(d)); correctly rounded with WS_FLAG_IEEE_DIVISION, ((node - x_p) / d) * ((d - h) * pow2_der).  Every particle in
+ * the support counts exactly once: the reference's hash-aliasing multiplicity reproduces its own neighbour sets of
+ * particles, and a field has no reference counterpart.  Summation order is canonical (cells in increasing linear id of
+ * the handle's grid, ascending particle id inside a cell), so the result depends on the particle set and the query
+ * alone -- not on grid versus points call, slab count, WS_FLAG_GRAPH or the tile schedule.  Nothing the next ws_step
+ * reads is written (the sampler bins the positions into scratch of its own, allocated on the first call).
+ * Errors: WS_ERR_INVALID_ARG (NULL handle; both outputs NULL on a single handle; m == 0; a dims entry of 0; a non-finite
+ * origin or point; spacing <= 0 or non-finite; more than 2^31 nodes), WS_ERR_OUT_OF_MEMORY (scratch allocation failed:
+ * the handle stays usable), WS_ERR_UNSUPPORTED (WS_FLAG_REFERENCE_ORDER handles), WS_ERR_HIP on an unusable handle. */
+ws_status ws_sample_density_grid(ws_handle *h, const float origin[3], const float spacing[3], const uint32_t dims[3],
+                                 float *out_density, float *out_gradient);
+/* The same field at m arbitrary points (xyz: m*3 floats). */
+ws_status ws_sample_density_points(ws_handle *h, const float *xyz, uint32_t m, float *out_density, float *out_gradient);
+
 /* ---- introspection ------------------------------------------------------------- */
 const char *ws_last_error(ws_handle *h);
 uint32_t ws_num_particles(ws_handle *h);

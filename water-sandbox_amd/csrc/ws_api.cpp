@@ -29,6 +29,7 @@ ws_status slab_gather_by_id(ws_handle *h, int kind);
 ws_status slab_reset(ws_handle *h, const float *pos_xyz);
 ws_status slab_write_particles(ws_handle *h, const ws_particle80 *in);
 ws_status slab_regrid(ws_handle *h, const ws_params *params, bool rebalance);
+ws_status slab_field_positions(ws_handle *h, const float **xyz, WsDev *global);
 
 ws_status fail(ws_handle *h, ws_status st, const char *what, hipError_t e = hipSuccess)
 {
@@ -629,6 +630,83 @@ void free_particle_arrays(ws_handle *h)
     h->mask = WsMask{nullptr, 0};
 }
 
+// The density field sampler's scratch (ws_handle::field).  Per particle: 12 B positions by id (single-GPU handles),
+// 3 x 4 B keys / tentative slots / sorted ids, 16 B sorted {position, id} = 40 B; per cell: count, cursor and start
+// (4 B each) and the scan state; plus the queries and results of the largest call so far.  
+void free_field(ws_handle *h, bool all)
+{
+    auto &F = h->field;
+    hipFree(F.count); hipFree(F.cursor); hipFree(F.start); hipFree(F.bsum);
+    F.count = F.cursor = F.start = F.bsum = nullptr;
+    F.cells = 0;
+    if (!all) return;
+    hipFree(F.xyz); hipFree(F.keys); hipFree(F.tmp); hipFree(F.perm); hipFree(F.spos);
+    hipFree(F.q); hipFree(F.rho); hipFree(F.grad);
+    F.xyz = nullptr; F.keys = F.tmp = F.perm = nullptr; F.spos = nullptr;
+    F.q = F.rho = F.grad = nullptr;
+    F.n = 0;
+    F.q_bytes = F.rho_bytes = F.grad_bytes = 0;
+}
+
+// An allocation of the sampler: a failure is WS_ERR_OUT_OF_MEMORY and leaves no sticky HIP error behind (the next
+// ws_step checks hipGetLastError), so the handle stays usable.
+ws_status field_malloc(ws_handle *h, void **p, size_t bytes)
+{
+    const hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 4));
+    if (e == hipSuccess) return WS_OK;
+    (void)hipGetLastError();
+    *p = nullptr;
+    return fail(h, WS_ERR_OUT_OF_MEMORY, "density field scratch", e);
+}
+
+ws_status field_grow(ws_handle *h, float **p, size_t *have, size_t need)
+{
+    if (*have >= need) return WS_OK;
+    hipFree(*p);
+    *p = nullptr;
+    *have = 0;
+    const ws_status st = field_malloc(h, reinterpret_cast<void **>(p), need);
+    if (!st) *have = need;
+    return st;
+}
+
+ws_status field_alloc(ws_handle *h, uint32_t n, uint32_t ncells)
+{
+    auto &F = h->field;
+    ws_status st = WS_OK;
+    if (F.n != n) {
+        free_field(h, true);
+        if (!h->slab) st = field_malloc(h, reinterpret_cast<void **>(&F.xyz), (size_t)n * 12);
+        if (!st) st = field_malloc(h, reinterpret_cast<void **>(&F.keys), (size_t)n * 4);
+        if (!st) st = field_malloc(h, reinterpret_cast<void **>(&F.tmp), (size_t)n * 4);
+        if (!st) st = field_malloc(h, reinterpret_cast<void **>(&F.perm), (size_t)n * 4);
+        if (!st) st = field_malloc(h, reinterpret_cast<void **>(&F.spos), (size_t)n * 16);
+        if (st) {
+            free_field(h, true);
+            return st;
+        }
+        F.n = n;
+    }
+    if (F.cells != ncells) {  // (new handle, or a re-grid since the last sample call)
+        free_field(h, false);
+        const size_t sw = (size_t)wsk_scan_state_words(ncells) * 4;
+        st = field_malloc(h, reinterpret_cast<void **>(&F.count), (size_t)ncells * 4);
+        if (!st) st = field_malloc(h, reinterpret_cast<void **>(&F.cursor), (size_t)ncells * 4);
+        if (!st) st = field_malloc(h, reinterpret_cast<void **>(&F.start), ((size_t)ncells + 1) * 4);
+        if (!st) st = field_malloc(h, reinterpret_cast<void **>(&F.bsum), sw);
+        if (!st && hipMemsetAsync(F.bsum, 0, sw, h->stream) != hipSuccess) st = fail(h, WS_ERR_HIP, "density field scan state");
+        if (!st && hipMemcpyAsync(F.start + ncells, &n, 4, hipMemcpyHostToDevice, h->stream) != hipSuccess)
+            st = fail(h, WS_ERR_HIP, "density field cell starts");
+        if (!st && hipStreamSynchronize(h->stream) != hipSuccess) st = fail(h, WS_ERR_HIP, "density field scratch");
+        if (st) {
+            free_field(h, false);
+            return st;
+        }
+        F.cells = ncells;
+    }
+    return WS_OK;
+}
+
 void free_all(ws_handle *h)
 {
     if (h->stream) hipStreamSynchronize(h->stream);
@@ -649,6 +727,7 @@ void free_all(ws_handle *h)
     hipFree(h->stats); hipFree(h->mult); hipFree(h->stage);
     hipFree(h->v_keys); hipFree(h->v_perm); hipFree(h->v_tmp); hipFree(h->v_count);
     hipFree(h->v_cursor); hipFree(h->v_start); hipFree(h->v_bsum); hipFree(h->v_off);
+    free_field(h, true);
 #ifdef WS_WITH_REFCHECK
     ref_free(h);
 #endif
@@ -1279,6 +1358,129 @@ ws_status ws_read_sort_view(ws_handle *h, uint32_t *keys_by_id, uint32_t *perm, 
     if (perm) HIP_TRY(h, copy_now(h, perm, h->v_perm, (size_t)n * 4, hipMemcpyDeviceToHost));
     if (cell_offsets) HIP_TRY(h, copy_now(h, cell_offsets, h->v_off, (size_t)n * 4, hipMemcpyDeviceToHost));
     return WS_OK;
+}
+
+// ======================================================================================
+// density field (readback / render coupling)
+// ======================================================================================
+}  // extern "C"
+
+namespace {
+
+// Both sample calls.  grid6 = origin + spacing and dims (grid call) or nullptr (m points of xyz).
+ws_status sample_density(ws_handle *h, const float *xyz, uint32_t m, const float *grid6, const uint32_t *dims,
+                         float *out_rho, float *out_grad)
+{
+    if (!h) return WS_ERR_INVALID_ARG;
+    WS_DEAD_CHECK(h);
+    if (h->flags & WS_FLAG_REFERENCE_ORDER) return fail(h, WS_ERR_UNSUPPORTED, "density field: not in the reference-order validation mode");
+    const bool want = out_rho || out_grad;
+    if (!want && !h->slab) return fail(h, WS_ERR_INVALID_ARG, "density field: both outputs are NULL");
+    // (a slab rank validates its query only after the collective gather: a rank with a bad query leaves no peer waiting)
+    auto check = [&]() -> ws_status {
+        if (grid6) {
+            uint64_t nodes = 1;
+            for (int a = 0; a < 3; a++) {
+                if (!isfinite(grid6[a])) return fail(h, WS_ERR_INVALID_ARG, "density field: origin must be finite");
+                if (!(grid6[3 + a] > 0.0f) || !isfinite(grid6[3 + a]))
+                    return fail(h, WS_ERR_INVALID_ARG, "density field: spacing must be finite and > 0");
+                if (dims[a] == 0u) return fail(h, WS_ERR_INVALID_ARG, "density field: dims must be >= 1");
+                nodes *= dims[a];
+            }
+            if (nodes > (1ull << 31)) return fail(h, WS_ERR_INVALID_ARG, "density field: more than 2^31 nodes");
+        } else {
+            if (!xyz || m == 0u) return fail(h, WS_ERR_INVALID_ARG, "density field: no points");
+            for (size_t t = 0; t < (size_t)m * 3; t++)
+                if (!isfinite(xyz[t])) return fail(h, WS_ERR_INVALID_ARG, "density field: points must be finite");
+        }
+        return WS_OK;
+    };
+    if (!h->slab && want) {
+        const ws_status st = check();
+        if (st) return st;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    // the current positions by id, and the grid they are binned on
+    WsDev d = h->dev;
+    const float *pos = nullptr;
+    uint32_t n = h->n;
+    if (h->slab) {
+        ws_status st = slab_field_positions(h, &pos, &d);
+        if (st) return st;
+        n = h->slab->n_global;
+        if (!want) {
+            HIP_TRY(h, hipStreamSynchronize(s));
+            return WS_OK;
+        }
+        st = check();
+        if (st) {
+            HIP_TRY(h, hipStreamSynchronize(s));
+            return st;
+        }
+    }
+    auto &F = h->field;
+    ws_status st = field_alloc(h, n, d.ncells);
+    if (st) return st;
+    if (!h->slab) {
+        wsk_gather_positions(s, h->cur, F.xyz, n);
+        pos = F.xyz;
+    }
+    // counting sort by cell, ascending id inside a cell (the sort view's passes on the sampler's own arrays)
+    wsk_field_keys(s, d, pos, F.keys, n);
+    HIP_TRY(h, hipMemsetAsync(F.count, 0, (size_t)d.ncells * 4, s));
+    wsk_view_count(s, F.keys, F.count, n);
+    wsk_scan(s, F.count, F.start, F.cursor, F.bsum, d.ncells, false, 0);
+    wsk_scatter(s, F.keys, F.cursor, F.tmp, n, nullptr);
+    wsk_view_fix(s, F.tmp, F.keys, F.start, F.perm, n);
+    wsk_field_gather(s, F.perm, pos, F.spos, n);
+    HIP_TRY(h, hipGetLastError());
+    // queries and results
+    const uint64_t nq = grid6 ? (uint64_t)dims[0] * dims[1] * dims[2] : m;
+    if (!grid6) {
+        st = field_grow(h, &F.q, &F.q_bytes, (size_t)m * 12);
+        if (st) return st;
+        HIP_TRY(h, hipMemcpyAsync(F.q, xyz, (size_t)m * 12, hipMemcpyHostToDevice, s));
+    }
+    if (out_rho && (st = field_grow(h, &F.rho, &F.rho_bytes, (size_t)nq * 4))) return st;
+    if (out_grad && (st = field_grow(h, &F.grad, &F.grad_bytes, (size_t)nq * 12))) return st;
+    // the brick kernel from one node per cell up (spacing <= h on every axis); the points form below
+    const bool bricks = grid6 && grid6[3] <= d.h && grid6[4] <= d.h && grid6[5] <= d.h;
+    wsk_field_sample(s, d, F.start, F.spos, h->ieee, out_grad != nullptr, F.q, (uint32_t)nq, grid6, dims, bricks,
+                     out_rho ? F.rho : nullptr, out_grad ? F.grad : nullptr);
+    HIP_TRY(h, hipGetLastError());
+    if (out_rho) HIP_TRY(h, hipMemcpyAsync(out_rho, F.rho, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+    if (out_grad) HIP_TRY(h, hipMemcpyAsync(out_grad, F.grad, (size_t)nq * 12, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    drain_profile(h);
+    return WS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+ws_status ws_sample_density_grid(ws_handle *h, const float origin[3], const float spacing[3], const uint32_t dims[3],
+                                 float *out_density, float *out_gradient)
+{
+    if (!h) return WS_ERR_INVALID_ARG;
+    if ((out_density || out_gradient || !h->slab) && (!origin || !spacing || !dims))
+        return fail(h, WS_ERR_INVALID_ARG, "density field: origin, spacing and dims are required");
+    float g6[6] = {0.f, 0.f, 0.f, 1.f, 1.f, 1.f};
+    const uint32_t one[3] = {1u, 1u, 1u};
+    if (origin && spacing && dims) {
+        for (int a = 0; a < 3; a++) {
+            g6[a] = origin[a];
+            g6[3 + a] = spacing[a];
+        }
+    }
+    return sample_density(h, nullptr, 0, g6, dims ? dims : one, out_density, out_gradient);
+}
+
+ws_status ws_sample_density_points(ws_handle *h, const float *xyz, uint32_t m, float *out_density, float *out_gradient)
+{
+    if (!h) return WS_ERR_INVALID_ARG;
+    return sample_density(h, xyz, m, nullptr, nullptr, out_density, out_gradient);
 }
 
 // ======================================================================================

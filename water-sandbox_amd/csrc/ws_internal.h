@@ -229,6 +229,19 @@ struct ws_handle {
     uint32_t *v_keys = nullptr, *v_perm = nullptr, *v_tmp = nullptr, *v_count = nullptr,
              *v_cursor = nullptr, *v_start = nullptr, *v_bsum = nullptr, *v_off = nullptr;
 
+    // density field sampler (ws_sample_density_grid / _points): its own counting sort of the CURRENT positions, allocated
+    // on the first sample call, rebuilt when the grid changes, freed by ws_destroy.  Nothing ws_step reads is written.
+    struct {
+        float *xyz = nullptr;      // positions by id (single-GPU handles; a slab samples the gathered S->g_out)
+        uint32_t *keys = nullptr, *tmp = nullptr, *perm = nullptr;  // cell id by id, tentative slots, sorted ids
+        float4 *spos = nullptr;    // {position, id} in cell order, id inside a cell
+        uint32_t n = 0;            // particles the arrays hold
+        uint32_t *count = nullptr, *cursor = nullptr, *start = nullptr, *bsum = nullptr;  // ncells (+ 1) per-cell words
+        uint32_t cells = 0;        // cells the tables describe
+        float *q = nullptr, *rho = nullptr, *grad = nullptr;  // query points and results on the device
+        size_t q_bytes = 0, rho_bytes = 0, grad_bytes = 0;
+    } field;
+
     // profiling
     std::vector<WsEventPair> pending;
     std::vector<hipEvent_t> pool;
@@ -390,6 +403,13 @@ void wsk_view_fix(hipStream_t s, const uint32_t *tmp, const uint32_t *keys, cons
 void wsk_view_offsets(hipStream_t s, const uint32_t *start, uint32_t *off, uint32_t n);
 void wsk_iota(hipStream_t s, uint32_t *p, uint32_t n);
 void wsk_set_words4(hipStream_t s, uint32_t *p, uint32_t a, uint32_t b, uint32_t c, uint32_t d);
+// density field sampler (ws_sample_density_*)
+void wsk_field_keys(hipStream_t s, const WsDev &d, const float *xyz, uint32_t *keys, uint32_t n);
+void wsk_field_gather(hipStream_t s, const uint32_t *perm, const float *xyz, float4 *spos, uint32_t n);
+// grid6 = origin xyz, spacing xyz (nullptr: the m points of xyz); bricks: the brick kernel (grid only)
+void wsk_field_sample(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, bool ieee, bool grad_on,
+                      const float *xyz, uint32_t m, const float *grid6, const uint32_t *dims, bool bricks, float *rho,
+                      float *grad);
 // slabs
 void wsk_migrate_mark(hipStream_t s, const WsDev &d, WsSoA cur, uint32_t *cid_cur, uint32_t *count);
 void wsk_migrate_fill(hipStream_t s, const WsDev &d, uint32_t world, uint32_t me, uint32_t cap, uint32_t *dyn,

@@ -2624,3 +2624,263 @@ void wsk_slab_select(hipStream_t s, const WsDev &d, int src, const uint32_t *cut
 #ifdef WS_WITH_REFCHECK
 #include "ws_refcheck.inc"
 #endif
+
+// ---------------------------------------------------------------------------------
+// density field sampler (ws_sample_density_grid / _points; never inside ws_step)
+//
+// The field at a query point o is sum over particles p with !(d2 > d2_accept) of sk_density(|x_p - o|), and its gradient
+// sum of sk_der(d) * (o - x_p) / d -- the reference's smoothing_kernel / smoothing_kernel_derivative
+// (assets/simulation.wgsl:93-107) with d2 and d formed exactly as K4 forms them (e = x_p - o).  The particles are the
+// CURRENT positions, binned by the sampler itself into arrays of its own (the step's sorted arrays describe the
+// predicted positions the last step started from): keys = grid_cell(position) by id, then the sort view's count / scan /
+// scatter / rank-by-id (k_view_count, k_scan, k_scatter, k_view_fix) and k_field_gather.  Candidates are visited in
+// increasing linear cell id and, inside a cell, by particle id, whatever kernel visits them: the sums are a function of
+// the particle set and the query point alone.  Neither the multiplicity path (ALIAS) nor the tile schedule applies.
+// ---------------------------------------------------------------------------------
+__global__ void __launch_bounds__(WS_BLOCK) k_field_keys(WsDev d, const float *__restrict__ xyz, uint32_t *__restrict__ keys,
+                                                         uint32_t n)
+{
+    const uint32_t i = blockIdx.x * WS_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    keys[i] = grid_cell(d, xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2]);
+}
+
+void wsk_field_keys(hipStream_t s, const WsDev &d, const float *xyz, uint32_t *keys, uint32_t n)
+{
+    hipLaunchKernelGGL(k_field_keys, dim3(cdiv(n, WS_BLOCK)), dim3(WS_BLOCK), 0, s, d, xyz, keys, n);
+}
+
+// sorted copy: spos[j] = {position of particle perm[j], its id (bits)}
+__global__ void __launch_bounds__(WS_BLOCK) k_field_gather(const uint32_t *__restrict__ perm, const float *__restrict__ xyz,
+                                                           float4 *__restrict__ spos, uint32_t n)
+{
+    const uint32_t j = blockIdx.x * WS_BLOCK + threadIdx.x;
+    if (j >= n) return;
+    const size_t id = perm[j];
+    spos[j] = make_float4(xyz[3 * id], xyz[3 * id + 1], xyz[3 * id + 2], __uint_as_float((uint32_t)id));
+}
+
+void wsk_field_gather(hipStream_t s, const uint32_t *perm, const float *xyz, float4 *spos, uint32_t n)
+{
+    hipLaunchKernelGGL(k_field_gather, dim3(cdiv(n, WS_BLOCK)), dim3(WS_BLOCK), 0, s, perm, xyz, spos, n);
+}
+
+// Cell coordinate of x along axis a of a single-GPU (or gathered global) grid: the per-axis part of grid_cell.
+__device__ __forceinline__ int field_axis_cell(const WsDev &d, int a, float x)
+{
+    const float f = floorf(x / d.h) - (float)d.org[a];
+    int g = (int)fminf(fmaxf(f, 0.0f), (float)(d.fdim[a] - 1));
+    if (d.coarse) g /= d.cm[a];
+    return g;
+}
+
+// node (i, j, k) of the grid: fl(origin + fl((float)i * spacing)) per axis
+struct WsFieldGrid {
+    float ox, oy, oz, sx, sy, sz;
+    uint32_t nx, ny, nz;
+};
+__device__ __forceinline__ float4 field_node(const WsFieldGrid &g, uint32_t i, uint32_t j, uint32_t k)
+{
+    return make_float4(g.ox + (float)i * g.sx, g.oy + (float)j * g.sy, g.oz + (float)k * g.sz, 0.f);
+}
+
+struct FieldAcc {
+    float rho, gx, gy, gz;
+};
+
+// One accepted pair.  (ex, ey, ez) = x_p - o (K4's e), d2 its squared length.  Gradient term (o - x_p) * W'(d) / d:
+// IEEE = ((o - x_p) / d) * W'(d) with correctly rounded sqrt and division; default = (o - x_p) * (W'(d) * rcp(d)) with
+// the hardware v_sqrt_f32 / v_rcp_f32 -- the two forms K5 uses for its direction.  d == 0 contributes no gradient.
+template <bool IEEE, bool GRAD>
+__device__ __forceinline__ void field_pair(const WsDev &d, float ex, float ey, float ez, float d2, FieldAcc &a)
+{
+    const float dst = ws_sqrt<IEEE>(d2);
+    a.rho += sk_density(d, dst);
+    if constexpr (GRAD) {
+        const float slope = sk_der(d, dst);
+        const bool apart = dst > 0.f;
+        if constexpr (IEEE) {
+            const WsDivisor<IEEE> by_dst(dst);
+            a.gx += apart ? by_dst(-ex) * slope : 0.f;
+            a.gy += apart ? by_dst(-ey) * slope : 0.f;
+            a.gz += apart ? by_dst(-ez) * slope : 0.f;
+        } else {
+            const float s = slope * __builtin_amdgcn_rcpf(dst);
+            a.gx += apart ? -ex * s : 0.f;
+            a.gy += apart ? -ey * s : 0.f;
+            a.gz += apart ? -ez * s : 0.f;
+        }
+    }
+}
+
+// The definition: the 27 cells around the query's (clamped) cell, as 9 contiguous z-runs in increasing cell id.
+// start has ncells + 1 entries (start[ncells] = n).
+template <bool IEEE, bool GRAD>
+__device__ __forceinline__ FieldAcc field_sweep(const WsDev &d, const uint32_t *__restrict__ start, const float4 *__restrict__ spos,
+                                                float4 o)
+{
+    FieldAcc a = {0.f, 0.f, 0.f, 0.f};
+    const int cx = field_axis_cell(d, 0, o.x), cy = field_axis_cell(d, 1, o.y), cz = field_axis_cell(d, 2, o.z);
+    const int z0 = max(cz - 1, 0), z1 = min(cz + 1, d.dim[2] - 1);
+    for (int x = max(cx - 1, 0); x <= min(cx + 1, d.dim[0] - 1); x++) {
+        for (int y = max(cy - 1, 0); y <= min(cy + 1, d.dim[1] - 1); y++) {
+            const uint32_t col = (uint32_t)(x * d.dim[1] + y) * (uint32_t)d.dim[2];
+            const uint32_t b = start[col + z0], e = start[col + z1 + 1];
+            for (uint32_t j = b; j < e; j++) {
+                const float4 q = spos[j];
+                const float ex = q.x - o.x, ey = q.y - o.y, ez = q.z - o.z;
+                const float d2 = ex * ex + ey * ey + ez * ez;
+                if (d2 > d.d2_accept) continue;
+                field_pair<IEEE, GRAD>(d, ex, ey, ez, d2, a);
+            }
+        }
+    }
+    return a;
+}
+
+__device__ __forceinline__ void field_store(const FieldAcc &a, size_t at, float *__restrict__ rho, float *__restrict__ grad)
+{
+    if (rho) rho[at] = a.rho;
+    if (grad) {
+        grad[3 * at] = a.gx;
+        grad[3 * at + 1] = a.gy;
+        grad[3 * at + 2] = a.gz;
+    }
+}
+
+// Points form: one lane per query.  GRID = the queries are the nodes of g (node index = lane index, x fastest) -- the
+// grid call's form below one node per cell; otherwise the m points of xyz.
+template <bool IEEE, bool GRAD, bool GRID>
+__global__ void __launch_bounds__(WS_BLOCK) k_field_points(WsDev d, const uint32_t *__restrict__ start, const float4 *__restrict__ spos,
+                                                           const float *__restrict__ xyz, WsFieldGrid g, uint32_t m,
+                                                           float *__restrict__ rho, float *__restrict__ grad)
+{
+    const uint32_t t = blockIdx.x * WS_BLOCK + threadIdx.x;
+    if (t >= m) return;
+    float4 o;
+    if constexpr (GRID) {
+        const uint32_t i = t % g.nx, r = t / g.nx;
+        o = field_node(g, i, r % g.ny, r / g.ny);
+    } else {
+        o = make_float4(xyz[3 * (size_t)t], xyz[3 * (size_t)t + 1], xyz[3 * (size_t)t + 2], 0.f);
+    }
+    field_store(field_sweep<IEEE, GRAD>(d, start, spos, o), t, rho, grad);
+}
+
+// Grid form (the hot path): one wave per brick of 4 x 4 x 4 nodes, lane l = node (l & 3, (l >> 2) & 3, l >> 4) of the
+// brick.  The brick's support is the box of cells [first node's cell - 1, last node's cell + 1] per axis (clamped to
+// the grid; cell coordinates are monotone in the node index), i.e. at most 64 z-runs (one per (x, y) column, x
+// slower) when the node spacing is at most h.  The wave stages the runs' candidates into LDS in that order -- which
+// is increasing cell id, then particle id -- a chunk at a time, and every lane tests every staged candidate against
+// its node.  A candidate counts for a node iff it passes the distance test AND lies in the node's own 27 cells (the
+// points form never sees the others; the cell test is made on accepted candidates only), so each node sums the same
+// terms in the same order as the points form: bit-identical.  A brick whose support holds no particle (air) writes
+// zeros without a candidate loop.
+#define FB_CHUNK 512  // staged candidates (8 KiB of LDS per wave)
+#define FB_COLS 64    // z-runs a brick may span (6 x 6 = 36 at spacing h; more only through rounding at exactly h)
+
+// staged candidate: xyz and the cell relative to the brick's first cell, one byte per axis + 1 (w lane)
+__device__ __forceinline__ uint32_t field_pack_cell(int x, int y, int z) { return (uint32_t)((x + 1) << 16 | (y + 1) << 8 | (z + 1)); }
+
+template <bool IEEE, bool GRAD>
+__global__ void __launch_bounds__(64) k_field_bricks(WsDev d, const uint32_t *__restrict__ start, const float4 *__restrict__ spos,
+                                                     WsFieldGrid g, uint32_t bx_n, uint32_t by_n, float *__restrict__ rho,
+                                                     float *__restrict__ grad)
+{
+    __shared__ float4 s_q[FB_CHUNK];
+    __shared__ uint32_t s_pre[FB_COLS + 1], s_b[FB_COLS];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t bid = blockIdx.x;
+    const uint32_t bi = bid % bx_n, bj = (bid / bx_n) % by_n, bk = bid / (bx_n * by_n);
+    const uint32_t i0 = bi * 4u, j0 = bj * 4u, k0 = bk * 4u;
+    const uint32_t i = i0 + (lane & 3u), j = j0 + ((lane >> 2) & 3u), k = k0 + (lane >> 4);
+    const bool valid = i < g.nx && j < g.ny && k < g.nz;
+    const float4 o = field_node(g, i, j, k);
+    // the brick's cell box from its first and last VALID node (wave-uniform)
+    const uint32_t il = min(i0 + 3u, g.nx - 1u), jl = min(j0 + 3u, g.ny - 1u), kl = min(k0 + 3u, g.nz - 1u);
+    const float4 lo = field_node(g, i0, j0, k0), hi = field_node(g, il, jl, kl);
+    const int x0 = max(field_axis_cell(d, 0, lo.x) - 1, 0), x1 = min(field_axis_cell(d, 0, hi.x) + 1, d.dim[0] - 1);
+    const int y0 = max(field_axis_cell(d, 1, lo.y) - 1, 0), y1 = min(field_axis_cell(d, 1, hi.y) + 1, d.dim[1] - 1);
+    const int z0 = max(field_axis_cell(d, 2, lo.z) - 1, 0), z1 = min(field_axis_cell(d, 2, hi.z) + 1, d.dim[2] - 1);
+    const int ny_c = y1 - y0 + 1;
+    const int ncol = (x1 - x0 + 1) * ny_c;
+    const size_t at = ((size_t)k * g.ny + j) * g.nx + i;
+    if (ncol > FB_COLS) {  // (a spacing the host would not send here: take the points form, lane by lane)
+        if (valid) field_store(field_sweep<IEEE, GRAD>(d, start, spos, o), at, rho, grad);
+        return;
+    }
+    // the runs: lane c = column c (x slower), then an exclusive scan of their lengths
+    uint32_t len = 0, b = 0;
+    if ((int)lane < ncol) {
+        const int x = x0 + (int)lane / ny_c, y = y0 + (int)lane % ny_c;
+        const uint32_t col = (uint32_t)(x * d.dim[1] + y) * (uint32_t)d.dim[2];
+        b = start[col + z0];
+        len = start[col + z1 + 1] - b;
+    }
+    const uint32_t incl = wave_incl_scan(len);
+    const uint32_t total = __shfl(incl, 63, 64);
+    FieldAcc a = {0.f, 0.f, 0.f, 0.f};
+    if (total != 0u) {
+        s_pre[lane] = incl - len;
+        s_b[lane] = b;
+        if (lane == 0) s_pre[FB_COLS] = total;
+        // this lane's node: its 27 cells, relative to the brick's box (fields >= 0; see field_pack_cell)
+        const uint32_t own = (uint32_t)((field_axis_cell(d, 0, o.x) - x0) << 16 | (field_axis_cell(d, 1, o.y) - y0) << 8 |
+                                        (field_axis_cell(d, 2, o.z) - z0));
+        for (uint32_t base = 0; base < total; base += FB_CHUNK) {
+            const uint32_t cnt = min((uint32_t)FB_CHUNK, total - base);
+            __syncthreads();  // (the previous chunk has been consumed; s_pre / s_b are written)
+            for (uint32_t t = lane; t < cnt; t += 64u) {
+                const uint32_t v = base + t;
+                int lo_c = 0, hi_c = ncol - 1;  // last column whose prefix is <= v (empty columns share a prefix)
+                while (lo_c < hi_c) {
+                    const int mid = (lo_c + hi_c + 1) >> 1;
+                    if (s_pre[mid] <= v) lo_c = mid;
+                    else hi_c = mid - 1;
+                }
+                const float4 q = spos[s_b[lo_c] + (v - s_pre[lo_c])];
+                const uint32_t code = field_pack_cell(lo_c / ny_c, lo_c % ny_c, field_axis_cell(d, 2, q.z) - z0);
+                s_q[t] = make_float4(q.x, q.y, q.z, __uint_as_float(code));
+            }
+            __syncthreads();
+            for (uint32_t t = 0; t < cnt; t++) {
+                const float4 q = s_q[t];
+                const float ex = q.x - o.x, ey = q.y - o.y, ez = q.z - o.z;
+                const float d2 = ex * ex + ey * ey + ez * ez;
+                if (d2 > d.d2_accept) continue;
+                // in the node's 27 cells: every byte of code - own lies in [0, 2] (guard bit 7 keeps the bytes apart)
+                if ((((__float_as_uint(q.w) | 0x808080u) - own) & 0xFCFCFCu) != 0x808080u) continue;
+                field_pair<IEEE, GRAD>(d, ex, ey, ez, d2, a);
+            }
+        }
+    }
+    if (valid) field_store(a, at, rho, grad);
+}
+
+void wsk_field_sample(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, bool ieee, bool grad_on,
+                      const float *xyz, uint32_t m, const float *grid6, const uint32_t *dims, bool bricks, float *rho,
+                      float *grad)
+{
+    WsFieldGrid g = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0u, 0u, 0u};
+    if (grid6) g = {grid6[0], grid6[1], grid6[2], grid6[3], grid6[4], grid6[5], dims[0], dims[1], dims[2]};
+    if (grid6 && bricks) {
+        const uint32_t bx = cdiv(dims[0], 4u), by = cdiv(dims[1], 4u), bz = cdiv(dims[2], 4u);
+        const dim3 grid(bx * by * bz);
+#define FB_LAUNCH(I, G) hipLaunchKernelGGL((k_field_bricks<I, G>), grid, dim3(64), 0, s, d, start, spos, g, bx, by, rho, grad)
+        if (ieee) { if (grad_on) FB_LAUNCH(true, true); else FB_LAUNCH(true, false); }
+        else { if (grad_on) FB_LAUNCH(false, true); else FB_LAUNCH(false, false); }
+#undef FB_LAUNCH
+        return;
+    }
+    const dim3 grid(cdiv(m, WS_BLOCK));
+#define FP_LAUNCH(I, G, R) \
+    hipLaunchKernelGGL((k_field_points<I, G, R>), grid, dim3(WS_BLOCK), 0, s, d, start, spos, xyz, g, m, rho, grad)
+    if (grid6) {
+        if (ieee) { if (grad_on) FP_LAUNCH(true, true, true); else FP_LAUNCH(true, false, true); }
+        else { if (grad_on) FP_LAUNCH(false, true, true); else FP_LAUNCH(false, false, true); }
+    } else {
+        if (ieee) { if (grad_on) FP_LAUNCH(true, true, false); else FP_LAUNCH(true, false, false); }
+        else { if (grad_on) FP_LAUNCH(false, true, false); else FP_LAUNCH(false, false, false); }
+    }
+#undef FP_LAUNCH
+}

@@ -1139,6 +1139,21 @@ ws_status slab_regrid(ws_handle *h, const ws_params *params, bool rebalance)
     return WS_OK;
 }
 
+// ws_sample_density_* on a slab handle (COLLECTIVE): every rank's current positions all-gathered by id into S->g_out
+// (what ws_read_positions does) and the GLOBAL single-GPU grid, so that the single-GPU binning and sampler run on the
+// whole particle set -- bit-identical to a single handle by construction.  (A ghost-layer sampler that avoids the
+// all-gather is the scale-out follow-up: DESIGN.md 8.)
+ws_status slab_field_positions(ws_handle *h, const float **xyz, WsDev *global)
+{
+    WsSlab *S = h->slab;
+    ws_status st = slab_gather_by_id(h, WS_PACK_POS_H);
+    if (st) return st;
+    st = global_grid(&h->params, S->n_global, global);
+    if (st) return fail(h, st, g_create_error.c_str());
+    *xyz = reinterpret_cast<const float *>(S->g_out);
+    return WS_OK;
+}
+
 }  // namespace
 
 extern "C" {

@@ -49,6 +49,7 @@ ABI_SYMBOLS = [
     "ws_local_hub_create", "ws_local_hub_destroy", "ws_local_transport_create", "ws_local_transport_destroy", "ws_read_sort_view", "ws_last_error", "ws_num_particles",
     "ws_steps_done", "ws_kernel_name", "ws_profile_read", "ws_profile_reset", "ws_profile_select",
     "ws_grid_dims", "ws_read_stats", "ws_slab_assign", "ws_slab_create", "ws_slab_read_particles", "ws_slab_rebalance", "ws_slab_balanced_cuts",
+    "ws_sample_density_grid", "ws_sample_density_points",
 ]
 
 
@@ -158,7 +159,39 @@ def bind_library(path):
     L.ws_profile_select.argtypes = [vp, u32]
     L.ws_grid_dims.argtypes = [vp, vp]
     L.ws_read_stats.argtypes = [vp, vp]
+    L.ws_sample_density_grid.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.ws_sample_density_points.argtypes = [vp, vp, u32, vp, vp]
     return L
+
+
+def sample_density_grid(L, h, check, origin, spacing, dims, gradient=False, want=True):
+    """ws_sample_density_grid: (density (nz, ny, nx), gradient (nz, ny, nx, 3) or None); dims = (nx, ny, nz).
+    want=False (slab handles): contribute to the collective call and return (None, None)."""
+    o = np.ascontiguousarray(origin, np.float32).reshape(3)
+    sp = np.ascontiguousarray(spacing, np.float32).reshape(3)
+    d = np.ascontiguousarray(dims, np.uint32).reshape(3)
+    if not want:
+        check(L.ws_sample_density_grid(h, o.ctypes.data, sp.ctypes.data, d.ctypes.data, None, None))
+        return None, None
+    nx, ny, nz = (int(v) for v in d)
+    rho = np.empty((nz, ny, nx), np.float32)
+    grad = np.empty((nz, ny, nx, 3), np.float32) if gradient else None
+    check(L.ws_sample_density_grid(h, o.ctypes.data, sp.ctypes.data, d.ctypes.data, rho.ctypes.data,
+                                   grad.ctypes.data if gradient else None))
+    return rho, grad
+
+
+def sample_density_points(L, h, check, xyz, gradient=False, want=True):
+    """ws_sample_density_points: (density (m,), gradient (m, 3) or None)."""
+    q = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    m = q.shape[0]
+    if not want:
+        check(L.ws_sample_density_points(h, q.ctypes.data, m, None, None))
+        return None, None
+    rho = np.empty(m, np.float32)
+    grad = np.empty((m, 3), np.float32) if gradient else None
+    check(L.ws_sample_density_points(h, q.ctypes.data, m, rho.ctypes.data, grad.ctypes.data if gradient else None))
+    return rho, grad
 
 
 # ---------------------------------------------------------------------------------------
@@ -339,6 +372,17 @@ class FluidWorker:
         off = np.empty(self.n, np.uint32)
         self._check(self._L.ws_read_sort_view(self._h, keys.ctypes.data, perm.ctypes.data, off.ctypes.data))
         return keys, perm, off
+
+    def sample_density_grid(self, origin, spacing, dims, gradient=False):
+        """The SPH density field of the current positions at the nodes origin + (i, j, k) * spacing, dims = (nx, ny, nz):
+        a float32 array of shape (nz, ny, nx) (x fastest), with gradient=True also its gradient, shape (nz, ny, nx, 3)."""
+        rho, grad = sample_density_grid(self._L, self._h, self._check, origin, spacing, dims, gradient)
+        return (rho, grad) if gradient else rho
+
+    def sample_density_points(self, xyz, gradient=False):
+        """The same field at m points (xyz: (m, 3)): shape (m,), with gradient=True also (m, 3)."""
+        rho, grad = sample_density_points(self._L, self._h, self._check, xyz, gradient)
+        return (rho, grad) if gradient else rho
 
     def steps_done(self):
         return int(self._L.ws_steps_done(self._h))

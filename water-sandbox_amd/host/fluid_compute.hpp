@@ -198,6 +198,19 @@ class FluidWorker {
     void pin(std::vector<Vec3> &buf) { check(ws_pin_host_buffer(h_, buf.data(), buf.size() * sizeof(Vec3))); }
     void unpin(std::vector<Vec3> &buf) { check(ws_unpin_host_buffer(h_, buf.data())); }
     // velocities.length() per particle: the input of update_particle_color, :489-502
+    // The SPH density field of the current positions at the nodes origin + (i, j, k) * spacing (ws_sample_density_grid):
+    // dims[0] * dims[1] * dims[2] values, x fastest; with a gradient vector, 3 floats per node in the same order.
+    std::vector<float> sample_density_grid(const Vec3 &origin, const Vec3 &spacing, const uint32_t dims[3],
+                                           std::vector<float> *gradient = nullptr)
+    {
+        const size_t nodes = (size_t)dims[0] * dims[1] * dims[2];
+        std::vector<float> out(nodes);
+        if (gradient) gradient->resize(nodes * 3);
+        check(ws_sample_density_grid(h_, reinterpret_cast<const float *>(&origin), reinterpret_cast<const float *>(&spacing),
+                                     dims, out.data(), gradient ? gradient->data() : nullptr));
+        return out;
+    }
+
     std::vector<float> read_speeds()
     {
         std::vector<float> out(n_);

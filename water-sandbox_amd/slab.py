@@ -368,6 +368,16 @@ class SlabWorker:
         self._check(self._L.ws_read_positions(self._h, out.ctypes.data if want else None))
         return out
 
+    def sample_density_grid(self, origin, spacing, dims, gradient=False, want=True):
+        """FluidWorker.sample_density_grid over the GLOBAL particle set (COLLECTIVE); want=False: only contribute (None)."""
+        rho, grad = fluid.sample_density_grid(self._L, self._h, self._check, origin, spacing, dims, gradient, want)
+        return (rho, grad) if gradient else rho
+
+    def sample_density_points(self, xyz, gradient=False, want=True):
+        """FluidWorker.sample_density_points over the GLOBAL particle set (COLLECTIVE); want=False: only contribute."""
+        rho, grad = fluid.sample_density_points(self._L, self._h, self._check, xyz, gradient, want)
+        return (rho, grad) if gradient else rho
+
     def read_positions_begin(self, buf):
         assert buf.dtype == np.float32 and buf.shape == (self.n_global, 3) and buf.flags.c_contiguous
         self._check(self._L.ws_read_positions_begin(self._h, buf.ctypes.data))
