@@ -415,6 +415,53 @@ ws_status ws_sample_density_grid(ws_handle *h, const float origin[3], const floa
 /* The same field at m arbitrary points (xyz: m*3 floats). */
 ws_status ws_sample_density_points(ws_handle *h, const float *xyz, uint32_t m, float *out_density, float *out_gradient);
 
+/* The fluid's surface, rho = iso, as a triangle mesh (marching tetrahedra on the sampled grid).  The volume
+ * never leaves the device: only vertices, normals and triangles are copied out.  A pure function of the grid field:
+ *   Field: exactly what ws_sample_density_grid returns for the same origin, spacing and dims (density, gradient, node
+ *     coordinates fl(origin + fl(i * spacing)), the handle's arithmetic).  A node is INSIDE iff rho >= iso.
+ *   Edges and vertices: node n = (i, j, k) has 7 forward edges of type d = 1..7, to n + (d & 1, d >> 1 & 1, d >> 2 & 1)
+ *     when that node exists.  An edge is crossed iff its ends differ in "inside"; each crossed edge carries one vertex,
+ *     at t = (iso - rho_a) / (rho_b - rho_a), p = p_a + t * (p_b - p_a) per axis (a = n, b = its neighbour; every
+ *     operation rounded to float, divisions correctly rounded).  Vertices are ordered by the node's linear index
+ *     (k * ny + j) * nx + i, then by d.
+ *   Normals: g = g_a + t * (g_b - g_a) per axis, n = -g / sqrtf(g.g), g.g = gx*gx + gy*gy + gz*gz left to right,
+ *     correctly rounded sqrt and divisions; (0, 0, 0) where g.g == 0.  This arithmetic is IEEE whatever the handle's
+ *     flags: only the sampled field follows WS_FLAG_IEEE_DIVISION.
+ *   Tetrahedra: the cube at n exists when i < nx-1, j < ny-1, k < nz-1; corner c = 0..7 lies at
+ *     n + (c & 1, c >> 1 & 1, c >> 2 & 1).  It is split along its 0-7 diagonal into six tets, in this order:
+ *     {0,1,3,7} {0,1,5,7} {0,2,3,7} {0,2,6,7} {0,4,5,7} {0,4,6,7} (corners q0 q1 q2 q3 as listed).  A tet edge (u, v)
+ *     has u a bitwise subset of v: it is the forward edge of type u ^ v at node n + u.  Neighbouring cubes cut their
+ *     shared face along the same diagonal, so the mesh has no cracks and needs no ambiguity table.
+ *   Triangles: case s = sum of 2^k over the tet's inside corners q_k.  Local edges 0..5 = (q0 q1) (q0 q2) (q0 q3)
+ *     (q1 q2) (q1 q3) (q2 q3).  Triangles per case, as local edges (v0 v1 v2):
+ *        1: 0 1 2     2: 0 4 3     4: 1 3 5     8: 2 5 4
+ *       14: 0 2 1    13: 0 3 4    11: 1 5 3     7: 2 4 5
+ *        3: 1 2 4, 1 4 3     12: 1 3 4, 1 4 2
+ *        5: 2 0 3, 2 3 5     10: 3 0 2, 3 2 5
+ *        9: 0 1 5, 0 5 4      6: 0 4 5, 0 5 1       (0 and 15: none)
+ *     Tets 1, 2 and 5 are negatively oriented (det(q1 - q0, q2 - q0, q3 - q0) < 0): their triangles are written as
+ *     (v0 v2 v1).  So (v1 - v0) x (v2 - v0) points from the inside corners to the outside ones: out of the fluid.
+ *     Triangles are ordered by cube (linear index of its corner 0), then tet 0..5, then table order; out_tri holds
+ *     three vertex indices (0-based, into out_xyz) per triangle.
+ *   Counts and capacity, like snprintf: on WS_OK *n_vertices and *n_triangles hold the full counts.  The mesh (out_xyz
+ *     3 floats per vertex, out_normal the same, out_tri) is written only when out_xyz and out_tri are both non-NULL and
+ *     both counts fit max_vertices / max_triangles; otherwise nothing else is written.  The gradient is sampled only
+ *     when out_normal, out_xyz and out_tri are all non-NULL (out_normal == NULL: neither sampled nor copied).
+ *   Boundary: the surface is clipped open at the grid's boundary.  If every boundary node is outside (a grid reaching
+ *     h beyond the fluid) the mesh is closed: every edge is shared by exactly two triangles, in opposite directions.
+ *     A node whose density equals iso exactly may give zero-area triangles.
+ * Waits for enqueued steps.  Nothing ws_step reads is written.  Slab handles: COLLECTIVE (the global particle set,
+ * bit-identical to a single handle); a rank that passes all five outputs NULL only contributes, and a rank validates
+ * its query (origin, spacing and dims included) only after the gather, so a refused rank leaves no peer waiting.
+ * Errors: WS_ERR_INVALID_ARG (NULL handle, origin, spacing or dims; NULL count pointers on a rank that wants output; a
+ * dims entry < 2; a non-finite origin; spacing <= 0 or non-finite; iso <= 0 or non-finite; more than 2^28 nodes, which
+ * keeps every vertex id below 2^31 and the triangle count below 2^32), WS_ERR_UNSUPPORTED (WS_FLAG_REFERENCE_ORDER
+ * handles), WS_ERR_OUT_OF_MEMORY (scratch allocation failed: the handle stays usable), WS_ERR_HIP on an unusable handle. */
+ws_status ws_extract_surface(ws_handle *h, const float origin[3], const float spacing[3], const uint32_t dims[3],
+                             float iso, uint32_t max_vertices, uint32_t max_triangles,
+                             float *out_xyz, float *out_normal, uint32_t *out_tri,
+                             uint32_t *n_vertices, uint32_t *n_triangles);
+
 /* ---- introspection ------------------------------------------------------------- */
 const char *ws_last_error(ws_handle *h);
 uint32_t ws_num_particles(ws_handle *h);

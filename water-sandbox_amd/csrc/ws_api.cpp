@@ -646,6 +646,13 @@ void free_field(ws_handle *h, bool all)
     F.q = F.rho = F.grad = nullptr;
     F.n = 0;
     F.q_bytes = F.rho_bytes = F.grad_bytes = 0;
+    hipFree(F.code); hipFree(F.vbase); hipFree(F.bcnt); hipFree(F.bstart); hipFree(F.bstate); hipFree(F.tri);
+    hipFree(F.mxyz); hipFree(F.mnrm);
+    F.code = nullptr;
+    F.vbase = F.bcnt = F.bstart = F.bstate = F.tri = nullptr;
+    F.mxyz = F.mnrm = nullptr;
+    F.code_bytes = F.vbase_bytes = F.bcnt_bytes = F.bstart_bytes = F.bstate_bytes = F.tri_bytes = 0;
+    F.mxyz_bytes = F.mnrm_bytes = 0;
 }
 
 // An allocation of the sampler: a failure is WS_ERR_OUT_OF_MEMORY and leaves no sticky HIP error behind (the next
@@ -659,7 +666,8 @@ ws_status field_malloc(ws_handle *h, void **p, size_t bytes)
     return fail(h, WS_ERR_OUT_OF_MEMORY, "density field scratch", e);
 }
 
-ws_status field_grow(ws_handle *h, float **p, size_t *have, size_t need)
+template <class T>
+ws_status field_grow(ws_handle *h, T **p, size_t *have, size_t need)
 {
     if (*have >= need) return WS_OK;
     hipFree(*p);
@@ -1367,34 +1375,36 @@ ws_status ws_read_sort_view(ws_handle *h, uint32_t *keys_by_id, uint32_t *perm, 
 
 namespace {
 
-// Both sample calls.  grid6 = origin + spacing and dims (grid call) or nullptr (m points of xyz).
-ws_status sample_density(ws_handle *h, const float *xyz, uint32_t m, const float *grid6, const uint32_t *dims,
-                         float *out_rho, float *out_grad)
+// The query of a sample call.  grid6 = origin + spacing and dims (grid call) or nullptr (m points of xyz).
+ws_status field_check(ws_handle *h, const float *xyz, uint32_t m, const float *grid6, const uint32_t *dims)
 {
-    if (!h) return WS_ERR_INVALID_ARG;
-    WS_DEAD_CHECK(h);
-    if (h->flags & WS_FLAG_REFERENCE_ORDER) return fail(h, WS_ERR_UNSUPPORTED, "density field: not in the reference-order validation mode");
-    const bool want = out_rho || out_grad;
-    if (!want && !h->slab) return fail(h, WS_ERR_INVALID_ARG, "density field: both outputs are NULL");
-    // (a slab rank validates its query only after the collective gather: a rank with a bad query leaves no peer waiting)
-    auto check = [&]() -> ws_status {
-        if (grid6) {
-            uint64_t nodes = 1;
-            for (int a = 0; a < 3; a++) {
-                if (!isfinite(grid6[a])) return fail(h, WS_ERR_INVALID_ARG, "density field: origin must be finite");
-                if (!(grid6[3 + a] > 0.0f) || !isfinite(grid6[3 + a]))
-                    return fail(h, WS_ERR_INVALID_ARG, "density field: spacing must be finite and > 0");
-                if (dims[a] == 0u) return fail(h, WS_ERR_INVALID_ARG, "density field: dims must be >= 1");
-                nodes *= dims[a];
-            }
-            if (nodes > (1ull << 31)) return fail(h, WS_ERR_INVALID_ARG, "density field: more than 2^31 nodes");
-        } else {
-            if (!xyz || m == 0u) return fail(h, WS_ERR_INVALID_ARG, "density field: no points");
-            for (size_t t = 0; t < (size_t)m * 3; t++)
-                if (!isfinite(xyz[t])) return fail(h, WS_ERR_INVALID_ARG, "density field: points must be finite");
+    if (grid6) {
+        uint64_t nodes = 1;
+        for (int a = 0; a < 3; a++) {
+            if (!isfinite(grid6[a])) return fail(h, WS_ERR_INVALID_ARG, "density field: origin must be finite");
+            if (!(grid6[3 + a] > 0.0f) || !isfinite(grid6[3 + a]))
+                return fail(h, WS_ERR_INVALID_ARG, "density field: spacing must be finite and > 0");
+            if (dims[a] == 0u) return fail(h, WS_ERR_INVALID_ARG, "density field: dims must be >= 1");
+            nodes *= dims[a];
         }
-        return WS_OK;
-    };
+        if (nodes > (1ull << 31)) return fail(h, WS_ERR_INVALID_ARG, "density field: more than 2^31 nodes");
+    } else {
+        if (!xyz || m == 0u) return fail(h, WS_ERR_INVALID_ARG, "density field: no points");
+        for (size_t t = 0; t < (size_t)m * 3; t++)
+            if (!isfinite(xyz[t])) return fail(h, WS_ERR_INVALID_ARG, "density field: points must be finite");
+    }
+    return WS_OK;
+}
+
+// Bin the current positions and sample the field into device scratch: F.rho (rho_on) and F.grad (grad_on), nodes x
+// fastest or the m points.  check() validates the query: before anything else on a single handle, after the collective
+// gather on a slab rank (a rank with a bad query leaves no peer waiting).  *contributed: a slab rank that wants nothing
+// took part in the gather and has nothing more to do.  The caller has checked h and its mode.
+template <class Check>
+ws_status field_sample_device(ws_handle *h, const float *xyz, uint32_t m, const float *grid6, const uint32_t *dims,
+                              bool want, bool rho_on, bool grad_on, Check check, bool *contributed)
+{
+    *contributed = false;
     if (!h->slab && want) {
         const ws_status st = check();
         if (st) return st;
@@ -1411,6 +1421,7 @@ ws_status sample_density(ws_handle *h, const float *xyz, uint32_t m, const float
         n = h->slab->n_global;
         if (!want) {
             HIP_TRY(h, hipStreamSynchronize(s));
+            *contributed = true;
             return WS_OK;
         }
         st = check();
@@ -1442,16 +1453,104 @@ ws_status sample_density(ws_handle *h, const float *xyz, uint32_t m, const float
         if (st) return st;
         HIP_TRY(h, hipMemcpyAsync(F.q, xyz, (size_t)m * 12, hipMemcpyHostToDevice, s));
     }
-    if (out_rho && (st = field_grow(h, &F.rho, &F.rho_bytes, (size_t)nq * 4))) return st;
-    if (out_grad && (st = field_grow(h, &F.grad, &F.grad_bytes, (size_t)nq * 12))) return st;
+    if (rho_on && (st = field_grow(h, &F.rho, &F.rho_bytes, (size_t)nq * 4))) return st;
+    if (grad_on && (st = field_grow(h, &F.grad, &F.grad_bytes, (size_t)nq * 12))) return st;
     // the brick kernel from one node per cell up (spacing <= h on every axis); the points form below
     const bool bricks = grid6 && grid6[3] <= d.h && grid6[4] <= d.h && grid6[5] <= d.h;
-    wsk_field_sample(s, d, F.start, F.spos, h->ieee, out_grad != nullptr, F.q, (uint32_t)nq, grid6, dims, bricks,
-                     out_rho ? F.rho : nullptr, out_grad ? F.grad : nullptr);
+    wsk_field_sample(s, d, F.start, F.spos, h->ieee, grad_on, F.q, (uint32_t)nq, grid6, dims, bricks,
+                     rho_on ? F.rho : nullptr, grad_on ? F.grad : nullptr);
     HIP_TRY(h, hipGetLastError());
+    return WS_OK;
+}
+
+// Both sample calls: the field into device scratch, then copied out.
+ws_status sample_density(ws_handle *h, const float *xyz, uint32_t m, const float *grid6, const uint32_t *dims,
+                         float *out_rho, float *out_grad)
+{
+    if (!h) return WS_ERR_INVALID_ARG;
+    WS_DEAD_CHECK(h);
+    if (h->flags & WS_FLAG_REFERENCE_ORDER) return fail(h, WS_ERR_UNSUPPORTED, "density field: not in the reference-order validation mode");
+    const bool want = out_rho || out_grad;
+    if (!want && !h->slab) return fail(h, WS_ERR_INVALID_ARG, "density field: both outputs are NULL");
+    bool contributed = false;
+    const ws_status st = field_sample_device(h, xyz, m, grid6, dims, want, out_rho != nullptr, out_grad != nullptr,
+                                             [&]() { return field_check(h, xyz, m, grid6, dims); }, &contributed);
+    if (st || contributed) return st;
+    hipStream_t s = h->stream;
+    auto &F = h->field;
+    const uint64_t nq = grid6 ? (uint64_t)dims[0] * dims[1] * dims[2] : m;
     if (out_rho) HIP_TRY(h, hipMemcpyAsync(out_rho, F.rho, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
     if (out_grad) HIP_TRY(h, hipMemcpyAsync(out_grad, F.grad, (size_t)nq * 12, hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
+    drain_profile(h);
+    return WS_OK;
+}
+
+// ws_extract_surface: the grid field into device scratch, the node codes and per-workgroup totals, their scans, the
+// counts back to the host and -- when the caller's buffers hold them -- the mesh.  query = origin, spacing and dims were
+// given (grid6 / dims hold placeholders otherwise): a slab rank without them still takes part in the gather, then fails.
+ws_status extract_surface(ws_handle *h, bool query, const float *grid6, const uint32_t *dims, float iso, uint32_t max_v,
+                          uint32_t max_t, float *out_xyz, float *out_nrm, uint32_t *out_tri, uint32_t *n_v, uint32_t *n_t)
+{
+    WS_DEAD_CHECK(h);
+    if (h->flags & WS_FLAG_REFERENCE_ORDER) return fail(h, WS_ERR_UNSUPPORTED, "surface: not in the reference-order validation mode");
+    const bool want = out_xyz || out_nrm || out_tri || n_v || n_t;
+    // a single handle always wants the counts (field_sample_device validates a single handle's query only if it wants)
+    if (!h->slab && (!n_v || !n_t)) return fail(h, WS_ERR_INVALID_ARG, "surface: the count pointers are required");
+    auto check = [&]() -> ws_status {
+        if (!query) return fail(h, WS_ERR_INVALID_ARG, "surface: origin, spacing and dims are required");
+        if (!n_v || !n_t) return fail(h, WS_ERR_INVALID_ARG, "surface: the count pointers are required");
+        uint64_t nodes = 1;
+        for (int a = 0; a < 3; a++) {
+            if (dims[a] < 2u) return fail(h, WS_ERR_INVALID_ARG, "surface: dims must be >= 2");
+            nodes *= dims[a];
+        }
+        if (nodes > (1ull << 28)) return fail(h, WS_ERR_INVALID_ARG, "surface: more than 2^28 nodes");
+        if (!(iso > 0.0f) || !isfinite(iso)) return fail(h, WS_ERR_INVALID_ARG, "surface: iso must be finite and > 0");
+        return field_check(h, nullptr, 0, grid6, dims);
+    };
+    // the gradient only for a call that asks for normals and passes both mesh buffers (a call whose counts then exceed
+    // its capacities has sampled it for nothing; FluidWorker sizes its first guess from the previous mesh)
+    const bool grad_on = out_nrm && out_xyz && out_tri;
+    bool contributed = false;
+    ws_status st = field_sample_device(h, nullptr, 0, grid6, dims, want, true, grad_on, check, &contributed);
+    if (st || contributed) return st;
+    hipStream_t s = h->stream;
+    auto &F = h->field;
+    const size_t nodes = (size_t)dims[0] * dims[1] * dims[2];
+    const uint32_t nb = wsk_iso_blocks(dims);
+    const size_t half = ((size_t)nb + 4) & ~(size_t)3;  // nb + 1 totals, 16 B aligned for the scan's uint4 accesses
+    const size_t sw = (size_t)wsk_scan_state_words(nb + 1) * 4;
+    if ((st = field_grow(h, &F.code, &F.code_bytes, nodes))) return st;
+    if ((st = field_grow(h, &F.bcnt, &F.bcnt_bytes, 2 * half * 4))) return st;
+    if ((st = field_grow(h, &F.bstart, &F.bstart_bytes, (2 * half + 4) * 4))) return st;  // (+ the two grand totals)
+    if ((st = field_grow(h, &F.bstate, &F.bstate_bytes, sw))) return st;
+    // (the scan's tickets number its launches on a state buffer of a fixed length: fresh state for every call)
+    HIP_TRY(h, hipMemsetAsync(F.bstate, 0, sw, s));
+    wsk_iso_count(s, F.rho, grid6, dims, iso, F.code, F.bcnt, F.bcnt + half);
+    wsk_scan(s, F.bcnt, F.bstart, nullptr, F.bstate, nb + 1, false, 0);
+    wsk_scan(s, F.bcnt + half, F.bstart + half, nullptr, F.bstate, nb + 1, false, 0);
+    wsk_iso_totals(s, F.bstart + nb, F.bstart + half + nb, F.bstart + 2 * half);
+    HIP_TRY(h, hipGetLastError());
+    uint32_t counts[2] = {0u, 0u};
+    HIP_TRY(h, hipMemcpyAsync(counts, F.bstart + 2 * half, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    *n_v = counts[0];
+    *n_t = counts[1];
+    if (out_xyz && out_tri && counts[0] <= max_v && counts[1] <= max_t) {
+        const size_t V = counts[0], T = counts[1];
+        if ((st = field_grow(h, &F.vbase, &F.vbase_bytes, nodes * 4))) return st;
+        if ((st = field_grow(h, &F.mxyz, &F.mxyz_bytes, V * 12))) return st;
+        if (grad_on && (st = field_grow(h, &F.mnrm, &F.mnrm_bytes, V * 12))) return st;
+        if ((st = field_grow(h, &F.tri, &F.tri_bytes, T * 12))) return st;
+        wsk_iso_mesh(s, F.rho, F.grad, grid6, dims, iso, F.code, F.bstart, F.bstart + half, F.vbase, F.mxyz,
+                     grad_on ? F.mnrm : nullptr, F.tri);
+        HIP_TRY(h, hipGetLastError());
+        if (V) HIP_TRY(h, hipMemcpyAsync(out_xyz, F.mxyz, V * 12, hipMemcpyDeviceToHost, s));
+        if (V && grad_on) HIP_TRY(h, hipMemcpyAsync(out_nrm, F.mnrm, V * 12, hipMemcpyDeviceToHost, s));
+        if (T) HIP_TRY(h, hipMemcpyAsync(out_tri, F.tri, T * 12, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+    }
     drain_profile(h);
     return WS_OK;
 }
@@ -1481,6 +1580,26 @@ ws_status ws_sample_density_points(ws_handle *h, const float *xyz, uint32_t m, f
 {
     if (!h) return WS_ERR_INVALID_ARG;
     return sample_density(h, xyz, m, nullptr, nullptr, out_density, out_gradient);
+}
+
+ws_status ws_extract_surface(ws_handle *h, const float origin[3], const float spacing[3], const uint32_t dims[3], float iso,
+                             uint32_t max_vertices, uint32_t max_triangles, float *out_xyz, float *out_normal,
+                             uint32_t *out_tri, uint32_t *n_vertices, uint32_t *n_triangles)
+{
+    if (!h) return WS_ERR_INVALID_ARG;
+    const bool query = origin && spacing && dims;
+    // (a slab rank without a query fails after the collective gather: extract_surface's check)
+    if (!query && !h->slab) return fail(h, WS_ERR_INVALID_ARG, "surface: origin, spacing and dims are required");
+    float g6[6] = {0.f, 0.f, 0.f, 1.f, 1.f, 1.f};
+    const uint32_t two[3] = {2u, 2u, 2u};
+    if (query) {
+        for (int a = 0; a < 3; a++) {
+            g6[a] = origin[a];
+            g6[3 + a] = spacing[a];
+        }
+    }
+    return extract_surface(h, query, g6, query ? dims : two, iso, max_vertices, max_triangles, out_xyz, out_normal,
+                           out_tri, n_vertices, n_triangles);
 }
 
 // ======================================================================================

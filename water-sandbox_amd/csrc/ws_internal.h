@@ -240,6 +240,14 @@ struct ws_handle {
         uint32_t cells = 0;        // cells the tables describe
         float *q = nullptr, *rho = nullptr, *grad = nullptr;  // query points and results on the device
         size_t q_bytes = 0, rho_bytes = 0, grad_bytes = 0;
+        // surface extraction (ws_extract_surface): node codes and vertex bases, per-workgroup totals and their scans
+        // (2 x blocks + 1 words each, 16 B aligned halves; bstart also the two grand totals) and scan state, the mesh --
+        // all grow-only
+        uint8_t *code = nullptr;
+        uint32_t *vbase = nullptr, *bcnt = nullptr, *bstart = nullptr, *bstate = nullptr, *tri = nullptr;
+        float *mxyz = nullptr, *mnrm = nullptr;
+        size_t code_bytes = 0, vbase_bytes = 0, bcnt_bytes = 0, bstart_bytes = 0, bstate_bytes = 0, tri_bytes = 0,
+               mxyz_bytes = 0, mnrm_bytes = 0;
     } field;
 
     // profiling
@@ -410,6 +418,15 @@ void wsk_field_gather(hipStream_t s, const uint32_t *perm, const float *xyz, flo
 void wsk_field_sample(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, bool ieee, bool grad_on,
                       const float *xyz, uint32_t m, const float *grid6, const uint32_t *dims, bool bricks, float *rho,
                       float *grad);
+// surface extraction (ws_extract_surface) on a sampled grid: node codes and per-workgroup totals (wsk_iso_blocks() of
+// them, then one 0 each), then -- after two wsk_scan launches over blocks + 1 totals -- vertices and triangles
+uint32_t wsk_iso_blocks(const uint32_t *dims);
+void wsk_iso_totals(hipStream_t s, const uint32_t *v_total, const uint32_t *t_total, uint32_t *out);  // out[0..1]
+void wsk_iso_count(hipStream_t s, const float *rho, const float *grid6, const uint32_t *dims, float iso, uint8_t *code,
+                   uint32_t *vcnt, uint32_t *tcnt);
+void wsk_iso_mesh(hipStream_t s, const float *rho, const float *grad, const float *grid6, const uint32_t *dims, float iso,
+                  const uint8_t *code, const uint32_t *vstart, const uint32_t *tstart, uint32_t *vbase, float *xyz,
+                  float *nrm, uint32_t *tri);
 // slabs
 void wsk_migrate_mark(hipStream_t s, const WsDev &d, WsSoA cur, uint32_t *cid_cur, uint32_t *count);
 void wsk_migrate_fill(hipStream_t s, const WsDev &d, uint32_t world, uint32_t me, uint32_t cap, uint32_t *dyn,

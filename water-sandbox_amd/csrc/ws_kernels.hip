@@ -2884,3 +2884,284 @@ void wsk_field_sample(hipStream_t s, const WsDev &d, const uint32_t *start, cons
     }
 #undef FP_LAUNCH
 }
+
+// ---------------------------------------------------------------------------------
+// surface extraction (ws_extract_surface; never inside ws_step)
+//
+// The iso-surface rho = iso of a sampled grid (rho / grad: what k_field_bricks / k_field_points wrote for that grid),
+// by marching tetrahedra, exactly as include/wsfluid.h defines it.  Three streaming passes over the nodes, each one
+// lane per node in workgroups of WS_BLOCK consecutive linear nodes (workgroup b = nodes [b * WS_BLOCK, + WS_BLOCK),
+// dealt to the XCDs with xcd_tile so that each XCD's L2 walks one contiguous range, whose +y / +z neighbours are one
+// row and one plane ahead):
+//   k_iso_count      node code (bits 0-6: forward edge of type d = bit + 1 crossed; bit 7: inside) and the
+//                    workgroup's vertex and triangle totals;
+//   (two wsk_scan launches over the totals: every workgroup's first vertex and first triangle; k_iso_totals puts the
+//   two grand totals side by side for the host)
+//   k_iso_vertices   vertex base of every node with a crossed edge, its vertices' positions and normals;
+//   k_iso_triangles  the triangles of the node's cube, as vertex ids.
+// Both later passes recompute their lane's count from its code byte and scan it in the workgroup, so the ids are the
+// definition's order: nodes by linear index then edges by type; cubes by linear index, then tets, then the case table.
+// ---------------------------------------------------------------------------------
+#define ISO_INSIDE 0x80u
+
+// The six tets of a cube, corners as bit offsets (x = 1, y = 2, z = 4), all on the 0-7 diagonal: {0, m1, m2, 7}.
+// Tets 1, 2 and 5 are negatively oriented (det(c1 - c0, c2 - c0, c3 - c0) < 0): their triangles are reversed.
+#define ISO_TET_M1 0x442211u   // nibble t: m1 of tet t = 1 1 2 2 4 4
+#define ISO_TET_M2 0x656353u   // nibble t: m2 of tet t = 3 5 3 6 5 6
+#define ISO_TET_FLIP 0x26u     // bit t: tet t is negatively oriented
+
+// Case table of a positively oriented tet (local corners q0..q3, case bit k = q_k inside).  Local edges 0..5 =
+// (q0 q1) (q0 q2) (q0 q3) (q1 q2) (q1 q3) (q2 q3).  Entry: bits 0-11 the first triangle's three edges (4 bits each,
+// v0 lowest), bits 12-23 the second's, bits 24-25 the triangle count.  Every triangle's (v1 - v0) x (v2 - v0) points
+// from the inside corners to the outside ones (include/wsfluid.h lists the same table).
+#define ISO_T1(a, b, c) (1u << 24 | (a) | (b) << 4 | (c) << 8)
+#define ISO_T2(a, b, c, d, e, f) (2u << 24 | (a) | (b) << 4 | (c) << 8 | (d) << 12 | (e) << 16 | (f) << 20)
+__constant__ uint32_t c_iso_case[16] = {
+    0u,                        // 0: none inside
+    ISO_T1(0, 1, 2),           // 1: q0
+    ISO_T1(0, 4, 3),           // 2: q1
+    ISO_T2(1, 2, 4, 1, 4, 3),  // 3: q0 q1
+    ISO_T1(1, 3, 5),           // 4: q2
+    ISO_T2(2, 0, 3, 2, 3, 5),  // 5: q0 q2
+    ISO_T2(0, 4, 5, 0, 5, 1),  // 6: q1 q2
+    ISO_T1(2, 4, 5),           // 7: all but q3
+    ISO_T1(2, 5, 4),           // 8: q3
+    ISO_T2(0, 1, 5, 0, 5, 4),  // 9: q0 q3
+    ISO_T2(3, 0, 2, 3, 2, 5),  // 10: q1 q3
+    ISO_T1(1, 5, 3),           // 11: all but q2
+    ISO_T2(1, 3, 4, 1, 4, 2),  // 12: q2 q3
+    ISO_T1(0, 3, 4),           // 13: all but q1
+    ISO_T1(0, 2, 1),           // 14: all but q0
+    0u,                        // 15: all inside
+};
+#undef ISO_T1
+#undef ISO_T2
+#define ISO_CASE_TRIS 0x16696994u  // 2 bits per case: the table's triangle counts
+
+// corner c of the cube inside (bit c), from the code byte of its corner 0
+__device__ __forceinline__ uint32_t iso_corners(uint32_t code)
+{
+    const uint32_t x = (code & 0x7Fu) << 1;
+    return (code & ISO_INSIDE) ? (~x & 0xFFu) : x;
+}
+
+__device__ __forceinline__ uint32_t iso_tet_case(uint32_t cm, int t)
+{
+    const uint32_t m1 = (ISO_TET_M1 >> (4 * t)) & 15u, m2 = (ISO_TET_M2 >> (4 * t)) & 15u;
+    return (cm & 1u) | ((cm >> m1) & 1u) << 1 | ((cm >> m2) & 1u) << 2 | ((cm >> 7) & 1u) << 3;
+}
+
+__device__ __forceinline__ uint32_t iso_cube_triangles(uint32_t code)
+{
+    const uint32_t cm = iso_corners(code);
+    uint32_t tri = 0;
+#pragma unroll
+    for (int t = 0; t < 6; t++) tri += (ISO_CASE_TRIS >> (2 * iso_tet_case(cm, t))) & 3u;
+    return tri;
+}
+
+// Exclusive scan of v over the workgroup (WS_BLOCK lanes); *total = the workgroup's sum.
+__device__ __forceinline__ uint32_t iso_block_scan(uint32_t v, uint32_t *total)
+{
+    __shared__ uint32_t s_wave[WS_BLOCK / 64];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t incl = wave_incl_scan(v);
+    if (lane == 63u) s_wave[wave] = incl;
+    __syncthreads();
+    uint32_t base = 0, sum = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < WS_BLOCK / 64; w++) {
+        const uint32_t x = s_wave[w];
+        base += w < wave ? x : 0u;
+        sum += x;
+    }
+    *total = sum;
+    return base + incl - v;
+}
+
+__global__ void __launch_bounds__(WS_BLOCK) k_iso_count(const float *__restrict__ rho, WsFieldGrid g, float iso,
+                                                        uint8_t *__restrict__ code, uint32_t *__restrict__ vcnt,
+                                                        uint32_t *__restrict__ tcnt, uint32_t nodes)
+{
+    const uint32_t b = xcd_tile(blockIdx.x, gridDim.x);
+    const uint32_t n = b * WS_BLOCK + threadIdx.x;
+    uint32_t c = 0, tri = 0;
+    if (n < nodes) {
+        const uint32_t i = n % g.nx, r = n / g.nx, j = r % g.ny, k = r / g.ny;
+        const uint32_t row = g.nx, plane = g.nx * g.ny;
+        const bool in0 = rho[n] >= iso;
+#pragma unroll
+        for (uint32_t d = 1; d < 8; d++) {
+            const uint32_t dx = d & 1u, dy = (d >> 1) & 1u, dz = d >> 2;
+            if (i + dx < g.nx && j + dy < g.ny && k + dz < g.nz) {
+                const bool in = rho[n + dx + dy * row + dz * plane] >= iso;
+                c |= (in != in0 ? 1u : 0u) << (d - 1u);
+            }
+        }
+        c |= in0 ? ISO_INSIDE : 0u;
+        code[n] = (uint8_t)c;
+        if (i + 1u < g.nx && j + 1u < g.ny && k + 1u < g.nz) tri = iso_cube_triangles(c);
+    }
+    uint32_t vtot, ttot;
+    iso_block_scan(__builtin_popcount(c & 0x7Fu), &vtot);
+    __syncthreads();  // (the scan's LDS is reused)
+    iso_block_scan(tri, &ttot);
+    if (threadIdx.x == 0) {
+        vcnt[b] = vtot;
+        tcnt[b] = ttot;
+        if (b == 0) {  // the scans run over gridDim.x + 1 totals: the last one, 0, becomes the grand total
+            vcnt[gridDim.x] = 0u;
+            tcnt[gridDim.x] = 0u;
+        }
+    }
+}
+
+// The vertex on the forward edge of type d at node (i, j, k): t = (iso - ra) / (rb - ra) (correctly rounded),
+// p = pa + t * (pb - pa) per axis; the normal -g / sqrtf(g . g) of g = ga + t * (gb - ga), (0, 0, 0) where g . g == 0.
+template <bool NORMALS>
+__global__ void __launch_bounds__(WS_BLOCK) k_iso_vertices(const float *__restrict__ rho, const float *__restrict__ grad,
+                                                           WsFieldGrid g, float iso, const uint8_t *__restrict__ code,
+                                                           const uint32_t *__restrict__ vstart, uint32_t *__restrict__ vbase,
+                                                           float *__restrict__ xyz, float *__restrict__ nrm, uint32_t nodes)
+{
+    const uint32_t b = xcd_tile(blockIdx.x, gridDim.x);
+    const uint32_t n = b * WS_BLOCK + threadIdx.x;
+    const uint32_t c = n < nodes ? (uint32_t)code[n] & 0x7Fu : 0u;
+    uint32_t total;
+    const uint32_t v0 = vstart[b] + iso_block_scan(__builtin_popcount(c), &total);
+    if (c == 0u) return;
+    vbase[n] = v0;
+    const uint32_t i = n % g.nx, r = n / g.nx, j = r % g.ny, k = r / g.ny;
+    const float4 pa = field_node(g, i, j, k);
+    const float ra = rho[n];
+    uint32_t v = v0;
+    for (uint32_t d = 1; d < 8; d++) {
+        if (!((c >> (d - 1u)) & 1u)) continue;
+        const uint32_t dx = d & 1u, dy = (d >> 1) & 1u, dz = d >> 2;
+        const uint32_t m = n + dx + dy * g.nx + dz * g.nx * g.ny;
+        const float4 pb = field_node(g, i + dx, j + dy, k + dz);
+        const float rb = rho[m];
+        const float t = (iso - ra) / (rb - ra);
+        const size_t at = 3 * (size_t)v;
+        xyz[at] = pa.x + t * (pb.x - pa.x);
+        xyz[at + 1] = pa.y + t * (pb.y - pa.y);
+        xyz[at + 2] = pa.z + t * (pb.z - pa.z);
+        if constexpr (NORMALS) {
+            const float gx = grad[3 * (size_t)n] + t * (grad[3 * (size_t)m] - grad[3 * (size_t)n]);
+            const float gy = grad[3 * (size_t)n + 1] + t * (grad[3 * (size_t)m + 1] - grad[3 * (size_t)n + 1]);
+            const float gz = grad[3 * (size_t)n + 2] + t * (grad[3 * (size_t)m + 2] - grad[3 * (size_t)n + 2]);
+            const float gg = gx * gx + gy * gy + gz * gz;
+            float nx = 0.f, ny = 0.f, nz = 0.f;
+            if (gg != 0.f) {
+                const float len = sqrtf(gg);
+                nx = -gx / len;
+                ny = -gy / len;
+                nz = -gz / len;
+            }
+            nrm[at] = nx;
+            nrm[at + 1] = ny;
+            nrm[at + 2] = nz;
+        }
+        v++;
+    }
+}
+
+// vertex id of the forward edge of type d at the node whose code and vertex base are given
+__device__ __forceinline__ uint32_t iso_vertex_id(uint32_t code, uint32_t base, uint32_t d)
+{
+    return base + __builtin_popcount(code & ((1u << (d - 1u)) - 1u));
+}
+
+__global__ void __launch_bounds__(WS_BLOCK) k_iso_triangles(WsFieldGrid g, const uint8_t *__restrict__ code,
+                                                            const uint32_t *__restrict__ tstart,
+                                                            const uint32_t *__restrict__ vbase, uint32_t *__restrict__ tri,
+                                                            uint32_t nodes)
+{
+    const uint32_t b = xcd_tile(blockIdx.x, gridDim.x);
+    const uint32_t n = b * WS_BLOCK + threadIdx.x;
+    uint32_t c = 0, ntri = 0, i = 0, j = 0, k = 0;
+    if (n < nodes) {
+        const uint32_t r = n / g.nx;
+        i = n % g.nx;
+        j = r % g.ny;
+        k = r / g.ny;
+        if (i + 1u < g.nx && j + 1u < g.ny && k + 1u < g.nz) {
+            c = code[n];
+            ntri = iso_cube_triangles(c);
+        }
+    }
+    uint32_t total;
+    uint32_t out = tstart[b] + iso_block_scan(ntri, &total);
+    if (ntri == 0u) return;
+    // corners 0..6 (n + u): their codes and vertex bases (a corner whose code has no crossed edge carries no vertex)
+    const uint32_t row = g.nx, plane = g.nx * g.ny;
+    uint32_t cc[7], vb[7];
+#pragma unroll
+    for (uint32_t u = 0; u < 7; u++) {
+        const uint32_t m = n + (u & 1u) + ((u >> 1) & 1u) * row + (u >> 2) * plane;
+        cc[u] = u == 0 ? c : (uint32_t)code[m];
+        vb[u] = (cc[u] & 0x7Fu) ? vbase[m] : 0u;
+    }
+    const uint32_t cm = iso_corners(c);
+#pragma unroll
+    for (int t = 0; t < 6; t++) {
+        const uint32_t e = c_iso_case[iso_tet_case(cm, t)];
+        const uint32_t cnt = e >> 24;
+        if (cnt == 0u) continue;
+        const uint32_t m1 = (ISO_TET_M1 >> (4 * t)) & 15u, m2 = (ISO_TET_M2 >> (4 * t)) & 15u;
+        // the tet's six edges (q0 q1) (q0 q2) (q0 q3) (q1 q2) (q1 q3) (q2 q3) as vertex ids: edge (a, b), a a subset of
+        // b, is the forward edge of type a ^ b at corner a
+        uint32_t vid[6];
+        vid[0] = iso_vertex_id(cc[0], vb[0], m1);
+        vid[1] = iso_vertex_id(cc[0], vb[0], m2);
+        vid[2] = iso_vertex_id(cc[0], vb[0], 7u);
+        vid[3] = iso_vertex_id(cc[m1], vb[m1], m1 ^ m2);
+        vid[4] = iso_vertex_id(cc[m1], vb[m1], 7u ^ m1);
+        vid[5] = iso_vertex_id(cc[m2], vb[m2], 7u ^ m2);
+        const bool flip = (ISO_TET_FLIP >> t) & 1u;
+        for (uint32_t q = 0; q < cnt; q++) {
+            const uint32_t f = e >> (12 * q);
+            const uint32_t a = vid[f & 15u], b1 = vid[(f >> 4) & 15u], b2 = vid[(f >> 8) & 15u];
+            const size_t at = 3 * (size_t)out++;
+            tri[at] = a;
+            tri[at + 1] = flip ? b2 : b1;
+            tri[at + 2] = flip ? b1 : b2;
+        }
+    }
+}
+
+void wsk_iso_count(hipStream_t s, const float *rho, const float *grid6, const uint32_t *dims, float iso, uint8_t *code,
+                   uint32_t *vcnt, uint32_t *tcnt)
+{
+    const WsFieldGrid g = {grid6[0], grid6[1], grid6[2], grid6[3], grid6[4], grid6[5], dims[0], dims[1], dims[2]};
+    const uint32_t nodes = dims[0] * dims[1] * dims[2];
+    hipLaunchKernelGGL(k_iso_count, dim3(cdiv(nodes, WS_BLOCK)), dim3(WS_BLOCK), 0, s, rho, g, iso, code, vcnt, tcnt, nodes);
+}
+
+uint32_t wsk_iso_blocks(const uint32_t *dims) { return cdiv(dims[0] * dims[1] * dims[2], WS_BLOCK); }
+
+// the two grand totals (the last entries of the two scans) side by side, for one small copy to the host
+__global__ void k_iso_totals(const uint32_t *__restrict__ v_total, const uint32_t *__restrict__ t_total, uint32_t *__restrict__ out)
+{
+    if (threadIdx.x == 0) {
+        out[0] = *v_total;
+        out[1] = *t_total;
+    }
+}
+
+void wsk_iso_totals(hipStream_t s, const uint32_t *v_total, const uint32_t *t_total, uint32_t *out)
+{
+    hipLaunchKernelGGL(k_iso_totals, dim3(1), dim3(64), 0, s, v_total, t_total, out);
+}
+
+void wsk_iso_mesh(hipStream_t s, const float *rho, const float *grad, const float *grid6, const uint32_t *dims, float iso,
+                  const uint8_t *code, const uint32_t *vstart, const uint32_t *tstart, uint32_t *vbase, float *xyz,
+                  float *nrm, uint32_t *tri)
+{
+    const WsFieldGrid g = {grid6[0], grid6[1], grid6[2], grid6[3], grid6[4], grid6[5], dims[0], dims[1], dims[2]};
+    const uint32_t nodes = dims[0] * dims[1] * dims[2];
+    const dim3 grid(cdiv(nodes, WS_BLOCK));
+    if (nrm) hipLaunchKernelGGL(k_iso_vertices<true>, grid, dim3(WS_BLOCK), 0, s, rho, grad, g, iso, code, vstart, vbase, xyz, nrm, nodes);
+    else hipLaunchKernelGGL(k_iso_vertices<false>, grid, dim3(WS_BLOCK), 0, s, rho, grad, g, iso, code, vstart, vbase, xyz, nrm, nodes);
+    hipLaunchKernelGGL(k_iso_triangles, grid, dim3(WS_BLOCK), 0, s, g, code, tstart, vbase, tri, nodes);
+}

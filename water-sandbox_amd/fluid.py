@@ -49,7 +49,7 @@ ABI_SYMBOLS = [
     "ws_local_hub_create", "ws_local_hub_destroy", "ws_local_transport_create", "ws_local_transport_destroy", "ws_read_sort_view", "ws_last_error", "ws_num_particles",
     "ws_steps_done", "ws_kernel_name", "ws_profile_read", "ws_profile_reset", "ws_profile_select",
     "ws_grid_dims", "ws_read_stats", "ws_slab_assign", "ws_slab_create", "ws_slab_read_particles", "ws_slab_rebalance", "ws_slab_balanced_cuts",
-    "ws_sample_density_grid", "ws_sample_density_points",
+    "ws_sample_density_grid", "ws_sample_density_points", "ws_extract_surface",
 ]
 
 
@@ -161,6 +161,7 @@ def bind_library(path):
     L.ws_read_stats.argtypes = [vp, vp]
     L.ws_sample_density_grid.argtypes = [vp, vp, vp, vp, vp, vp]
     L.ws_sample_density_points.argtypes = [vp, vp, u32, vp, vp]
+    L.ws_extract_surface.argtypes = [vp, vp, vp, vp, C.c_float, u32, u32, vp, vp, vp, vp, vp]
     return L
 
 
@@ -192,6 +193,44 @@ def sample_density_points(L, h, check, xyz, gradient=False, want=True):
     grad = np.empty((m, 3), np.float32) if gradient else None
     check(L.ws_sample_density_points(h, q.ctypes.data, m, rho.ctypes.data, grad.ctypes.data if gradient else None))
     return rho, grad
+
+
+def extract_surface(L, h, check, origin, spacing, dims, iso, normals=True, want=True, collective=False, cap=None):
+    """ws_extract_surface: (vertices (V, 3) f32, normals (V, 3) f32 or None, triangles (T, 3) uint32).
+    cap = (vertices, triangles): a first guess of the capacities, and one retry at the exact counts when it is too small.
+    cap=None, and always on slab handles (collective): a counts-only call first (it samples no gradient), then one at the
+    exact counts -- every rank makes the same two calls; want=False contributes to both and returns (None, None, None)."""
+    o = np.ascontiguousarray(origin, np.float32).reshape(3)
+    sp = np.ascontiguousarray(spacing, np.float32).reshape(3)
+    d = np.ascontiguousarray(dims, np.uint32).reshape(3)
+    nv, nt = C.c_uint32(0), C.c_uint32(0)
+
+    def call(cap_v, cap_t, xyz=None, nrm=None, tri=None, counts=True):
+        check(L.ws_extract_surface(h, o.ctypes.data, sp.ctypes.data, d.ctypes.data, C.c_float(iso), cap_v, cap_t,
+                                   None if xyz is None else xyz.ctypes.data, None if nrm is None else nrm.ctypes.data,
+                                   None if tri is None else tri.ctypes.data, C.byref(nv) if counts else None,
+                                   C.byref(nt) if counts else None))
+
+    if not want:  # a slab rank that only contributes, to both calls
+        call(0, 0, counts=False)
+        call(0, 0, counts=False)
+        return None, None, None
+    if collective or cap is None:
+        call(0, 0)
+        cap_v, cap_t = nv.value, nt.value
+    else:
+        cap_v, cap_t = (int(c) for c in cap)
+    for _ in range(2):
+        xyz = np.empty((cap_v, 3), np.float32)
+        nrm = np.empty((cap_v, 3), np.float32) if normals else None
+        tri = np.empty((cap_t, 3), np.uint32)
+        call(cap_v, cap_t, xyz, nrm, tri)
+        if nv.value <= cap_v and nt.value <= cap_t:
+            return xyz[:nv.value], (nrm[:nv.value] if normals else None), tri[:nt.value]
+        if collective:
+            break
+        cap_v, cap_t = nv.value, nt.value
+    raise RuntimeError("ws_extract_surface: the mesh changed between two calls on the same state")
 
 
 # ---------------------------------------------------------------------------------------
@@ -252,6 +291,7 @@ class FluidWorker:
                  library=None, graph=False):
         self._L = library if library is not None else load_library()
         self._h = C.c_void_p()
+        self._surface_cap = None  # extract_surface's first guess of the capacities, from the previous mesh
         positions = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
         self.n = positions.shape[0]
         self.params = params if params is not None else default_params()
@@ -383,6 +423,15 @@ class FluidWorker:
         """The same field at m points (xyz: (m, 3)): shape (m,), with gradient=True also (m, 3)."""
         rho, grad = sample_density_points(self._L, self._h, self._check, xyz, gradient)
         return (rho, grad) if gradient else rho
+
+    def extract_surface(self, origin, spacing, dims, iso, normals=True):
+        """The surface rho = iso of the density field on the grid origin + (i, j, k) * spacing, dims = (nx, ny, nz), as a
+        mesh: (vertices (V, 3) float32, normals (V, 3) float32 or None, triangles (T, 3) uint32), triangles counter-
+        clockwise seen from outside the fluid (include/wsfluid.h ws_extract_surface has the definition)."""
+        mesh = extract_surface(self._L, self._h, self._check, origin, spacing, dims, iso, normals, cap=self._surface_cap)
+        nv, nt = len(mesh[0]), len(mesh[2])
+        self._surface_cap = (nv + nv // 4 + 4096, nt + nt // 4 + 8192)  # (a mesh moves little from one frame to the next)
+        return mesh
 
     def steps_done(self):
         return int(self._L.ws_steps_done(self._h))

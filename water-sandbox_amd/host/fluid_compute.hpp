@@ -210,6 +210,23 @@ class FluidWorker {
                                      dims, out.data(), gradient ? gradient->data() : nullptr));
         return out;
     }
+    // The surface rho = iso of that field as a triangle mesh (ws_extract_surface): 3 floats per vertex (and normal, when
+    // asked for), 3 vertex indices per triangle.  Counts first, then the mesh at exactly that size.
+    void extract_surface(const Vec3 &origin, const Vec3 &spacing, const uint32_t dims[3], float iso, std::vector<float> &xyz,
+                         std::vector<uint32_t> &tri, std::vector<float> *normals = nullptr)
+    {
+        const float *o = reinterpret_cast<const float *>(&origin), *s = reinterpret_cast<const float *>(&spacing);
+        uint32_t nv = 0, nt = 0;
+        check(ws_extract_surface(h_, o, s, dims, iso, 0, 0, nullptr, nullptr, nullptr, &nv, &nt));
+        xyz.resize((size_t)nv * 3 + 1);
+        tri.resize((size_t)nt * 3 + 1);
+        if (normals) normals->resize((size_t)nv * 3 + 1);
+        check(ws_extract_surface(h_, o, s, dims, iso, nv, nt, xyz.data(), normals ? normals->data() : nullptr, tri.data(),
+                                 &nv, &nt));
+        xyz.resize((size_t)nv * 3);
+        tri.resize((size_t)nt * 3);
+        if (normals) normals->resize((size_t)nv * 3);
+    }
 
     std::vector<float> read_speeds()
     {

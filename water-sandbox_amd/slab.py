@@ -378,6 +378,12 @@ class SlabWorker:
         rho, grad = fluid.sample_density_points(self._L, self._h, self._check, xyz, gradient, want)
         return (rho, grad) if gradient else rho
 
+    def extract_surface(self, origin, spacing, dims, iso, normals=True, want=True):
+        """FluidWorker.extract_surface over the GLOBAL particle set (COLLECTIVE: two calls on every rank, counts first);
+        want=False: only contribute (None, None, None)."""
+        return fluid.extract_surface(self._L, self._h, self._check, origin, spacing, dims, iso, normals, want,
+                                     collective=True)
+
     def read_positions_begin(self, buf):
         assert buf.dtype == np.float32 and buf.shape == (self.n_global, 3) and buf.flags.c_contiguous
         self._check(self._L.ws_read_positions_begin(self._h, buf.ctypes.data))
