@@ -462,6 +462,77 @@ ws_status ws_extract_surface(ws_handle *h, const float origin[3], const float sp
                              float *out_xyz, float *out_normal, uint32_t *out_tri,
                              uint32_t *n_vertices, uint32_t *n_triangles);
 
+/* ---- smooth surfaces: anisotropic particle kernels (Yu & Turk, ACM TOG 2013) ----------------------
+ * The field above gives every particle a ball of radius h: flat water shows bumps at the particle spacing, thin sheets
+ * break into blobs and a lone droplet is a ball about h wide.  Here each particle's kernel is an ellipsoid shaped by
+ * the weighted covariance of its neighbours (flat along the normal at a free surface, about round in the bulk, small
+ * and round with few neighbours), and its centre moves toward its neighbourhood mean.
+ *
+ * Per-particle stage.  IEEE arithmetic whatever the handle's flags: every operation rounded to float, divisions and
+ * sqrt correctly rounded, no contraction; sums run left to right in the order given, starting from 0.
+ *   Neighbours: N_i = the particles j (i included) the density sampler's sweep visits around o = x_i and accepts: the
+ *     27 cells of the handle's grid around x_i's (clamped) cell, cells in increasing linear id, ids ascending inside a
+ *     cell; e = x_j - x_i, d2 = e.x*e.x + e.y*e.y + e.z*e.z, j counts unless d2 > d2_accept.  n_i = |N_i|.
+ *   Weights and moments, from that one sweep: d = sqrt(d2), q = d / h, w = 1 - (q*q)*q; W = sum w, S_a = sum w*e_a,
+ *     Q_ab = sum (w*e_a)*e_b for ab = xx, yy, zz, xy, xz, yz.
+ *   Mean and covariance: m_a = S_a / W, C_ab = Q_ab / W - m_a*m_b (W >= 1: the self term; the moments are taken about
+ *     x_i, so |e| <= h and the one-pass form loses only a few bits).  Centre: c_a = x_a + lambda*m_a.
+ *   Lone branch, taken if n_i < N_eps or if the anisotropic branch finds sigma_max not > 0: inv = 1 / k_n, M = inv*I
+ *     (off-diagonals +0), f = (inv*inv)*inv.
+ *   Anisotropic branch: cyclic Jacobi on A = C, R = I, exactly 5 sweeps of the pairs (p, q) = (0,1), (0,2), (1,2), r
+ *     the third index; no convergence exit.  A rotation is skipped iff a_pq == 0; otherwise, in this order:
+ *       theta = (a_qq - a_pp) / (2*a_pq);
+ *       t = 1 / (2*theta) if |theta| > 2^32, else t = g / (|theta| + sqrt(theta*theta + 1)), g = +1 if theta >= 0 else -1;
+ *       c = 1 / sqrt(t*t + 1), s = t*c;
+ *       a_pp = a_pp - t*a_pq; a_qq = a_qq + t*a_pq; a_pq = 0;
+ *       a_rp, a_rq = c*a_rp - s*a_rq, s*a_rp + c*a_rq (both from the old values);
+ *       for k = 0, 1, 2: R_kp, R_kq = c*R_kp - s*R_kq, s*R_kp + c*R_kq.
+ *     sigma_k = the final a_kk and r_k = column k of R (unsorted); sigma_max = fmaxf(fmaxf(sigma_0, sigma_1), sigma_2);
+ *     floor = sigma_max / k_r; s_k = fmaxf(sigma_k, floor) / sigma_max (the longest axis is exactly 1; a slightly
+ *     negative sigma from rounding is floored); M_ab = sum over k = 0, 1, 2 of ((1/s_k)*r_k[a])*r_k[b], from 0;
+ *     f = 1 / ((s_0*s_1)*s_2).
+ *   Every 1/s_k >= 1, so the ellipsoid |M e| <= h lies inside the ball |e| <= h, and the 27-cell stencil stays valid.
+ *   This departs from Yu & Turk's k_s: the longest axis is normalised to h, where Y&T scale the whole kernel (which
+ *   could grow wider than h).
+ * Field at a node or point o, in the handle's arithmetic exactly as ws_sample_density_grid: the particles are binned by
+ *   their CENTRES c_j on the handle's grid and visited in the canonical order.  A particle counts iff e = c_j - o has
+ *   !(d2 > d2_accept) and u = M_j e, u_a = (M_a0*e.x + M_a1*e.y) + M_a2*e.z, has !(dM2 > d2_accept), dM2 = u.x*u.x +
+ *   u.y*u.y + u.z*u.z.  Density term sk_density(dM) * f_j, dM = sqrt(dM2) (the handle's sqrt); gradient term: the
+ *   density sampler's expression (both arithmetic forms) with e replaced by v = M_j u (same row order as u) and d by
+ *   dM, then times f_j; f_j is the last operation of both (0 at dM == 0).
+ * Mesh: ws_extract_surface's definition, word for word, on this grid field.
+ * The isotropic limit is a contract: with smoothing 0, lone_scale 1 and min_neighbours 0xFFFFFFFF every particle takes
+ *   the lone branch with M = I, f = 1 and c = x, and the field, gradient, points output and mesh are bit-identical to
+ *   ws_sample_density_grid / _points and ws_extract_surface.
+ * All four calls wait for enqueued steps, write nothing ws_step reads, recompute everything from the current positions
+ * and keep their scratch in the sampler's (grow-only, freed by ws_destroy).  Slab handles: COLLECTIVE on the gathered
+ * global set, the same bits as a single handle; a rank validates its query and its params only after the gather.
+ * Errors: as the corresponding density / surface call, plus WS_ERR_INVALID_ARG for NULL params, smoothing outside
+ * [0, 1], max_ratio < 1, lone_scale outside (0, 1] or a non-finite value. */
+typedef struct ws_aniso_params {
+    float smoothing;         /* lambda in [0, 1]: centre = x + lambda * (weighted mean offset)       default 0.9 */
+    float max_ratio;         /* k_r >= 1: shortest axis >= longest / k_r                             default 4   */
+    float lone_scale;        /* k_n in (0, 1]: radius of a lone particle's ball, in units of h       default 0.5 */
+    uint32_t min_neighbours; /* N_eps: fewer neighbours (self included) -> lone ball                 default 12  */
+} ws_aniso_params;
+/* The defaults above (host-only: no handle, no device). */
+ws_status ws_default_aniso_params(ws_aniso_params *out);
+/* The stage, per particle in original-id order: out_centre n*3 (c), out_matrix n*6 (M: xx yy zz xy xz yz), out_scale n
+ * (f = det M), out_neighbours n (n_i).  n = ws_num_particles, or the global count on slab handles.  Any output may be
+ * NULL; a single handle with all four NULL only checks a. */
+ws_status ws_read_anisotropy(ws_handle *h, const ws_aniso_params *a, float *out_centre, float *out_matrix, float *out_scale,
+                             uint32_t *out_neighbours);
+/* ws_sample_density_grid / _points with the anisotropic field. */
+ws_status ws_sample_aniso_grid(ws_handle *h, const ws_aniso_params *a, const float origin[3], const float spacing[3],
+                               const uint32_t dims[3], float *out_field, float *out_gradient);
+ws_status ws_sample_aniso_points(ws_handle *h, const ws_aniso_params *a, const float *xyz, uint32_t m, float *out_field,
+                                 float *out_gradient);
+/* ws_extract_surface on the anisotropic field (same arguments, same capacity protocol). */
+ws_status ws_extract_aniso_surface(ws_handle *h, const ws_aniso_params *a, const float origin[3], const float spacing[3],
+                                   const uint32_t dims[3], float iso, uint32_t max_vertices, uint32_t max_triangles,
+                                   float *out_xyz, float *out_normal, uint32_t *out_tri, uint32_t *n_vertices,
+                                   uint32_t *n_triangles);
+
 /* ---- introspection ------------------------------------------------------------- */
 const char *ws_last_error(ws_handle *h);
 uint32_t ws_num_particles(ws_handle *h);

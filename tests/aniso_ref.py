@@ -1,0 +1,345 @@
+"""numpy restatement of the anisotropic kernels (include/wsfluid.h, ws_aniso_params): the per-particle stage in float32
+bit for bit, the field in float32 (IEEE arithmetic, bit for bit with the library's WS_FLAG_IEEE_DIVISION form) and in
+float64 with a per-node error bound, and the mesh through surface_ref.extract.  Vectorised over particles (or query
+points), with the candidate columns in the canonical order: the 27 cells of the handle's grid around the query's
+cell as 9 (x, y) columns, x slower, each a z-run of cells, particles by id inside a cell.  Padded columns are guarded
+with np.where, never added as 0 (that would turn a -0 into +0)."""
+import numpy as np
+
+import surface_ref as S
+from f64_step import U, accept
+
+F32 = np.float32
+GRID_PAD = 2  # empty cell layers around the container (the library's grid)
+CHUNK = 4096  # queries per numpy chunk
+
+
+def defaults():
+    """ws_default_aniso_params as a dict."""
+    return dict(smoothing=0.9, max_ratio=4.0, lone_scale=0.5, min_neighbours=12)
+
+
+def isotropic_limit():
+    return dict(smoothing=0.0, max_ratio=4.0, lone_scale=1.0, min_neighbours=0xFFFFFFFF)
+
+
+class Grid:
+    """The handle's cell grid (reference-sized cells over the container padded by GRID_PAD; no merged cells)."""
+
+    def __init__(self, params):
+        self.h = F32(params.smoothing_radius)
+        mn = np.asarray(params.ext_min[:3], F32)
+        mx = np.asarray(params.ext_max[:3], F32)
+        self.org = np.floor(mn / self.h).astype(np.int64) - GRID_PAD
+        self.dim = np.floor(mx / self.h).astype(np.int64) + GRID_PAD - self.org + 1
+        assert np.prod(self.dim) <= max(1 << 24, 16 * 4096), "merged cells are not restated"
+        self.d2_accept = accept(self.h)
+
+    def cells(self, x):
+        """(n, 3) int64 cell coordinates: floorf(x / h) - org, clamped to the grid."""
+        c = np.floor(np.asarray(x, F32) / self.h).astype(np.int64) - self.org
+        return np.clip(c, 0, self.dim - 1)
+
+    def linear(self, c):
+        return (c[:, 0] * self.dim[1] + c[:, 1]) * self.dim[2] + c[:, 2]
+
+
+class Binned:
+    """Points binned on a Grid in canonical order: order[j] = id of sorted slot j, start[cell] (ncells + 1 entries)."""
+
+    def __init__(self, grid, x):
+        self.grid = grid
+        key = grid.linear(grid.cells(x))
+        self.order = np.argsort(key, kind="stable")  # (stable: ids ascending inside a cell)
+        self.start = np.searchsorted(key[self.order], np.arange(int(np.prod(grid.dim)) + 1)).astype(np.int64)
+
+    def columns(self, q):
+        """Candidate columns of the query points q (m, 3): (m, K) int64 sorted slots in canonical order, -1 padded."""
+        g = self.grid
+        c = g.cells(q)
+        z0 = np.maximum(c[:, 2] - 1, 0)
+        z1 = np.minimum(c[:, 2] + 1, g.dim[2] - 1)
+        b, ln = [], []
+        for dx in (-1, 0, 1):
+            for dy in (-1, 0, 1):
+                x, y = c[:, 0] + dx, c[:, 1] + dy
+                ok = (x >= 0) & (x < g.dim[0]) & (y >= 0) & (y < g.dim[1])
+                col = (np.clip(x, 0, g.dim[0] - 1) * g.dim[1] + np.clip(y, 0, g.dim[1] - 1)) * g.dim[2]
+                bb = self.start[col + z0]
+                ee = self.start[col + z1 + 1]
+                b.append(np.where(ok, bb, 0))
+                ln.append(np.where(ok, ee - bb, 0))
+        b, ln = np.stack(b, 1), np.stack(ln, 1)
+        pre = np.concatenate([np.zeros((len(q), 1), np.int64), np.cumsum(ln, 1)], 1)
+        k = int(pre[:, -1].max()) if len(q) else 0
+        ar = np.arange(k)[None, :]
+        out = np.full((len(q), k), -1, np.int64)
+        for r in range(9):
+            m = (ar >= pre[:, r, None]) & (ar < pre[:, r + 1, None])
+            out = np.where(m, b[:, r, None] + ar - pre[:, r, None], out)
+        return out
+
+
+# ---- the per-particle stage (float32, bit for bit) ---------------------------------------------------------------------
+def jacobi(a, iterations=5):
+    """Cyclic Jacobi of the header on symmetric 3x3 matrices a (m, 6) = xx yy zz xy xz yz, float32:
+    (sigma (m, 3), R (m, 3, 3) with r_k = R[:, :, k])."""
+    a = [np.array(a[:, k], F32) for k in range(6)]  # a00 a11 a22 a01 a02 a12
+    m = len(a[0])
+    R = np.zeros((m, 3, 3), F32)
+    for k in range(3):
+        R[:, k, k] = F32(1)
+    # (p, q, index of a_pp, a_qq, a_pq, a_rp, a_rq)
+    pairs = ((0, 1, 0, 1, 3, 4, 5), (0, 2, 0, 2, 4, 3, 5), (1, 2, 1, 2, 5, 3, 4))
+    one, two = F32(1), F32(2)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        for _ in range(iterations):
+            for p, q, ipp, iqq, ipq, irp, irq in pairs:
+                app, aqq, apq, arp, arq = a[ipp], a[iqq], a[ipq], a[irp], a[irq]
+                go = apq != 0
+                theta = ((aqq - app) / (two * apq)).astype(F32)
+                big = np.abs(theta) > F32(2.0 ** 32)
+                g = np.where(theta >= 0, one, -one).astype(F32)
+                t_small = (g / (np.abs(theta) + np.sqrt((theta * theta + one).astype(F32)))).astype(F32)
+                t_big = (one / (two * theta)).astype(F32)
+                t = np.where(big, t_big, t_small).astype(F32)
+                c = (one / np.sqrt((t * t + one).astype(F32))).astype(F32)
+                s = (t * c).astype(F32)
+                a[ipp] = np.where(go, app - t * apq, app).astype(F32)
+                a[iqq] = np.where(go, aqq + t * apq, aqq).astype(F32)
+                a[ipq] = np.where(go, F32(0), apq).astype(F32)
+                a[irp] = np.where(go, c * arp - s * arq, arp).astype(F32)
+                a[irq] = np.where(go, s * arp + c * arq, arq).astype(F32)
+                vp, vq = R[:, :, p].copy(), R[:, :, q].copy()
+                R[:, :, p] = np.where(go[:, None], c[:, None] * vp - s[:, None] * vq, vp)
+                R[:, :, q] = np.where(go[:, None], s[:, None] * vp + c[:, None] * vq, vq)
+    return np.stack(a[:3], 1), R
+
+
+def stage(params, x, aniso):
+    """The stage of the header for the float32 positions x (n, 3) by id: (centre (n, 3), M (n, 6), f (n,),
+    neighbours (n,) uint32), each float32 bit for bit."""
+    x = np.ascontiguousarray(x, F32).reshape(-1, 3)
+    lam, kr, kn = F32(aniso["smoothing"]), F32(aniso["max_ratio"]), F32(aniso["lone_scale"])
+    neps = int(aniso["min_neighbours"])
+    grid = Grid(params)
+    bins = Binned(grid, x)
+    n = len(x)
+    cen = np.empty((n, 3), F32)
+    mat = np.empty((n, 6), F32)
+    det = np.empty(n, F32)
+    cnt = np.empty(n, np.uint32)
+    for s0 in range(0, n, CHUNK):
+        ids = np.arange(s0, min(n, s0 + CHUNK))
+        xi = x[ids]
+        cols = bins.columns(xi)
+        valid = cols >= 0
+        xj = x[bins.order[np.where(valid, cols, 0)]]
+        e = (xj - xi[:, None, :]).astype(F32)
+        d2 = ((e[..., 0] * e[..., 0] + e[..., 1] * e[..., 1]) + e[..., 2] * e[..., 2]).astype(F32)
+        acc = valid & ~(d2 > grid.d2_accept)
+        r = (np.sqrt(d2) / grid.h).astype(F32)
+        w = (F32(1) - (r * r) * r).astype(F32)
+        we = (w[..., None] * e).astype(F32)
+        terms = [w, we[..., 0], we[..., 1], we[..., 2], we[..., 0] * e[..., 0], we[..., 1] * e[..., 1],
+                 we[..., 2] * e[..., 2], we[..., 0] * e[..., 1], we[..., 0] * e[..., 2], we[..., 1] * e[..., 2]]
+        sums = [np.zeros(len(ids), F32) for _ in terms]
+        for k in range(cols.shape[1]):
+            a = acc[:, k]
+            for t, sm in zip(terms, sums):
+                sm[...] = np.where(a, sm + t[:, k].astype(F32), sm)
+        W, sx, sy, sz, qxx, qyy, qzz, qxy, qxz, qyz = sums
+        nb = acc.sum(1).astype(np.uint32)
+        mx, my, mz = sx / W, sy / W, sz / W
+        cen[ids] = np.stack([xi[:, 0] + lam * mx, xi[:, 1] + lam * my, xi[:, 2] + lam * mz], 1).astype(F32)
+        cov = np.stack([qxx / W - mx * mx, qyy / W - my * my, qzz / W - mz * mz,
+                        qxy / W - mx * my, qxz / W - mx * mz, qyz / W - my * mz], 1).astype(F32)
+        sig, R = jacobi(cov)
+        smax = np.fmax(np.fmax(sig[:, 0], sig[:, 1]), sig[:, 2])
+        lone = (nb < neps) | ~(smax > 0)
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            fl = (smax / kr).astype(F32)
+            s = (np.fmax(sig, fl[:, None]) / smax[:, None]).astype(F32)
+            inv_s = (F32(1) / s).astype(F32)
+            M = np.zeros((len(ids), 6), F32)
+            for col, (p, q) in enumerate(((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2))):
+                for k in range(3):
+                    M[:, col] = M[:, col] + (inv_s[:, k] * R[:, p, k]) * R[:, q, k]
+            f = (F32(1) / ((s[:, 0] * s[:, 1]) * s[:, 2])).astype(F32)
+        inv = F32(F32(1) / kn)
+        lone_m = np.array([inv, inv, inv, 0, 0, 0], F32)
+        mat[ids] = np.where(lone[:, None], lone_m[None, :], M)
+        det[ids] = np.where(lone, F32((inv * inv) * inv), f)
+        cnt[ids] = nb
+    return cen, mat, det, cnt
+
+
+# ---- the field ---------------------------------------------------------------------------------------------------------
+def _kernel(params):
+    """(h, pow2, pow2_der) as float32: ws_get_smoothing_kernel's constants."""
+    import water_sandbox_amd as ws
+
+    k = ws.get_smoothing_kernel(params)
+    return F32(params.smoothing_radius), F32(k.pow2), F32(k.pow2_der)
+
+
+def _candidates(params, cen, q):
+    grid = Grid(params)
+    bins = Binned(grid, cen)
+    return grid, bins
+
+
+def field32(params, cen, mat, det, q, gradient=True):
+    """The field of the header at the points q (m, 3), float32 with correctly rounded sqrt and division (the library's
+    WS_FLAG_IEEE_DIVISION form, bit for bit): (rho (m,), grad (m, 3) or None)."""
+    h, p2, p2d = _kernel(params)
+    cen = np.ascontiguousarray(cen, F32)
+    q = np.ascontiguousarray(q, F32).reshape(-1, 3)
+    grid, bins = _candidates(params, cen, q)
+    rho = np.zeros(len(q), F32)
+    grad = np.zeros((len(q), 3), F32)
+    for s0 in range(0, len(q), CHUNK):
+        sl = slice(s0, min(len(q), s0 + CHUNK))
+        cols = bins.columns(q[sl])
+        valid = cols >= 0
+        j = bins.order[np.where(valid, cols, 0)]
+        e = (cen[j] - q[sl][:, None, :]).astype(F32)
+        d2 = ((e[..., 0] * e[..., 0] + e[..., 1] * e[..., 1]) + e[..., 2] * e[..., 2]).astype(F32)
+        M = mat[j]
+        u = _mul(M, e)
+        dm2 = ((u[..., 0] * u[..., 0] + u[..., 1] * u[..., 1]) + u[..., 2] * u[..., 2]).astype(F32)
+        acc = valid & ~(d2 > grid.d2_accept) & ~(dm2 > grid.d2_accept)
+        dst = np.sqrt(dm2).astype(F32)
+        f = det[j]
+        v = (h - dst).astype(F32)
+        tr = ((v * v * p2) * f).astype(F32)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            vv = _mul(M, u)
+            slope = ((dst - h) * p2d).astype(F32)
+            tg = (((-vv / dst[..., None]) * slope[..., None]) * f[..., None]).astype(F32)
+        apart = dst > 0
+        r, g = rho[sl].copy(), grad[sl].copy()
+        for k in range(cols.shape[1]):
+            a = acc[:, k]
+            r = np.where(a, r + tr[:, k], r)
+            if gradient:
+                g = np.where(a[:, None], g + np.where(apart[:, k, None], tg[:, k], F32(0)), g)
+        rho[sl], grad[sl] = r, g
+    return rho, (grad if gradient else None)
+
+
+def _mul(M, e):
+    """u_a = (M_a0 e_x + M_a1 e_y) + M_a2 e_z in float32, M (..., 6) = xx yy zz xy xz yz."""
+    xx, yy, zz, xy, xz, yz = (M[..., k] for k in range(6))
+    ex, ey, ez = e[..., 0], e[..., 1], e[..., 2]
+    return np.stack([(xx * ex + xy * ey) + xz * ez, (xy * ex + yy * ey) + yz * ez, (xz * ex + yz * ey) + zz * ez],
+                    -1).astype(F32)
+
+
+def iso_field32(params, x, q):
+    """The density sampler's field (ws_sample_density_points, IEEE form) at q, float32: the isotropic reference."""
+    h, p2, _ = _kernel(params)
+    x = np.ascontiguousarray(x, F32)
+    q = np.ascontiguousarray(q, F32).reshape(-1, 3)
+    grid, bins = _candidates(params, x, q)
+    rho = np.zeros(len(q), F32)
+    for s0 in range(0, len(q), CHUNK):
+        sl = slice(s0, min(len(q), s0 + CHUNK))
+        cols = bins.columns(q[sl])
+        valid = cols >= 0
+        e = (x[bins.order[np.where(valid, cols, 0)]] - q[sl][:, None, :]).astype(F32)
+        d2 = ((e[..., 0] * e[..., 0] + e[..., 1] * e[..., 1]) + e[..., 2] * e[..., 2]).astype(F32)
+        acc = valid & ~(d2 > grid.d2_accept)
+        v = (h - np.sqrt(d2)).astype(F32)
+        t = (v * v * p2).astype(F32)
+        r = rho[sl].copy()
+        for k in range(cols.shape[1]):
+            r = np.where(acc[:, k], r + t[:, k], r)
+        rho[sl] = r
+    return rho
+
+
+def field64(params, cen, mat, det, q, c=4.0):
+    """The field at q in float64 over the float32 stage outputs, with the float32 accept decisions, and a per-point bound
+    tol = c u [(n + 8) sum |t| + sum |dt/ddM| G] per component (G = |(sum_b |M_ab| |e_b|)_a| >= dM bounds the rounding
+    of dM; for the gradient the analogous terms of v / dM): (rho, grad (m, 3), tol_rho, tol_grad (m, 3), n)."""
+    h32, p2_32, p2d_32 = _kernel(params)
+    h, p2, p2d = float(h32), float(p2_32), float(p2d_32)
+    cen = np.ascontiguousarray(cen, F32)
+    q = np.ascontiguousarray(q, F32).reshape(-1, 3)
+    grid, bins = _candidates(params, cen, q)
+    m = len(q)
+    rho, grad = np.zeros(m), np.zeros((m, 3))
+    tr, tg, nn = np.zeros(m), np.zeros((m, 3)), np.zeros(m)
+    sr, sg = np.zeros(m), np.zeros((m, 3))
+    for s0 in range(0, m, CHUNK):
+        sl = slice(s0, min(m, s0 + CHUNK))
+        cols = bins.columns(q[sl])
+        valid = cols >= 0
+        j = bins.order[np.where(valid, cols, 0)]
+        e32 = (cen[j] - q[sl][:, None, :]).astype(F32)
+        d2 = ((e32[..., 0] * e32[..., 0] + e32[..., 1] * e32[..., 1]) + e32[..., 2] * e32[..., 2]).astype(F32)
+        M32 = mat[j]
+        u32 = _mul(M32, e32)
+        dm2 = ((u32[..., 0] * u32[..., 0] + u32[..., 1] * u32[..., 1]) + u32[..., 2] * u32[..., 2]).astype(F32)
+        acc = valid & ~(d2 > grid.d2_accept) & ~(dm2 > grid.d2_accept)
+        e = cen[j].astype(np.float64) - q[sl][:, None, :].astype(np.float64)
+        M = M32.astype(np.float64)
+        f = det[j].astype(np.float64)
+        u = _mul64(M, e)
+        dM = np.sqrt(np.einsum("...a,...a->...", u, u))
+        v = _mul64(M, u)
+        Mabs = np.abs(M)
+        Ua = _mul64(Mabs, np.abs(e))
+        G = np.sqrt(np.einsum("...a,...a->...", Ua, Ua))
+        Va = _mul64(Mabs, Ua)
+        t_r = (h - dM) ** 2 * p2 * f
+        dt_r = 2.0 * np.abs(h - dM) * p2 * f
+        with np.errstate(divide="ignore", invalid="ignore"):
+            safe = np.where(dM > 0, dM, 1.0)
+            slope = (dM - h) * p2d
+            t_g = -v * (slope / safe)[..., None] * f[..., None]
+            # |d t_g|: the slope's change with dM, v's own rounding, and the 1 / dM
+            dt_g = abs(p2d) * f[..., None] * (G[..., None] * np.abs(v) / safe[..., None]
+                                              + np.abs(dM - h)[..., None] * (Va / safe[..., None]
+                                                                             + np.abs(v) * (G / safe ** 2)[..., None]))
+        apart = acc & (dM > 0)
+        t_g = np.where(apart[..., None], t_g, 0.0)
+        dt_g = np.where(apart[..., None], dt_g, 0.0)
+        t_r = np.where(acc, t_r, 0.0)
+        dt_r = np.where(acc, dt_r, 0.0)
+        rho[sl] = t_r.sum(1)
+        grad[sl] = t_g.sum(1)
+        nn[sl] = acc.sum(1)
+        tr[sl] = np.abs(t_r).sum(1)
+        tg[sl] = np.abs(t_g).sum(1)
+        sr[sl] = (dt_r * G).sum(1)
+        sg[sl] = dt_g.sum(1)
+    tol_r = c * U * ((nn + 8) * tr + sr)
+    tol_g = c * U * ((nn + 8)[:, None] * tg + sg)
+    return rho, grad, tol_r, tol_g, nn
+
+
+def _mul64(M, e):
+    xx, yy, zz, xy, xz, yz = (M[..., k] for k in range(6))
+    ex, ey, ez = e[..., 0], e[..., 1], e[..., 2]
+    return np.stack([xx * ex + xy * ey + xz * ez, xy * ex + yy * ey + yz * ez, xz * ex + yz * ey + zz * ez], -1)
+
+
+def grid_nodes(origin, spacing, dims):
+    """The grid's nodes, x fastest, as (nx ny nz, 3) float32 (fl(origin + fl(i * spacing)))."""
+    ax = S.axes(origin, spacing, dims)
+    z, y, x = np.meshgrid(ax[2], ax[1], ax[0], indexing="ij")
+    return np.stack([x.reshape(-1), y.reshape(-1), z.reshape(-1)], 1).astype(F32)
+
+
+def mesh(params, cen, mat, det, origin, spacing, dims, iso):
+    """The anisotropic surface of the header (IEEE field form) via surface_ref.extract: (xyz, normals, triangles)."""
+    nx, ny, nz = (int(v) for v in dims)
+    rho, grad = field32(params, cen, mat, det, grid_nodes(origin, spacing, dims))
+    return S.extract(rho.reshape(nz, ny, nx), grad.reshape(nz, ny, nx, 3), origin, spacing, dims, iso)
+
+
+def lone_radius(h, pow2, iso, kn):
+    """Radius of a lone particle's surface: k_n (h - sqrt(iso k_n^3 / pow2))."""
+    return kn * (h - np.sqrt(iso * kn ** 3 / pow2))

@@ -653,6 +653,11 @@ void free_field(ws_handle *h, bool all)
     F.mxyz = F.mnrm = nullptr;
     F.code_bytes = F.vbase_bytes = F.bcnt_bytes = F.bstart_bytes = F.bstate_bytes = F.tri_bytes = 0;
     F.mxyz_bytes = F.mnrm_bytes = 0;
+    hipFree(F.cxyz); hipFree(F.amf); hipFree(F.smf); hipFree(F.anb);
+    F.cxyz = nullptr;
+    F.amf = F.smf = nullptr;
+    F.anb = nullptr;
+    F.cxyz_bytes = F.amf_bytes = F.smf_bytes = F.anb_bytes = 0;
 }
 
 // An allocation of the sampler: a failure is WS_ERR_OUT_OF_MEMORY and leaves no sticky HIP error behind (the next
@@ -1400,9 +1405,12 @@ ws_status field_check(ws_handle *h, const float *xyz, uint32_t m, const float *g
 // fastest or the m points.  check() validates the query: before anything else on a single handle, after the collective
 // gather on a slab rank (a rank with a bad query leaves no peer waiting).  *contributed: a slab rank that wants nothing
 // took part in the gather and has nothing more to do.  The caller has checked h and its mode.
+// ap != nullptr (checked by check()): the anisotropic field -- the per-particle stage over the binned positions (F.cxyz,
+// F.amf, F.anb by id), then the centres binned the same way (F.spos, F.smf); stage_only: stop after the stage.
 template <class Check>
 ws_status field_sample_device(ws_handle *h, const float *xyz, uint32_t m, const float *grid6, const uint32_t *dims,
-                              bool want, bool rho_on, bool grad_on, Check check, bool *contributed)
+                              bool want, bool rho_on, bool grad_on, Check check, bool *contributed,
+                              const ws_aniso_params *ap = nullptr, bool stage_only = false)
 {
     *contributed = false;
     if (!h->slab && want) {
@@ -1446,6 +1454,25 @@ ws_status field_sample_device(ws_handle *h, const float *xyz, uint32_t m, const 
     wsk_view_fix(s, F.tmp, F.keys, F.start, F.perm, n);
     wsk_field_gather(s, F.perm, pos, F.spos, n);
     HIP_TRY(h, hipGetLastError());
+    if (ap) {
+        if ((st = field_grow(h, &F.cxyz, &F.cxyz_bytes, (size_t)n * 12))) return st;
+        if ((st = field_grow(h, &F.amf, &F.amf_bytes, (size_t)n * 32))) return st;
+        if ((st = field_grow(h, &F.anb, &F.anb_bytes, (size_t)n * 4))) return st;
+        if (!stage_only && (st = field_grow(h, &F.smf, &F.smf_bytes, (size_t)n * 32))) return st;
+        const WsAnisoParams a = {ap->smoothing, ap->max_ratio, ap->lone_scale, ap->min_neighbours};
+        wsk_aniso(s, d, F.start, F.spos, a, F.cxyz, F.amf, F.anb, n);
+        HIP_TRY(h, hipGetLastError());
+        if (stage_only) return WS_OK;
+        // the centres, binned by the same passes (the positions' binning is consumed: the stage ran before, in order)
+        wsk_field_keys(s, d, F.cxyz, F.keys, n);
+        HIP_TRY(h, hipMemsetAsync(F.count, 0, (size_t)d.ncells * 4, s));
+        wsk_view_count(s, F.keys, F.count, n);
+        wsk_scan(s, F.count, F.start, F.cursor, F.bsum, d.ncells, false, 0);
+        wsk_scatter(s, F.keys, F.cursor, F.tmp, n, nullptr);
+        wsk_view_fix(s, F.tmp, F.keys, F.start, F.perm, n);
+        wsk_aniso_gather(s, F.perm, F.cxyz, F.amf, F.spos, F.smf, n);
+        HIP_TRY(h, hipGetLastError());
+    }
     // queries and results
     const uint64_t nq = grid6 ? (uint64_t)dims[0] * dims[1] * dims[2] : m;
     if (!grid6) {
@@ -1457,15 +1484,27 @@ ws_status field_sample_device(ws_handle *h, const float *xyz, uint32_t m, const 
     if (grad_on && (st = field_grow(h, &F.grad, &F.grad_bytes, (size_t)nq * 12))) return st;
     // the brick kernel from one node per cell up (spacing <= h on every axis); the points form below
     const bool bricks = grid6 && grid6[3] <= d.h && grid6[4] <= d.h && grid6[5] <= d.h;
-    wsk_field_sample(s, d, F.start, F.spos, h->ieee, grad_on, F.q, (uint32_t)nq, grid6, dims, bricks,
+    wsk_field_sample(s, d, F.start, F.spos, ap ? F.smf : nullptr, h->ieee, grad_on, F.q, (uint32_t)nq, grid6, dims, bricks,
                      rho_on ? F.rho : nullptr, grad_on ? F.grad : nullptr);
     HIP_TRY(h, hipGetLastError());
     return WS_OK;
 }
 
-// Both sample calls: the field into device scratch, then copied out.
+// The anisotropy parameters of a call (include/wsfluid.h ws_aniso_params).
+ws_status aniso_check(ws_handle *h, const ws_aniso_params *a)
+{
+    if (!a) return fail(h, WS_ERR_INVALID_ARG, "anisotropy: the parameters are required");
+    if (!isfinite(a->smoothing) || !isfinite(a->max_ratio) || !isfinite(a->lone_scale))
+        return fail(h, WS_ERR_INVALID_ARG, "anisotropy: parameters must be finite");
+    if (!(a->smoothing >= 0.0f && a->smoothing <= 1.0f)) return fail(h, WS_ERR_INVALID_ARG, "anisotropy: smoothing must lie in [0, 1]");
+    if (!(a->max_ratio >= 1.0f)) return fail(h, WS_ERR_INVALID_ARG, "anisotropy: max_ratio must be >= 1");
+    if (!(a->lone_scale > 0.0f && a->lone_scale <= 1.0f)) return fail(h, WS_ERR_INVALID_ARG, "anisotropy: lone_scale must lie in (0, 1]");
+    return WS_OK;
+}
+
+// Both sample calls, isotropic (aniso false) or anisotropic (ap): the field into device scratch, then copied out.
 ws_status sample_density(ws_handle *h, const float *xyz, uint32_t m, const float *grid6, const uint32_t *dims,
-                         float *out_rho, float *out_grad)
+                         float *out_rho, float *out_grad, bool aniso = false, const ws_aniso_params *ap = nullptr)
 {
     if (!h) return WS_ERR_INVALID_ARG;
     WS_DEAD_CHECK(h);
@@ -1473,8 +1512,15 @@ ws_status sample_density(ws_handle *h, const float *xyz, uint32_t m, const float
     const bool want = out_rho || out_grad;
     if (!want && !h->slab) return fail(h, WS_ERR_INVALID_ARG, "density field: both outputs are NULL");
     bool contributed = false;
-    const ws_status st = field_sample_device(h, xyz, m, grid6, dims, want, out_rho != nullptr, out_grad != nullptr,
-                                             [&]() { return field_check(h, xyz, m, grid6, dims); }, &contributed);
+    auto check = [&]() -> ws_status {
+        if (aniso) {
+            const ws_status st = aniso_check(h, ap);
+            if (st) return st;
+        }
+        return field_check(h, xyz, m, grid6, dims);
+    };
+    const ws_status st = field_sample_device(h, xyz, m, grid6, dims, want, out_rho != nullptr, out_grad != nullptr, check,
+                                             &contributed, aniso ? ap : nullptr);
     if (st || contributed) return st;
     hipStream_t s = h->stream;
     auto &F = h->field;
@@ -1489,8 +1535,10 @@ ws_status sample_density(ws_handle *h, const float *xyz, uint32_t m, const float
 // ws_extract_surface: the grid field into device scratch, the node codes and per-workgroup totals, their scans, the
 // counts back to the host and -- when the caller's buffers hold them -- the mesh.  query = origin, spacing and dims were
 // given (grid6 / dims hold placeholders otherwise): a slab rank without them still takes part in the gather, then fails.
+// aniso: ws_extract_aniso_surface (ap checked with the query).
 ws_status extract_surface(ws_handle *h, bool query, const float *grid6, const uint32_t *dims, float iso, uint32_t max_v,
-                          uint32_t max_t, float *out_xyz, float *out_nrm, uint32_t *out_tri, uint32_t *n_v, uint32_t *n_t)
+                          uint32_t max_t, float *out_xyz, float *out_nrm, uint32_t *out_tri, uint32_t *n_v, uint32_t *n_t,
+                          bool aniso = false, const ws_aniso_params *ap = nullptr)
 {
     WS_DEAD_CHECK(h);
     if (h->flags & WS_FLAG_REFERENCE_ORDER) return fail(h, WS_ERR_UNSUPPORTED, "surface: not in the reference-order validation mode");
@@ -1507,13 +1555,18 @@ ws_status extract_surface(ws_handle *h, bool query, const float *grid6, const ui
         }
         if (nodes > (1ull << 28)) return fail(h, WS_ERR_INVALID_ARG, "surface: more than 2^28 nodes");
         if (!(iso > 0.0f) || !isfinite(iso)) return fail(h, WS_ERR_INVALID_ARG, "surface: iso must be finite and > 0");
+        if (aniso) {
+            const ws_status st = aniso_check(h, ap);
+            if (st) return st;
+        }
         return field_check(h, nullptr, 0, grid6, dims);
     };
     // the gradient only for a call that asks for normals and passes both mesh buffers (a call whose counts then exceed
     // its capacities has sampled it for nothing; FluidWorker sizes its first guess from the previous mesh)
     const bool grad_on = out_nrm && out_xyz && out_tri;
     bool contributed = false;
-    ws_status st = field_sample_device(h, nullptr, 0, grid6, dims, want, true, grad_on, check, &contributed);
+    ws_status st = field_sample_device(h, nullptr, 0, grid6, dims, want, true, grad_on, check, &contributed,
+                                       aniso ? ap : nullptr);
     if (st || contributed) return st;
     hipStream_t s = h->stream;
     auto &F = h->field;
@@ -1550,6 +1603,37 @@ ws_status extract_surface(ws_handle *h, bool query, const float *grid6, const ui
         if (V && grad_on) HIP_TRY(h, hipMemcpyAsync(out_nrm, F.mnrm, V * 12, hipMemcpyDeviceToHost, s));
         if (T) HIP_TRY(h, hipMemcpyAsync(out_tri, F.tri, T * 12, hipMemcpyDeviceToHost, s));
         HIP_TRY(h, hipStreamSynchronize(s));
+    }
+    drain_profile(h);
+    return WS_OK;
+}
+
+// ws_read_anisotropy: the stage alone, copied out by id (the ellipsoids split into M and f on the host).
+ws_status read_anisotropy(ws_handle *h, const ws_aniso_params *ap, float *out_c, float *out_m, float *out_f, uint32_t *out_n)
+{
+    WS_DEAD_CHECK(h);
+    if (h->flags & WS_FLAG_REFERENCE_ORDER) return fail(h, WS_ERR_UNSUPPORTED, "anisotropy: not in the reference-order validation mode");
+    const bool want = out_c || out_m || out_f || out_n;
+    if (!want && !h->slab) return aniso_check(h, ap);
+    bool contributed = false;
+    ws_status st = field_sample_device(h, nullptr, 0, nullptr, nullptr, want, false, false, [&]() { return aniso_check(h, ap); },
+                                       &contributed, ap, true);
+    if (st || contributed) return st;
+    hipStream_t s = h->stream;
+    auto &F = h->field;
+    const size_t n = F.n;
+    if (out_c) HIP_TRY(h, hipMemcpyAsync(out_c, F.cxyz, n * 12, hipMemcpyDeviceToHost, s));
+    if (out_n) HIP_TRY(h, hipMemcpyAsync(out_n, F.anb, n * 4, hipMemcpyDeviceToHost, s));
+    std::vector<float> mf;
+    if (out_m || out_f) {
+        mf.resize(n * 8);
+        HIP_TRY(h, hipMemcpyAsync(mf.data(), F.amf, n * 32, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(h, hipStreamSynchronize(s));
+    for (size_t i = 0; i < n && (out_m || out_f); i++) {
+        if (out_m)
+            for (int k = 0; k < 6; k++) out_m[6 * i + k] = mf[8 * i + k];
+        if (out_f) out_f[i] = mf[8 * i + 6];
     }
     drain_profile(h);
     return WS_OK;
@@ -1600,6 +1684,70 @@ ws_status ws_extract_surface(ws_handle *h, const float origin[3], const float sp
     }
     return extract_surface(h, query, g6, query ? dims : two, iso, max_vertices, max_triangles, out_xyz, out_normal,
                            out_tri, n_vertices, n_triangles);
+}
+
+// ======================================================================================
+// anisotropic kernels (Yu & Turk 2013; include/wsfluid.h defines the stage, the field and the mesh)
+// ======================================================================================
+ws_status ws_default_aniso_params(ws_aniso_params *out)
+{
+    if (!out) return WS_ERR_INVALID_ARG;
+    out->smoothing = 0.9f;
+    out->max_ratio = 4.0f;
+    out->lone_scale = 0.5f;
+    out->min_neighbours = 12u;
+    return WS_OK;
+}
+
+ws_status ws_read_anisotropy(ws_handle *h, const ws_aniso_params *a, float *out_centre, float *out_matrix, float *out_scale,
+                             uint32_t *out_neighbours)
+{
+    if (!h) return WS_ERR_INVALID_ARG;
+    return read_anisotropy(h, a, out_centre, out_matrix, out_scale, out_neighbours);
+}
+
+ws_status ws_sample_aniso_grid(ws_handle *h, const ws_aniso_params *a, const float origin[3], const float spacing[3],
+                               const uint32_t dims[3], float *out_field, float *out_gradient)
+{
+    if (!h) return WS_ERR_INVALID_ARG;
+    if ((out_field || out_gradient || !h->slab) && (!origin || !spacing || !dims))
+        return fail(h, WS_ERR_INVALID_ARG, "density field: origin, spacing and dims are required");
+    float g6[6] = {0.f, 0.f, 0.f, 1.f, 1.f, 1.f};
+    const uint32_t one[3] = {1u, 1u, 1u};
+    if (origin && spacing && dims) {
+        for (int k = 0; k < 3; k++) {
+            g6[k] = origin[k];
+            g6[3 + k] = spacing[k];
+        }
+    }
+    return sample_density(h, nullptr, 0, g6, dims ? dims : one, out_field, out_gradient, true, a);
+}
+
+ws_status ws_sample_aniso_points(ws_handle *h, const ws_aniso_params *a, const float *xyz, uint32_t m, float *out_field,
+                                 float *out_gradient)
+{
+    if (!h) return WS_ERR_INVALID_ARG;
+    return sample_density(h, xyz, m, nullptr, nullptr, out_field, out_gradient, true, a);
+}
+
+ws_status ws_extract_aniso_surface(ws_handle *h, const ws_aniso_params *a, const float origin[3], const float spacing[3],
+                                   const uint32_t dims[3], float iso, uint32_t max_vertices, uint32_t max_triangles,
+                                   float *out_xyz, float *out_normal, uint32_t *out_tri, uint32_t *n_vertices,
+                                   uint32_t *n_triangles)
+{
+    if (!h) return WS_ERR_INVALID_ARG;
+    const bool query = origin && spacing && dims;
+    if (!query && !h->slab) return fail(h, WS_ERR_INVALID_ARG, "surface: origin, spacing and dims are required");
+    float g6[6] = {0.f, 0.f, 0.f, 1.f, 1.f, 1.f};
+    const uint32_t two[3] = {2u, 2u, 2u};
+    if (query) {
+        for (int k = 0; k < 3; k++) {
+            g6[k] = origin[k];
+            g6[3 + k] = spacing[k];
+        }
+    }
+    return extract_surface(h, query, g6, query ? dims : two, iso, max_vertices, max_triangles, out_xyz, out_normal,
+                           out_tri, n_vertices, n_triangles, true, a);
 }
 
 // ======================================================================================

@@ -248,6 +248,12 @@ struct ws_handle {
         float *mxyz = nullptr, *mnrm = nullptr;
         size_t code_bytes = 0, vbase_bytes = 0, bcnt_bytes = 0, bstart_bytes = 0, bstate_bytes = 0, tri_bytes = 0,
                mxyz_bytes = 0, mnrm_bytes = 0;
+        // anisotropic kernels (ws_read_anisotropy, ws_sample_aniso_*, ws_extract_aniso_surface), grow-only: centres,
+        // ellipsoids and neighbour counts by id, the centres' ellipsoids in their cell order (their {c, id} reuse spos)
+        float *cxyz = nullptr;
+        float4 *amf = nullptr, *smf = nullptr;
+        uint32_t *anb = nullptr;
+        size_t cxyz_bytes = 0, amf_bytes = 0, smf_bytes = 0, anb_bytes = 0;
     } field;
 
     // profiling
@@ -414,10 +420,22 @@ void wsk_set_words4(hipStream_t s, uint32_t *p, uint32_t a, uint32_t b, uint32_t
 // density field sampler (ws_sample_density_*)
 void wsk_field_keys(hipStream_t s, const WsDev &d, const float *xyz, uint32_t *keys, uint32_t n);
 void wsk_field_gather(hipStream_t s, const uint32_t *perm, const float *xyz, float4 *spos, uint32_t n);
-// grid6 = origin xyz, spacing xyz (nullptr: the m points of xyz); bricks: the brick kernel (grid only)
-void wsk_field_sample(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, bool ieee, bool grad_on,
-                      const float *xyz, uint32_t m, const float *grid6, const uint32_t *dims, bool bricks, float *rho,
-                      float *grad);
+// grid6 = origin xyz, spacing xyz (nullptr: the m points of xyz); bricks: the brick kernel (grid only); smf = nullptr:
+// the density sampler (spos = sorted positions), else the anisotropic field (spos = sorted centres, smf their ellipsoids)
+void wsk_field_sample(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, const float4 *smf, bool ieee,
+                      bool grad_on, const float *xyz, uint32_t m, const float *grid6, const uint32_t *dims, bool bricks,
+                      float *rho, float *grad);
+// anisotropic kernels (ws_read_anisotropy / ws_sample_aniso_* / ws_extract_aniso_surface): the per-particle stage over
+// the sampler's binning of the positions (by id: centres, ellipsoids as 2 float4, neighbour counts), then the records
+// of the centres in their own cell order
+struct WsAnisoParams {
+    float lambda, kr, kn;
+    uint32_t neps;
+};
+void wsk_aniso(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, WsAnisoParams ap, float *cxyz,
+               float4 *mf, uint32_t *nb, uint32_t n);
+void wsk_aniso_gather(hipStream_t s, const uint32_t *perm, const float *cxyz, const float4 *mf, float4 *srec, float4 *smf,
+                      uint32_t n);
 // surface extraction (ws_extract_surface) on a sampled grid: node codes and per-workgroup totals (wsk_iso_blocks() of
 // them, then one 0 each), then -- after two wsk_scan launches over blocks + 1 totals -- vertices and triangles
 uint32_t wsk_iso_blocks(const uint32_t *dims);

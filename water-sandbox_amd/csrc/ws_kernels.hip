@@ -2713,11 +2713,64 @@ __device__ __forceinline__ void field_pair(const WsDev &d, float ex, float ey, f
     }
 }
 
+// The candidate source of a field kernel: FieldIso (the density sampler: sorted positions, K4's pair term) or FieldAniso
+// (ws_sample_aniso_*: sorted centres and their ellipsoids; points form only).  at(j) = {position, id bits} of sorted
+// candidate j; pair() adds candidate j, which passed the isotropic distance test.
+struct FieldIso {
+    const float4 *__restrict__ spos;
+    __device__ __forceinline__ float4 at(uint32_t j) const { return spos[j]; }
+    template <bool IEEE, bool GRAD>
+    __device__ __forceinline__ void pair(const WsDev &d, uint32_t, float ex, float ey, float ez, float d2, FieldAcc &a) const
+    {
+        field_pair<IEEE, GRAD>(d, ex, ey, ez, d2, a);
+    }
+};
+
+// ws_sample_aniso_*: candidates are the particles' CENTRES c_j binned like positions, each with its ellipsoid M_j (symmetric:
+// xx yy zz xy xz yz) and f_j = det M_j in smf[2j] = {xx, yy, zz, xy}, smf[2j + 1] = {xz, yz, f, 0}.  A candidate that
+// passed the isotropic test counts iff dM2 = |u|^2 <= d2_accept, u = M e; its terms are the isotropic ones with e -> v =
+// M u and d -> dM, times f last (include/wsfluid.h).  M = I, f = 1 gives field_pair's bits.
+struct FieldAniso {
+    const float4 *__restrict__ srec;  // {c, id bits} in cell order
+    const float4 *__restrict__ smf;
+    __device__ __forceinline__ float4 at(uint32_t j) const { return srec[j]; }
+    template <bool IEEE, bool GRAD>
+    __device__ __forceinline__ void pair(const WsDev &d, uint32_t j, float ex, float ey, float ez, float, FieldAcc &a) const
+    {
+        const float4 m0 = smf[2 * (size_t)j], m1 = smf[2 * (size_t)j + 1];
+        const float mxx = m0.x, myy = m0.y, mzz = m0.z, mxy = m0.w, mxz = m1.x, myz = m1.y, f = m1.z;
+        const float ux = (mxx * ex + mxy * ey) + mxz * ez;
+        const float uy = (mxy * ex + myy * ey) + myz * ez;
+        const float uz = (mxz * ex + myz * ey) + mzz * ez;
+        const float dm2 = ux * ux + uy * uy + uz * uz;
+        if (dm2 > d.d2_accept) return;
+        const float dst = ws_sqrt<IEEE>(dm2);
+        a.rho += sk_density(d, dst) * f;
+        if constexpr (GRAD) {
+            const float vx = (mxx * ux + mxy * uy) + mxz * uz;
+            const float vy = (mxy * ux + myy * uy) + myz * uz;
+            const float vz = (mxz * ux + myz * uy) + mzz * uz;
+            const float slope = sk_der(d, dst);
+            const bool apart = dst > 0.f;
+            if constexpr (IEEE) {
+                const WsDivisor<IEEE> by_dst(dst);
+                a.gx += apart ? (by_dst(-vx) * slope) * f : 0.f;
+                a.gy += apart ? (by_dst(-vy) * slope) * f : 0.f;
+                a.gz += apart ? (by_dst(-vz) * slope) * f : 0.f;
+            } else {
+                const float s = slope * __builtin_amdgcn_rcpf(dst);
+                a.gx += apart ? (-vx * s) * f : 0.f;
+                a.gy += apart ? (-vy * s) * f : 0.f;
+                a.gz += apart ? (-vz * s) * f : 0.f;
+            }
+        }
+    }
+};
+
 // The definition: the 27 cells around the query's (clamped) cell, as 9 contiguous z-runs in increasing cell id.
 // start has ncells + 1 entries (start[ncells] = n).
-template <bool IEEE, bool GRAD>
-__device__ __forceinline__ FieldAcc field_sweep(const WsDev &d, const uint32_t *__restrict__ start, const float4 *__restrict__ spos,
-                                                float4 o)
+template <bool IEEE, bool GRAD, class Src>
+__device__ __forceinline__ FieldAcc field_sweep(const WsDev &d, const uint32_t *__restrict__ start, const Src &src, float4 o)
 {
     FieldAcc a = {0.f, 0.f, 0.f, 0.f};
     const int cx = field_axis_cell(d, 0, o.x), cy = field_axis_cell(d, 1, o.y), cz = field_axis_cell(d, 2, o.z);
@@ -2727,11 +2780,11 @@ __device__ __forceinline__ FieldAcc field_sweep(const WsDev &d, const uint32_t *
             const uint32_t col = (uint32_t)(x * d.dim[1] + y) * (uint32_t)d.dim[2];
             const uint32_t b = start[col + z0], e = start[col + z1 + 1];
             for (uint32_t j = b; j < e; j++) {
-                const float4 q = spos[j];
+                const float4 q = src.at(j);
                 const float ex = q.x - o.x, ey = q.y - o.y, ez = q.z - o.z;
                 const float d2 = ex * ex + ey * ey + ez * ez;
                 if (d2 > d.d2_accept) continue;
-                field_pair<IEEE, GRAD>(d, ex, ey, ez, d2, a);
+                src.template pair<IEEE, GRAD>(d, j, ex, ey, ez, d2, a);
             }
         }
     }
@@ -2750,8 +2803,8 @@ __device__ __forceinline__ void field_store(const FieldAcc &a, size_t at, float 
 
 // Points form: one lane per query.  GRID = the queries are the nodes of g (node index = lane index, x fastest) -- the
 // grid call's form below one node per cell; otherwise the m points of xyz.
-template <bool IEEE, bool GRAD, bool GRID>
-__global__ void __launch_bounds__(WS_BLOCK) k_field_points(WsDev d, const uint32_t *__restrict__ start, const float4 *__restrict__ spos,
+template <bool IEEE, bool GRAD, bool GRID, class Src>
+__global__ void __launch_bounds__(WS_BLOCK) k_field_points(WsDev d, const uint32_t *__restrict__ start, Src src,
                                                            const float *__restrict__ xyz, WsFieldGrid g, uint32_t m,
                                                            float *__restrict__ rho, float *__restrict__ grad)
 {
@@ -2764,7 +2817,7 @@ __global__ void __launch_bounds__(WS_BLOCK) k_field_points(WsDev d, const uint32
     } else {
         o = make_float4(xyz[3 * (size_t)t], xyz[3 * (size_t)t + 1], xyz[3 * (size_t)t + 2], 0.f);
     }
-    field_store(field_sweep<IEEE, GRAD>(d, start, spos, o), t, rho, grad);
+    field_store(field_sweep<IEEE, GRAD>(d, start, src, o), t, rho, grad);
 }
 
 // Grid form (the hot path): one wave per brick of 4 x 4 x 4 nodes, lane l = node (l & 3, (l >> 2) & 3, l >> 4) of the
@@ -2782,9 +2835,9 @@ __global__ void __launch_bounds__(WS_BLOCK) k_field_points(WsDev d, const uint32
 // staged candidate: xyz and the cell relative to the brick's first cell, one byte per axis + 1 (w lane)
 __device__ __forceinline__ uint32_t field_pack_cell(int x, int y, int z) { return (uint32_t)((x + 1) << 16 | (y + 1) << 8 | (z + 1)); }
 
-template <bool IEEE, bool GRAD>
-__global__ void __launch_bounds__(64) k_field_bricks(WsDev d, const uint32_t *__restrict__ start, const float4 *__restrict__ spos,
-                                                     WsFieldGrid g, uint32_t bx_n, uint32_t by_n, float *__restrict__ rho,
+template <bool IEEE, bool GRAD, class Src>
+__global__ void __launch_bounds__(64) k_field_bricks(WsDev d, const uint32_t *__restrict__ start, Src src, WsFieldGrid g,
+                                                     uint32_t bx_n, uint32_t by_n, float *__restrict__ rho,
                                                      float *__restrict__ grad)
 {
     __shared__ float4 s_q[FB_CHUNK];
@@ -2806,7 +2859,7 @@ __global__ void __launch_bounds__(64) k_field_bricks(WsDev d, const uint32_t *__
     const int ncol = (x1 - x0 + 1) * ny_c;
     const size_t at = ((size_t)k * g.ny + j) * g.nx + i;
     if (ncol > FB_COLS) {  // (a spacing the host would not send here: take the points form, lane by lane)
-        if (valid) field_store(field_sweep<IEEE, GRAD>(d, start, spos, o), at, rho, grad);
+        if (valid) field_store(field_sweep<IEEE, GRAD>(d, start, src, o), at, rho, grad);
         return;
     }
     // the runs: lane c = column c (x slower), then an exclusive scan of their lengths
@@ -2838,7 +2891,7 @@ __global__ void __launch_bounds__(64) k_field_bricks(WsDev d, const uint32_t *__
                     if (s_pre[mid] <= v) lo_c = mid;
                     else hi_c = mid - 1;
                 }
-                const float4 q = spos[s_b[lo_c] + (v - s_pre[lo_c])];
+                const float4 q = src.at(s_b[lo_c] + (v - s_pre[lo_c]));
                 const uint32_t code = field_pack_cell(lo_c / ny_c, lo_c % ny_c, field_axis_cell(d, 2, q.z) - z0);
                 s_q[t] = make_float4(q.x, q.y, q.z, __uint_as_float(code));
             }
@@ -2850,23 +2903,24 @@ __global__ void __launch_bounds__(64) k_field_bricks(WsDev d, const uint32_t *__
                 if (d2 > d.d2_accept) continue;
                 // in the node's 27 cells: every byte of code - own lies in [0, 2] (guard bit 7 keeps the bytes apart)
                 if ((((__float_as_uint(q.w) | 0x808080u) - own) & 0xFCFCFCu) != 0x808080u) continue;
-                field_pair<IEEE, GRAD>(d, ex, ey, ez, d2, a);
+                src.template pair<IEEE, GRAD>(d, 0u, ex, ey, ez, d2, a);  // (FieldIso only: see wsk_field_sample)
             }
         }
     }
     if (valid) field_store(a, at, rho, grad);
 }
 
-void wsk_field_sample(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, bool ieee, bool grad_on,
-                      const float *xyz, uint32_t m, const float *grid6, const uint32_t *dims, bool bricks, float *rho,
-                      float *grad)
+template <class Src>
+void field_sample_launch(hipStream_t s, const WsDev &d, const uint32_t *start, Src src, bool ieee, bool grad_on,
+                         const float *xyz, uint32_t m, const float *grid6, const uint32_t *dims, bool bricks, float *rho,
+                         float *grad)
 {
     WsFieldGrid g = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0u, 0u, 0u};
     if (grid6) g = {grid6[0], grid6[1], grid6[2], grid6[3], grid6[4], grid6[5], dims[0], dims[1], dims[2]};
     if (grid6 && bricks) {
         const uint32_t bx = cdiv(dims[0], 4u), by = cdiv(dims[1], 4u), bz = cdiv(dims[2], 4u);
         const dim3 grid(bx * by * bz);
-#define FB_LAUNCH(I, G) hipLaunchKernelGGL((k_field_bricks<I, G>), grid, dim3(64), 0, s, d, start, spos, g, bx, by, rho, grad)
+#define FB_LAUNCH(I, G) hipLaunchKernelGGL((k_field_bricks<I, G, Src>), grid, dim3(64), 0, s, d, start, src, g, bx, by, rho, grad)
         if (ieee) { if (grad_on) FB_LAUNCH(true, true); else FB_LAUNCH(true, false); }
         else { if (grad_on) FB_LAUNCH(false, true); else FB_LAUNCH(false, false); }
 #undef FB_LAUNCH
@@ -2874,7 +2928,7 @@ void wsk_field_sample(hipStream_t s, const WsDev &d, const uint32_t *start, cons
     }
     const dim3 grid(cdiv(m, WS_BLOCK));
 #define FP_LAUNCH(I, G, R) \
-    hipLaunchKernelGGL((k_field_points<I, G, R>), grid, dim3(WS_BLOCK), 0, s, d, start, spos, xyz, g, m, rho, grad)
+    hipLaunchKernelGGL((k_field_points<I, G, R, Src>), grid, dim3(WS_BLOCK), 0, s, d, start, src, xyz, g, m, rho, grad)
     if (grid6) {
         if (ieee) { if (grad_on) FP_LAUNCH(true, true, true); else FP_LAUNCH(true, false, true); }
         else { if (grad_on) FP_LAUNCH(false, true, true); else FP_LAUNCH(false, false, true); }
@@ -2883,6 +2937,158 @@ void wsk_field_sample(hipStream_t s, const WsDev &d, const uint32_t *start, cons
         else { if (grad_on) FP_LAUNCH(false, true, false); else FP_LAUNCH(false, false, false); }
     }
 #undef FP_LAUNCH
+}
+
+void wsk_field_sample(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, const float4 *smf, bool ieee,
+                      bool grad_on, const float *xyz, uint32_t m, const float *grid6, const uint32_t *dims, bool bricks,
+                      float *rho, float *grad)
+{
+    // The anisotropic field takes the points form on grids too: a brick form of it (the staged candidates' sorted indices
+    // in LDS, M and f loaded for accepted pairs) lost to the points form on sparse C3 at spacing h.
+    if (smf) field_sample_launch(s, d, start, FieldAniso{spos, smf}, ieee, grad_on, xyz, m, grid6, dims, false, rho, grad);
+    else field_sample_launch(s, d, start, FieldIso{spos}, ieee, grad_on, xyz, m, grid6, dims, bricks, rho, grad);
+}
+
+// ---------------------------------------------------------------------------------
+// anisotropic kernels (ws_read_anisotropy / ws_sample_aniso_* / ws_extract_aniso_surface; never inside ws_step)
+//
+// k_aniso, the per-particle stage (include/wsfluid.h pins it bit for bit): one lane per particle in the sampler's cell
+// order of the current positions, so the lanes of a wave sweep neighbouring cells.  One sweep of the 27 cells around
+// x_i (the density sampler's canonical order and accept test) gives the weighted moments about x_i; the mean, the
+// covariance, a fixed 5-sweep cyclic Jacobi and the ellipsoid are then formed in registers.  IEEE arithmetic whatever
+// the handle's flags (correctly rounded sqrt and division, no contraction).  Writes, by id: the centre, M and f
+// (mf[2 id], mf[2 id + 1] as FieldAniso reads them) and the neighbour count.
+// ---------------------------------------------------------------------------------
+
+// One classic Jacobi rotation zeroing a_pq of the symmetric 3x3 A (r = the third index), R = R J (rp, rq: columns p, q).
+__device__ __forceinline__ void aniso_rotate(float &app, float &aqq, float &apq, float &arp, float &arq, float *rp, float *rq)
+{
+    if (apq == 0.f) return;
+    const float theta = (aqq - app) / (2.f * apq);
+    float t;
+    if (fabsf(theta) > 0x1p32f) t = 1.f / (2.f * theta);
+    else t = (theta >= 0.f ? 1.f : -1.f) / (fabsf(theta) + sqrtf(theta * theta + 1.f));
+    const float c = 1.f / sqrtf(t * t + 1.f), s = t * c;
+    app = app - t * apq;
+    aqq = aqq + t * apq;
+    apq = 0.f;
+    const float xp = arp, xq = arq;
+    arp = c * xp - s * xq;
+    arq = s * xp + c * xq;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const float vp = rp[k], vq = rq[k];
+        rp[k] = c * vp - s * vq;
+        rq[k] = s * vp + c * vq;
+    }
+}
+
+__global__ void __launch_bounds__(WS_BLOCK) k_aniso(WsDev d, const uint32_t *__restrict__ start, const float4 *__restrict__ spos,
+                                                    WsAnisoParams ap, float *__restrict__ cxyz, float4 *__restrict__ mf,
+                                                    uint32_t *__restrict__ nb, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * WS_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const float4 o = spos[i];
+    const uint32_t id = __float_as_uint(o.w);
+    float W = 0.f, sx = 0.f, sy = 0.f, sz = 0.f, qxx = 0.f, qyy = 0.f, qzz = 0.f, qxy = 0.f, qxz = 0.f, qyz = 0.f;
+    uint32_t cnt = 0;
+    const int cx = field_axis_cell(d, 0, o.x), cy = field_axis_cell(d, 1, o.y), cz = field_axis_cell(d, 2, o.z);
+    const int z0 = max(cz - 1, 0), z1 = min(cz + 1, d.dim[2] - 1);
+    for (int x = max(cx - 1, 0); x <= min(cx + 1, d.dim[0] - 1); x++) {
+        for (int y = max(cy - 1, 0); y <= min(cy + 1, d.dim[1] - 1); y++) {
+            const uint32_t col = (uint32_t)(x * d.dim[1] + y) * (uint32_t)d.dim[2];
+            const uint32_t b = start[col + z0], e = start[col + z1 + 1];
+            for (uint32_t j = b; j < e; j++) {
+                const float4 q = spos[j];
+                const float ex = q.x - o.x, ey = q.y - o.y, ez = q.z - o.z;
+                const float d2 = ex * ex + ey * ey + ez * ez;
+                if (d2 > d.d2_accept) continue;
+                const float r = sqrtf(d2) / d.h;
+                const float w = 1.f - (r * r) * r;
+                const float wx = w * ex, wy = w * ey, wz = w * ez;
+                cnt++;
+                W += w;
+                sx += wx;
+                sy += wy;
+                sz += wz;
+                qxx += wx * ex;
+                qyy += wy * ey;
+                qzz += wz * ez;
+                qxy += wx * ey;
+                qxz += wx * ez;
+                qyz += wy * ez;
+            }
+        }
+    }
+    const float mx = sx / W, my = sy / W, mz = sz / W;
+    cxyz[3 * (size_t)id] = o.x + ap.lambda * mx;
+    cxyz[3 * (size_t)id + 1] = o.y + ap.lambda * my;
+    cxyz[3 * (size_t)id + 2] = o.z + ap.lambda * mz;
+    nb[id] = cnt;
+    // covariance: a00 a11 a22 a01 a02 a12
+    float a00 = qxx / W - mx * mx, a11 = qyy / W - my * my, a22 = qzz / W - mz * mz;
+    float a01 = qxy / W - mx * my, a02 = qxz / W - mx * mz, a12 = qyz / W - my * mz;
+    float Mxx, Myy, Mzz, Mxy = 0.f, Mxz = 0.f, Myz = 0.f, f;
+    bool lone = cnt < ap.neps;
+    if (!lone) {
+        float r0[3] = {1.f, 0.f, 0.f}, r1[3] = {0.f, 1.f, 0.f}, r2[3] = {0.f, 0.f, 1.f};  // columns of R
+#pragma unroll
+        for (int sweep = 0; sweep < 5; sweep++) {
+            aniso_rotate(a00, a11, a01, a02, a12, r0, r1);  // (0, 1), r = 2
+            aniso_rotate(a00, a22, a02, a01, a12, r0, r2);  // (0, 2), r = 1
+            aniso_rotate(a11, a22, a12, a01, a02, r1, r2);  // (1, 2), r = 0
+        }
+        const float smax = fmaxf(fmaxf(a00, a11), a22);
+        if (smax > 0.f) {
+            const float fl = smax / ap.kr;
+            const float s0 = fmaxf(a00, fl) / smax, s1 = fmaxf(a11, fl) / smax, s2 = fmaxf(a22, fl) / smax;
+            const float i0 = 1.f / s0, i1 = 1.f / s1, i2 = 1.f / s2;
+            Mxx = 0.f; Myy = 0.f; Mzz = 0.f;
+            Mxx = Mxx + (i0 * r0[0]) * r0[0]; Mxx = Mxx + (i1 * r1[0]) * r1[0]; Mxx = Mxx + (i2 * r2[0]) * r2[0];
+            Myy = Myy + (i0 * r0[1]) * r0[1]; Myy = Myy + (i1 * r1[1]) * r1[1]; Myy = Myy + (i2 * r2[1]) * r2[1];
+            Mzz = Mzz + (i0 * r0[2]) * r0[2]; Mzz = Mzz + (i1 * r1[2]) * r1[2]; Mzz = Mzz + (i2 * r2[2]) * r2[2];
+            Mxy = Mxy + (i0 * r0[0]) * r0[1]; Mxy = Mxy + (i1 * r1[0]) * r1[1]; Mxy = Mxy + (i2 * r2[0]) * r2[1];
+            Mxz = Mxz + (i0 * r0[0]) * r0[2]; Mxz = Mxz + (i1 * r1[0]) * r1[2]; Mxz = Mxz + (i2 * r2[0]) * r2[2];
+            Myz = Myz + (i0 * r0[1]) * r0[2]; Myz = Myz + (i1 * r1[1]) * r1[2]; Myz = Myz + (i2 * r2[1]) * r2[2];
+            f = 1.f / ((s0 * s1) * s2);
+        } else {
+            lone = true;
+        }
+    }
+    if (lone) {
+        const float inv = 1.f / ap.kn;
+        Mxx = Myy = Mzz = inv;
+        Mxy = Mxz = Myz = 0.f;
+        f = (inv * inv) * inv;
+    }
+    mf[2 * (size_t)id] = make_float4(Mxx, Myy, Mzz, Mxy);
+    mf[2 * (size_t)id + 1] = make_float4(Mxz, Myz, f, 0.f);
+}
+
+void wsk_aniso(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, WsAnisoParams ap, float *cxyz,
+               float4 *mf, uint32_t *nb, uint32_t n)
+{
+    hipLaunchKernelGGL(k_aniso, dim3(cdiv(n, WS_BLOCK)), dim3(WS_BLOCK), 0, s, d, start, spos, ap, cxyz, mf, nb, n);
+}
+
+// the centres' records in their cell order: srec[j] = {c, id bits}, smf[2j], smf[2j + 1] = the ellipsoid of id perm[j]
+__global__ void __launch_bounds__(WS_BLOCK) k_aniso_gather(const uint32_t *__restrict__ perm, const float *__restrict__ cxyz,
+                                                           const float4 *__restrict__ mf, float4 *__restrict__ srec,
+                                                           float4 *__restrict__ smf, uint32_t n)
+{
+    const uint32_t j = blockIdx.x * WS_BLOCK + threadIdx.x;
+    if (j >= n) return;
+    const size_t id = perm[j];
+    srec[j] = make_float4(cxyz[3 * id], cxyz[3 * id + 1], cxyz[3 * id + 2], __uint_as_float((uint32_t)id));
+    smf[2 * (size_t)j] = mf[2 * id];
+    smf[2 * (size_t)j + 1] = mf[2 * id + 1];
+}
+
+void wsk_aniso_gather(hipStream_t s, const uint32_t *perm, const float *cxyz, const float4 *mf, float4 *srec, float4 *smf,
+                      uint32_t n)
+{
+    hipLaunchKernelGGL(k_aniso_gather, dim3(cdiv(n, WS_BLOCK)), dim3(WS_BLOCK), 0, s, perm, cxyz, mf, srec, smf, n);
 }
 
 // ---------------------------------------------------------------------------------

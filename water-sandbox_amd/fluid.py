@@ -50,6 +50,8 @@ ABI_SYMBOLS = [
     "ws_steps_done", "ws_kernel_name", "ws_profile_read", "ws_profile_reset", "ws_profile_select",
     "ws_grid_dims", "ws_read_stats", "ws_slab_assign", "ws_slab_create", "ws_slab_read_particles", "ws_slab_rebalance", "ws_slab_balanced_cuts",
     "ws_sample_density_grid", "ws_sample_density_points", "ws_extract_surface",
+    "ws_default_aniso_params", "ws_read_anisotropy", "ws_sample_aniso_grid", "ws_sample_aniso_points",
+    "ws_extract_aniso_surface",
 ]
 
 
@@ -68,6 +70,17 @@ class WsParams(C.Structure):
         ("gravity", C.c_float * 4),
         ("ext_min", C.c_float * 4),
         ("ext_max", C.c_float * 4),
+    ]
+
+
+class WsAnisoParams(C.Structure):
+    """ws_aniso_params: the anisotropic kernels' lambda, k_r, k_n and N_eps (include/wsfluid.h)."""
+
+    _fields_ = [
+        ("smoothing", C.c_float),
+        ("max_ratio", C.c_float),
+        ("lone_scale", C.c_float),
+        ("min_neighbours", C.c_uint32),
     ]
 
 
@@ -162,54 +175,96 @@ def bind_library(path):
     L.ws_sample_density_grid.argtypes = [vp, vp, vp, vp, vp, vp]
     L.ws_sample_density_points.argtypes = [vp, vp, u32, vp, vp]
     L.ws_extract_surface.argtypes = [vp, vp, vp, vp, C.c_float, u32, u32, vp, vp, vp, vp, vp]
+    L.ws_default_aniso_params.argtypes = [vp]
+    L.ws_read_anisotropy.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.ws_sample_aniso_grid.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.ws_sample_aniso_points.argtypes = [vp, vp, vp, u32, vp, vp]
+    L.ws_extract_aniso_surface.argtypes = [vp, vp, vp, vp, vp, C.c_float, u32, u32, vp, vp, vp, vp, vp]
     return L
 
 
-def sample_density_grid(L, h, check, origin, spacing, dims, gradient=False, want=True):
+def _aniso_args(aniso):
+    """The leading arguments an anisotropic call adds after the handle: () for the density sampler, (params,) else."""
+    return () if aniso is None else (C.byref(aniso),)
+
+
+def sample_density_grid(L, h, check, origin, spacing, dims, gradient=False, want=True, aniso=None):
     """ws_sample_density_grid: (density (nz, ny, nx), gradient (nz, ny, nx, 3) or None); dims = (nx, ny, nz).
-    want=False (slab handles): contribute to the collective call and return (None, None)."""
+    want=False (slab handles): contribute to the collective call and return (None, None).  aniso (a WsAnisoParams):
+    ws_sample_aniso_grid instead."""
+    f = L.ws_sample_density_grid if aniso is None else L.ws_sample_aniso_grid
+    a = _aniso_args(aniso)
     o = np.ascontiguousarray(origin, np.float32).reshape(3)
     sp = np.ascontiguousarray(spacing, np.float32).reshape(3)
     d = np.ascontiguousarray(dims, np.uint32).reshape(3)
     if not want:
-        check(L.ws_sample_density_grid(h, o.ctypes.data, sp.ctypes.data, d.ctypes.data, None, None))
+        check(f(h, *a, o.ctypes.data, sp.ctypes.data, d.ctypes.data, None, None))
         return None, None
     nx, ny, nz = (int(v) for v in d)
     rho = np.empty((nz, ny, nx), np.float32)
     grad = np.empty((nz, ny, nx, 3), np.float32) if gradient else None
-    check(L.ws_sample_density_grid(h, o.ctypes.data, sp.ctypes.data, d.ctypes.data, rho.ctypes.data,
-                                   grad.ctypes.data if gradient else None))
+    check(f(h, *a, o.ctypes.data, sp.ctypes.data, d.ctypes.data, rho.ctypes.data, grad.ctypes.data if gradient else None))
     return rho, grad
 
 
-def sample_density_points(L, h, check, xyz, gradient=False, want=True):
-    """ws_sample_density_points: (density (m,), gradient (m, 3) or None)."""
+def sample_density_points(L, h, check, xyz, gradient=False, want=True, aniso=None):
+    """ws_sample_density_points (aniso: ws_sample_aniso_points): (density (m,), gradient (m, 3) or None)."""
+    f = L.ws_sample_density_points if aniso is None else L.ws_sample_aniso_points
+    a = _aniso_args(aniso)
     q = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
     m = q.shape[0]
     if not want:
-        check(L.ws_sample_density_points(h, q.ctypes.data, m, None, None))
+        check(f(h, *a, q.ctypes.data, m, None, None))
         return None, None
     rho = np.empty(m, np.float32)
     grad = np.empty((m, 3), np.float32) if gradient else None
-    check(L.ws_sample_density_points(h, q.ctypes.data, m, rho.ctypes.data, grad.ctypes.data if gradient else None))
+    check(f(h, *a, q.ctypes.data, m, rho.ctypes.data, grad.ctypes.data if gradient else None))
     return rho, grad
 
 
-def extract_surface(L, h, check, origin, spacing, dims, iso, normals=True, want=True, collective=False, cap=None):
+def read_anisotropy(L, h, check, aniso, n, want=True):
+    """ws_read_anisotropy: (centre (n, 3), matrix (n, 6) xx yy zz xy xz yz, scale (n,), neighbours (n,) uint32)."""
+    if not want:
+        check(L.ws_read_anisotropy(h, C.byref(aniso), None, None, None, None))
+        return None, None, None, None
+    c = np.empty((n, 3), np.float32)
+    m = np.empty((n, 6), np.float32)
+    f = np.empty(n, np.float32)
+    nb = np.empty(n, np.uint32)
+    check(L.ws_read_anisotropy(h, C.byref(aniso), c.ctypes.data, m.ctypes.data, f.ctypes.data, nb.ctypes.data))
+    return c, m, f, nb
+
+
+def aniso_params(**kw):
+    """ws_default_aniso_params, with any field overridden by keyword (smoothing, max_ratio, lone_scale, min_neighbours)."""
+    p = WsAnisoParams()
+    load_library().ws_default_aniso_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def extract_surface(L, h, check, origin, spacing, dims, iso, normals=True, want=True, collective=False, cap=None,
+                    aniso=None):
     """ws_extract_surface: (vertices (V, 3) f32, normals (V, 3) f32 or None, triangles (T, 3) uint32).
     cap = (vertices, triangles): a first guess of the capacities, and one retry at the exact counts when it is too small.
     cap=None, and always on slab handles (collective): a counts-only call first (it samples no gradient), then one at the
-    exact counts -- every rank makes the same two calls; want=False contributes to both and returns (None, None, None)."""
+    exact counts -- every rank makes the same two calls; want=False contributes to both and returns (None, None, None).
+    aniso (a WsAnisoParams): ws_extract_aniso_surface instead."""
+    f = L.ws_extract_surface if aniso is None else L.ws_extract_aniso_surface
+    a = _aniso_args(aniso)
     o = np.ascontiguousarray(origin, np.float32).reshape(3)
     sp = np.ascontiguousarray(spacing, np.float32).reshape(3)
     d = np.ascontiguousarray(dims, np.uint32).reshape(3)
     nv, nt = C.c_uint32(0), C.c_uint32(0)
 
     def call(cap_v, cap_t, xyz=None, nrm=None, tri=None, counts=True):
-        check(L.ws_extract_surface(h, o.ctypes.data, sp.ctypes.data, d.ctypes.data, C.c_float(iso), cap_v, cap_t,
-                                   None if xyz is None else xyz.ctypes.data, None if nrm is None else nrm.ctypes.data,
-                                   None if tri is None else tri.ctypes.data, C.byref(nv) if counts else None,
-                                   C.byref(nt) if counts else None))
+        check(f(h, *a, o.ctypes.data, sp.ctypes.data, d.ctypes.data, C.c_float(iso), cap_v, cap_t,
+                None if xyz is None else xyz.ctypes.data, None if nrm is None else nrm.ctypes.data,
+                None if tri is None else tri.ctypes.data, C.byref(nv) if counts else None,
+                C.byref(nt) if counts else None))
 
     if not want:  # a slab rank that only contributes, to both calls
         call(0, 0, counts=False)
@@ -230,7 +285,7 @@ def extract_surface(L, h, check, origin, spacing, dims, iso, normals=True, want=
         if collective:
             break
         cap_v, cap_t = nv.value, nt.value
-    raise RuntimeError("ws_extract_surface: the mesh changed between two calls on the same state")
+    raise RuntimeError("%s: the mesh changed between two calls on the same state" % f.__name__)
 
 
 # ---------------------------------------------------------------------------------------
@@ -292,6 +347,7 @@ class FluidWorker:
         self._L = library if library is not None else load_library()
         self._h = C.c_void_p()
         self._surface_cap = None  # extract_surface's first guess of the capacities, from the previous mesh
+        self._aniso_cap = None  # the same for extract_aniso_surface
         positions = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
         self.n = positions.shape[0]
         self.params = params if params is not None else default_params()
@@ -431,6 +487,31 @@ class FluidWorker:
         mesh = extract_surface(self._L, self._h, self._check, origin, spacing, dims, iso, normals, cap=self._surface_cap)
         nv, nt = len(mesh[0]), len(mesh[2])
         self._surface_cap = (nv + nv // 4 + 4096, nt + nt // 4 + 8192)  # (a mesh moves little from one frame to the next)
+        return mesh
+
+    # anisotropic kernels (include/wsfluid.h ws_aniso_params): aniso=None takes the defaults, see aniso_params()
+    def anisotropy(self, aniso=None):
+        """Per particle in original-id order: (centre (n, 3), M (n, 6) as xx yy zz xy xz yz, f = det M (n,),
+        neighbour count (n,) uint32) -- the ellipsoids a splatting renderer draws."""
+        return read_anisotropy(self._L, self._h, self._check, aniso or aniso_params(), self.n)
+
+    def sample_aniso_grid(self, origin, spacing, dims, gradient=False, aniso=None):
+        """sample_density_grid of the anisotropic field."""
+        rho, grad = sample_density_grid(self._L, self._h, self._check, origin, spacing, dims, gradient,
+                                        aniso=aniso or aniso_params())
+        return (rho, grad) if gradient else rho
+
+    def sample_aniso_points(self, xyz, gradient=False, aniso=None):
+        """sample_density_points of the anisotropic field."""
+        rho, grad = sample_density_points(self._L, self._h, self._check, xyz, gradient, aniso=aniso or aniso_params())
+        return (rho, grad) if gradient else rho
+
+    def extract_aniso_surface(self, origin, spacing, dims, iso, normals=True, aniso=None):
+        """extract_surface of the anisotropic field (its own first guess of the capacities)."""
+        mesh = extract_surface(self._L, self._h, self._check, origin, spacing, dims, iso, normals, cap=self._aniso_cap,
+                               aniso=aniso or aniso_params())
+        nv, nt = len(mesh[0]), len(mesh[2])
+        self._aniso_cap = (nv + nv // 4 + 4096, nt + nt // 4 + 8192)
         return mesh
 
     def steps_done(self):

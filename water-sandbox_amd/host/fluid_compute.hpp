@@ -228,6 +228,49 @@ class FluidWorker {
         if (normals) normals->resize((size_t)nv * 3);
     }
 
+    // The anisotropic kernels (include/wsfluid.h ws_aniso_params; ws_default_aniso_params gives the defaults).  The
+    // per-particle ellipsoids in original-id order (ws_read_anisotropy): 3 floats of centre, 6 of M (xx yy zz xy xz yz),
+    // f = det M and the neighbour count per particle; any output may be null.
+    void read_anisotropy(const ws_aniso_params &a, std::vector<float> *centre, std::vector<float> *matrix,
+                         std::vector<float> *scale, std::vector<uint32_t> *neighbours)
+    {
+        const size_t n = ws_num_particles(h_);
+        if (centre) centre->resize(n * 3);
+        if (matrix) matrix->resize(n * 6);
+        if (scale) scale->resize(n);
+        if (neighbours) neighbours->resize(n);
+        check(ws_read_anisotropy(h_, &a, centre ? centre->data() : nullptr, matrix ? matrix->data() : nullptr,
+                                 scale ? scale->data() : nullptr, neighbours ? neighbours->data() : nullptr));
+    }
+    // sample_density_grid of the anisotropic field (ws_sample_aniso_grid).
+    std::vector<float> sample_aniso_grid(const ws_aniso_params &a, const Vec3 &origin, const Vec3 &spacing,
+                                         const uint32_t dims[3], std::vector<float> *gradient = nullptr)
+    {
+        const size_t nodes = (size_t)dims[0] * dims[1] * dims[2];
+        std::vector<float> out(nodes);
+        if (gradient) gradient->resize(nodes * 3);
+        check(ws_sample_aniso_grid(h_, &a, reinterpret_cast<const float *>(&origin), reinterpret_cast<const float *>(&spacing),
+                                   dims, out.data(), gradient ? gradient->data() : nullptr));
+        return out;
+    }
+    // extract_surface of the anisotropic field (ws_extract_aniso_surface): counts first, then the mesh at that size.
+    void extract_aniso_surface(const ws_aniso_params &a, const Vec3 &origin, const Vec3 &spacing, const uint32_t dims[3],
+                               float iso, std::vector<float> &xyz, std::vector<uint32_t> &tri,
+                               std::vector<float> *normals = nullptr)
+    {
+        const float *o = reinterpret_cast<const float *>(&origin), *s = reinterpret_cast<const float *>(&spacing);
+        uint32_t nv = 0, nt = 0;
+        check(ws_extract_aniso_surface(h_, &a, o, s, dims, iso, 0, 0, nullptr, nullptr, nullptr, &nv, &nt));
+        xyz.resize((size_t)nv * 3 + 1);
+        tri.resize((size_t)nt * 3 + 1);
+        if (normals) normals->resize((size_t)nv * 3 + 1);
+        check(ws_extract_aniso_surface(h_, &a, o, s, dims, iso, nv, nt, xyz.data(), normals ? normals->data() : nullptr,
+                                       tri.data(), &nv, &nt));
+        xyz.resize((size_t)nv * 3);
+        tri.resize((size_t)nt * 3);
+        if (normals) normals->resize((size_t)nv * 3);
+    }
+
     std::vector<float> read_speeds()
     {
         std::vector<float> out(n_);

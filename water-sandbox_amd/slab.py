@@ -384,6 +384,27 @@ class SlabWorker:
         return fluid.extract_surface(self._L, self._h, self._check, origin, spacing, dims, iso, normals, want,
                                      collective=True)
 
+    def anisotropy(self, aniso=None, want=True):
+        """FluidWorker.anisotropy over the GLOBAL particle set (COLLECTIVE); want=False: only contribute."""
+        return fluid.read_anisotropy(self._L, self._h, self._check, aniso or fluid.aniso_params(), self.n_global, want)
+
+    def sample_aniso_grid(self, origin, spacing, dims, gradient=False, want=True, aniso=None):
+        """FluidWorker.sample_aniso_grid over the GLOBAL particle set (COLLECTIVE); want=False: only contribute."""
+        rho, grad = fluid.sample_density_grid(self._L, self._h, self._check, origin, spacing, dims, gradient, want,
+                                              aniso=aniso or fluid.aniso_params())
+        return (rho, grad) if gradient else rho
+
+    def sample_aniso_points(self, xyz, gradient=False, want=True, aniso=None):
+        """FluidWorker.sample_aniso_points over the GLOBAL particle set (COLLECTIVE); want=False: only contribute."""
+        rho, grad = fluid.sample_density_points(self._L, self._h, self._check, xyz, gradient, want,
+                                                aniso=aniso or fluid.aniso_params())
+        return (rho, grad) if gradient else rho
+
+    def extract_aniso_surface(self, origin, spacing, dims, iso, normals=True, want=True, aniso=None):
+        """FluidWorker.extract_aniso_surface over the GLOBAL particle set (COLLECTIVE: two calls on every rank)."""
+        return fluid.extract_surface(self._L, self._h, self._check, origin, spacing, dims, iso, normals, want,
+                                     collective=True, aniso=aniso or fluid.aniso_params())
+
     def read_positions_begin(self, buf):
         assert buf.dtype == np.float32 and buf.shape == (self.n_global, 3) and buf.flags.c_contiguous
         self._check(self._L.ws_read_positions_begin(self._h, buf.ctypes.data))
