@@ -533,6 +533,61 @@ ws_status ws_extract_aniso_surface(ws_handle *h, const ws_aniso_params *a, const
                                    float *out_xyz, float *out_normal, uint32_t *out_tri, uint32_t *n_vertices,
                                    uint32_t *n_triangles);
 
+/* ---- rays at the fluid surface: first-hit distance and normal (picking, probes, depth images) ------
+ * Where does a ray enter the fluid?  A fixed-step march along the ray, a bisection of the step that crossed rho = iso and
+ * the field's gradient at the hit, all on the device: the host sends rays (or a camera) and receives one float of
+ * distance and three of normal per ray.  A pure function of the particle set, the ray and the parameters:
+ *   Field: exactly what ws_sample_density_points returns at a point -- with a non-NULL ws_aniso_params what
+ *     ws_sample_aniso_points returns: the handle's arithmetic (WS_FLAG_IEEE_DIVISION or not), the canonical summation
+ *     order, the 27 cells of the point's clamped cell.
+ *   Ray march: a ray has origin o and direction v; v is used as given (not normalised), so t is in units of |v|.
+ *     Sample parameter t_k = fl(t_start + fl((float)k * dt)) for k = 0 .. steps; sample point p_a(t) = fl(o_a + fl(t * v_a))
+ *     per axis; rho_k = the field at p(t_k).  The hit index K is the smallest k with rho_k >= iso.
+ *     No such k: a miss, out_t = +INFINITY and out_normal = (0, 0, 0).
+ *     K = 0: the ray starts inside, t = t_0, no refinement.
+ *     K >= 1: bisection from lo = t_{K-1}, hi = t_K, exactly `refine` times with no early exit: mid = fl(fl(lo + hi) *
+ *     0.5f); if rho(p(mid)) >= iso then hi = mid else lo = mid.  The result is t = hi, so the field at the reported
+ *     point p(t) is always >= iso.
+ *   Normal (sampled only when out_normal != NULL): g = the field's gradient at p(t) in the handle's arithmetic,
+ *     n = -g / sqrtf(g.g), g.g = gx*gx + gy*gy + gz*gz left to right, correctly rounded sqrt and divisions whatever the
+ *     handle's flags; (0, 0, 0) where g.g == 0 -- ws_extract_surface's rule for a vertex normal, word for word.
+ *   Camera rays (ws_cast_camera) are generated on the device: pixel (i, j) of a W x H image has
+ *     u = ((float)i + 0.5f) * (2.0f / (float)W) - 1.0f, w = 1.0f - ((float)j + 0.5f) * (2.0f / (float)H), every operation
+ *     rounded; o = eye, v_a = (forward_a + u * right_a) + w * up_a.  The host puts the field of view and the aspect ratio
+ *     into the lengths of right and up; with unit forward, and right and up perpendicular to it, out_t is the view-space
+ *     depth.  Outputs are H * W entries, x fastest (pixel (i, j) at j * W + i).  ws_cast_camera returns the bits
+ *     ws_cast_rays returns on those rays.
+ * Both calls wait for enqueued steps, write nothing ws_step reads, recompute the binning from the current positions (with
+ * params also the per-particle stage and the centres' binning) on every call and keep their scratch in the sampler's
+ * (grow-only, freed by ws_destroy).  A ray's result does not depend on the other rays of the call.  Either output may be
+ * NULL, not both on a single handle.  Slab handles: COLLECTIVE on the gathered global set, the same bits as a single
+ * handle; a rank that passes both outputs NULL only contributes, and a rank validates its query only after the gather.
+ * Errors: as ws_sample_density_points (ws_sample_aniso_points with params), plus WS_ERR_INVALID_ARG for: both outputs
+ * NULL on a single handle; NULL r; NULL
+ * origins or directions; NULL cam or size; steps outside 1 .. 65535; refine > 24; dt or iso not finite or not > 0; a
+ * non-finite t_start, origin or direction (camera: eye, forward, right, up); a direction (camera: forward) that is
+ * (0, 0, 0); any of |t_start| + steps * dt, |o_a|, |v_a| (camera: any component of the four vectors) above 1e15, which
+ * keeps every sample point finite; m == 0, a size of 0, more than 2^28 rays. */
+typedef struct ws_ray_params {
+    float t_start;   /* parameter of the first sample                                              */
+    float dt;        /* march step, > 0 (in units of |v|)                                          */
+    uint32_t steps;  /* samples k = 0 .. steps, 1 .. 65535                                         */
+    uint32_t refine; /* bisection steps of the crossing interval, 0 .. 24                          */
+    float iso;       /* the surface's level, > 0                                                   */
+} ws_ray_params;
+typedef struct ws_camera {
+    float eye[3];
+    float forward[3];
+    float right[3];
+    float up[3];
+} ws_camera;
+/* m rays: origin_xyz and dir_xyz hold m*3 floats; out_t m floats, out_normal m*3. */
+ws_status ws_cast_rays(ws_handle *h, const ws_aniso_params *a, const ws_ray_params *r, const float *origin_xyz,
+                       const float *dir_xyz, uint32_t m, float *out_t, float *out_normal);
+/* One ray per pixel of a size[0] x size[1] (W x H) image. */
+ws_status ws_cast_camera(ws_handle *h, const ws_aniso_params *a, const ws_ray_params *r, const ws_camera *cam,
+                         const uint32_t size[2], float *out_t, float *out_normal);
+
 /* ---- introspection ------------------------------------------------------------- */
 const char *ws_last_error(ws_handle *h);
 uint32_t ws_num_particles(ws_handle *h);

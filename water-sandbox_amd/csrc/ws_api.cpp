@@ -658,6 +658,9 @@ void free_field(ws_handle *h, bool all)
     F.amf = F.smf = nullptr;
     F.anb = nullptr;
     F.cxyz_bytes = F.amf_bytes = F.smf_bytes = F.anb_bytes = 0;
+    hipFree(F.rays); hipFree(F.ray_t); hipFree(F.ray_n);
+    F.rays = F.ray_t = F.ray_n = nullptr;
+    F.rays_bytes = F.ray_t_bytes = F.ray_n_bytes = 0;
 }
 
 // An allocation of the sampler: a failure is WS_ERR_OUT_OF_MEMORY and leaves no sticky HIP error behind (the next
@@ -1407,10 +1410,12 @@ ws_status field_check(ws_handle *h, const float *xyz, uint32_t m, const float *g
 // took part in the gather and has nothing more to do.  The caller has checked h and its mode.
 // ap != nullptr (checked by check()): the anisotropic field -- the per-particle stage over the binned positions (F.cxyz,
 // F.amf, F.anb by id), then the centres binned the same way (F.spos, F.smf); stage_only: stop after the stage.
+// bin_out != nullptr: stop after the binning (F.start, F.spos and with ap F.smf are what a field kernel reads) and
+// return the grid the particles were binned on -- the ray calls sample with a kernel of their own.
 template <class Check>
 ws_status field_sample_device(ws_handle *h, const float *xyz, uint32_t m, const float *grid6, const uint32_t *dims,
                               bool want, bool rho_on, bool grad_on, Check check, bool *contributed,
-                              const ws_aniso_params *ap = nullptr, bool stage_only = false)
+                              const ws_aniso_params *ap = nullptr, bool stage_only = false, WsDev *bin_out = nullptr)
 {
     *contributed = false;
     if (!h->slab && want) {
@@ -1472,6 +1477,10 @@ ws_status field_sample_device(ws_handle *h, const float *xyz, uint32_t m, const 
         wsk_view_fix(s, F.tmp, F.keys, F.start, F.perm, n);
         wsk_aniso_gather(s, F.perm, F.cxyz, F.amf, F.spos, F.smf, n);
         HIP_TRY(h, hipGetLastError());
+    }
+    if (bin_out) {
+        *bin_out = d;
+        return WS_OK;
     }
     // queries and results
     const uint64_t nq = grid6 ? (uint64_t)dims[0] * dims[1] * dims[2] : m;
@@ -1639,6 +1648,84 @@ ws_status read_anisotropy(ws_handle *h, const ws_aniso_params *ap, float *out_c,
     return WS_OK;
 }
 
+// The query of a ray call (include/wsfluid.h): the march, then the m rays of origin / dir or the camera and its size.
+ws_status ray_check(ws_handle *h, const ws_ray_params *r, bool camera, const float *origin, const float *dir, uint32_t m,
+                    const ws_camera *cam, const uint32_t *size)
+{
+    const float far = 1e15f;  // keeps every sample point finite: |t| * |v| <= 1e30
+    if (!r) return fail(h, WS_ERR_INVALID_ARG, "rays: the march parameters are required");
+    if (r->steps < 1u || r->steps > 65535u) return fail(h, WS_ERR_INVALID_ARG, "rays: steps must lie in 1 .. 65535");
+    if (r->refine > 24u) return fail(h, WS_ERR_INVALID_ARG, "rays: refine must be <= 24");
+    if (!isfinite(r->dt) || !(r->dt > 0.0f)) return fail(h, WS_ERR_INVALID_ARG, "rays: dt must be finite and > 0");
+    if (!isfinite(r->iso) || !(r->iso > 0.0f)) return fail(h, WS_ERR_INVALID_ARG, "rays: iso must be finite and > 0");
+    if (!isfinite(r->t_start)) return fail(h, WS_ERR_INVALID_ARG, "rays: t_start must be finite");
+    if (fabs((double)r->t_start) + (double)r->steps * (double)r->dt > (double)far)
+        return fail(h, WS_ERR_INVALID_ARG, "rays: |t_start| + steps * dt must be <= 1e15");
+    auto in_range = [&](const float *v, size_t k) {
+        for (size_t t = 0; t < k; t++)
+            if (!isfinite(v[t]) || fabsf(v[t]) > far) return false;
+        return true;
+    };
+    if (camera) {
+        if (!cam || !size) return fail(h, WS_ERR_INVALID_ARG, "rays: the camera and the image size are required");
+        if (size[0] == 0u || size[1] == 0u) return fail(h, WS_ERR_INVALID_ARG, "rays: the image size must be >= 1");
+        if ((uint64_t)size[0] * size[1] > (1ull << 28)) return fail(h, WS_ERR_INVALID_ARG, "rays: more than 2^28 rays");
+        if (!in_range(cam->eye, 3) || !in_range(cam->forward, 3) || !in_range(cam->right, 3) || !in_range(cam->up, 3))
+            return fail(h, WS_ERR_INVALID_ARG, "rays: the camera must be finite and within 1e15");
+        if (cam->forward[0] == 0.0f && cam->forward[1] == 0.0f && cam->forward[2] == 0.0f)
+            return fail(h, WS_ERR_INVALID_ARG, "rays: the camera's forward is (0, 0, 0)");
+        return WS_OK;
+    }
+    if (!origin || !dir || m == 0u) return fail(h, WS_ERR_INVALID_ARG, "rays: no rays");
+    if (m > (1u << 28)) return fail(h, WS_ERR_INVALID_ARG, "rays: more than 2^28 rays");
+    if (!in_range(origin, (size_t)m * 3) || !in_range(dir, (size_t)m * 3))
+        return fail(h, WS_ERR_INVALID_ARG, "rays: origins and directions must be finite and within 1e15");
+    for (size_t t = 0; t < m; t++)
+        if (dir[3 * t] == 0.0f && dir[3 * t + 1] == 0.0f && dir[3 * t + 2] == 0.0f)
+            return fail(h, WS_ERR_INVALID_ARG, "rays: a direction is (0, 0, 0)");
+    return WS_OK;
+}
+
+// ws_cast_rays / ws_cast_camera: the sampler's binning (with ap the stage and the centres' binning), the cast kernel,
+// the results copied out.
+ws_status cast_rays(ws_handle *h, const ws_aniso_params *ap, const ws_ray_params *r, bool camera, const float *origin,
+                    const float *dir, uint32_t m, const ws_camera *cam, const uint32_t *size, float *out_t, float *out_n)
+{
+    WS_DEAD_CHECK(h);
+    if (h->flags & WS_FLAG_REFERENCE_ORDER) return fail(h, WS_ERR_UNSUPPORTED, "rays: not in the reference-order validation mode");
+    const bool want = out_t || out_n;
+    if (!want && !h->slab) return fail(h, WS_ERR_INVALID_ARG, "rays: both outputs are NULL");
+    bool contributed = false;
+    auto check = [&]() -> ws_status {
+        if (ap) {
+            const ws_status st = aniso_check(h, ap);
+            if (st) return st;
+        }
+        return ray_check(h, r, camera, origin, dir, m, cam, size);
+    };
+    WsDev d;
+    ws_status st = field_sample_device(h, nullptr, 0, nullptr, nullptr, want, false, false, check, &contributed, ap, false, &d);
+    if (st || contributed) return st;
+    hipStream_t s = h->stream;
+    auto &F = h->field;
+    const size_t nr = camera ? (size_t)size[0] * size[1] : m;
+    if (out_t && (st = field_grow(h, &F.ray_t, &F.ray_t_bytes, nr * 4))) return st;
+    if (out_n && (st = field_grow(h, &F.ray_n, &F.ray_n_bytes, nr * 12))) return st;
+    if (!camera) {
+        if ((st = field_grow(h, &F.rays, &F.rays_bytes, nr * 24))) return st;
+        HIP_TRY(h, hipMemcpyAsync(F.rays, origin, nr * 12, hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(F.rays + 3 * nr, dir, nr * 12, hipMemcpyHostToDevice, s));
+    }
+    wsk_ray_cast(s, d, F.start, F.spos, ap ? F.smf : nullptr, h->ieee, *r, F.rays, camera ? nullptr : F.rays + 3 * nr,
+                 (uint32_t)nr, camera ? cam : nullptr, size, out_t ? F.ray_t : nullptr, out_n ? F.ray_n : nullptr);
+    HIP_TRY(h, hipGetLastError());
+    if (out_t) HIP_TRY(h, hipMemcpyAsync(out_t, F.ray_t, nr * 4, hipMemcpyDeviceToHost, s));
+    if (out_n) HIP_TRY(h, hipMemcpyAsync(out_n, F.ray_n, nr * 12, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    drain_profile(h);
+    return WS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1748,6 +1835,23 @@ ws_status ws_extract_aniso_surface(ws_handle *h, const ws_aniso_params *a, const
     }
     return extract_surface(h, query, g6, query ? dims : two, iso, max_vertices, max_triangles, out_xyz, out_normal,
                            out_tri, n_vertices, n_triangles, true, a);
+}
+
+// ======================================================================================
+// rays at the fluid surface (include/wsfluid.h defines the march, the hit and the normal)
+// ======================================================================================
+ws_status ws_cast_rays(ws_handle *h, const ws_aniso_params *a, const ws_ray_params *r, const float *origin_xyz,
+                       const float *dir_xyz, uint32_t m, float *out_t, float *out_normal)
+{
+    if (!h) return WS_ERR_INVALID_ARG;
+    return cast_rays(h, a, r, false, origin_xyz, dir_xyz, m, nullptr, nullptr, out_t, out_normal);
+}
+
+ws_status ws_cast_camera(ws_handle *h, const ws_aniso_params *a, const ws_ray_params *r, const ws_camera *cam,
+                         const uint32_t size[2], float *out_t, float *out_normal)
+{
+    if (!h) return WS_ERR_INVALID_ARG;
+    return cast_rays(h, a, r, true, nullptr, nullptr, 0, cam, size, out_t, out_normal);
 }
 
 // ======================================================================================

@@ -254,6 +254,10 @@ struct ws_handle {
         float4 *amf = nullptr, *smf = nullptr;
         uint32_t *anb = nullptr;
         size_t cxyz_bytes = 0, amf_bytes = 0, smf_bytes = 0, anb_bytes = 0;
+        // rays (ws_cast_rays / ws_cast_camera), grow-only: the rays of a list call (origins, then directions: 24 B per
+        // ray) and the results (4 B + 12 B per ray)
+        float *rays = nullptr, *ray_t = nullptr, *ray_n = nullptr;
+        size_t rays_bytes = 0, ray_t_bytes = 0, ray_n_bytes = 0;
     } field;
 
     // profiling
@@ -436,6 +440,11 @@ void wsk_aniso(hipStream_t s, const WsDev &d, const uint32_t *start, const float
                float4 *mf, uint32_t *nb, uint32_t n);
 void wsk_aniso_gather(hipStream_t s, const uint32_t *perm, const float *cxyz, const float4 *mf, float4 *srec, float4 *smf,
                       uint32_t n);
+// rays (ws_cast_rays / ws_cast_camera): one lane per ray -- the m rays of origin / dir, or with cam the pixels of a
+// size[0] x size[1] image.  spos / smf as wsk_field_sample; out_t or out_n may be nullptr.
+void wsk_ray_cast(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, const float4 *smf,
+                  bool ieee, const ws_ray_params &r, const float *origin, const float *dir, uint32_t m,
+                  const ws_camera *cam, const uint32_t *size, float *out_t, float *out_n);
 // surface extraction (ws_extract_surface) on a sampled grid: node codes and per-workgroup totals (wsk_iso_blocks() of
 // them, then one 0 each), then -- after two wsk_scan launches over blocks + 1 totals -- vertices and triangles
 uint32_t wsk_iso_blocks(const uint32_t *dims);

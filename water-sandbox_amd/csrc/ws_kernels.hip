@@ -2950,6 +2950,160 @@ void wsk_field_sample(hipStream_t s, const WsDev &d, const uint32_t *start, cons
 }
 
 // ---------------------------------------------------------------------------------
+// rays at the fluid surface (ws_cast_rays / ws_cast_camera; never inside ws_step)
+//
+// include/wsfluid.h pins the march bit for bit: samples t_k = t_start + k * dt at p = o + t * v, the first k with
+// field >= iso, `refine` bisections of [t_{k-1}, t_k], the gradient at the hit.  The field at a sample is field_sweep,
+// the points sampler's own definition, so a host that marches with ws_sample_density_points gets the same bits.
+//
+// k_ray_cast, one lane per ray: a plain loop that calls field_sweep at every march and bisection sample, then once more
+// at the hit for the gradient.  A lane's state is its own: no result depends on what the other lanes of the wave do.
+// (An occupancy bit per cell that skips air samples exactly, with a wave vote so that lanes sweep together, is
+// tools/ab/patches/rays_occupancy_vote.patch: not measured against this loop, so not adopted.)
+// ---------------------------------------------------------------------------------
+// The ray of a lane: its origin, direction and output slot; false = the lane has no ray.
+// RayList: the m rays of a ws_cast_rays call, ray t on lane t.
+struct RayList {
+    const float *__restrict__ o;
+    const float *__restrict__ v;
+    uint32_t m;
+    __device__ __forceinline__ bool ray(uint32_t t, size_t &at, float4 &org, float4 &dir) const
+    {
+        if (t >= m) return false;
+        at = t;
+        org = make_float4(o[3 * at], o[3 * at + 1], o[3 * at + 2], 0.f);
+        dir = make_float4(v[3 * at], v[3 * at + 1], v[3 * at + 2], 0.f);
+        return true;
+    }
+};
+
+// RayCamera: pixel (i, j) of a W x H image (include/wsfluid.h has the formula; su = 2 / W and sv = 2 / H are rounded on
+// the host).  A wave is a tile of 8 x 8 pixels, lane l = pixel (l & 7, l >> 3) of it: neighbouring rays walk
+// neighbouring cells, so their candidate runs overlap in L1.
+struct RayCamera {
+    ws_camera cam;
+    uint32_t w, h, tiles_x;
+    float su, sv;
+    __device__ __forceinline__ bool ray(uint32_t t, size_t &at, float4 &org, float4 &dir) const
+    {
+        const uint32_t tile = t >> 6, lane = t & 63u;
+        const uint32_t i = (tile % tiles_x) * 8u + (lane & 7u), j = (tile / tiles_x) * 8u + (lane >> 3);
+        if (i >= w || j >= h) return false;
+        at = (size_t)j * w + i;
+        const float u = ((float)i + 0.5f) * su - 1.0f;
+        const float q = 1.0f - ((float)j + 0.5f) * sv;
+        org = make_float4(cam.eye[0], cam.eye[1], cam.eye[2], 0.f);
+        dir = make_float4((cam.forward[0] + u * cam.right[0]) + q * cam.up[0], (cam.forward[1] + u * cam.right[1]) + q * cam.up[1],
+                          (cam.forward[2] + u * cam.right[2]) + q * cam.up[2], 0.f);
+        return true;
+    }
+};
+
+// Where a ray stands: marching at sample k (left == 0) or `left` bisections from the end, between lo and hi.
+struct RayState {
+    uint32_t k, left;
+    float lo, hi, t;  // t: the result (+INFINITY until a hit is final)
+    bool done;
+    // parameter of the next sample
+    __device__ __forceinline__ float next(const ws_ray_params &r) const
+    {
+        return left ? (lo + hi) * 0.5f : r.t_start + (float)k * r.dt;
+    }
+    // the field at that sample is rho
+    __device__ __forceinline__ void take(const ws_ray_params &r, float ts, float rho)
+    {
+        const bool inside = rho >= r.iso;
+        if (left) {
+            if (inside) hi = ts;
+            else lo = ts;
+            if (--left == 0u) {
+                t = hi;
+                done = true;
+            }
+        } else if (inside) {
+            if (k == 0u || r.refine == 0u) {
+                t = ts;
+                done = true;
+            } else {
+                lo = r.t_start + (float)(k - 1u) * r.dt;
+                hi = ts;
+                left = r.refine;
+            }
+        } else if (++k > r.steps) {
+            done = true;  // a miss
+        }
+    }
+};
+
+__device__ __forceinline__ float4 ray_point(const float4 &o, const float4 &v, float t)
+{
+    return make_float4(o.x + t * v.x, o.y + t * v.y, o.z + t * v.z, 0.f);
+}
+
+template <bool IEEE, bool NORMALS, class Src, class Rays>
+__global__ void __launch_bounds__(WS_BLOCK) k_ray_cast(WsDev d, const uint32_t *__restrict__ start, Src src,
+                                                       Rays rays, ws_ray_params r,
+                                                       float *__restrict__ out_t, float *__restrict__ out_n)
+{
+    size_t at = 0;
+    float4 o = make_float4(0.f, 0.f, 0.f, 0.f), v = o;
+    const bool valid = rays.ray(blockIdx.x * WS_BLOCK + threadIdx.x, at, o, v);
+    RayState st = {0u, 0u, 0.f, 0.f, INFINITY, !valid};
+    while (!st.done) {
+        const float ts = st.next(r);
+        st.take(r, ts, field_sweep<IEEE, false>(d, start, src, ray_point(o, v, ts)).rho);
+    }
+    const bool hit = valid && st.t != INFINITY;
+    if constexpr (NORMALS) {
+        float nx = 0.f, ny = 0.f, nz = 0.f;
+        if (hit) {
+            const FieldAcc g = field_sweep<IEEE, true>(d, start, src, ray_point(o, v, st.t));
+            const float gg = g.gx * g.gx + g.gy * g.gy + g.gz * g.gz;
+            if (gg != 0.f) {
+                const float len = sqrtf(gg);
+                nx = -g.gx / len;
+                ny = -g.gy / len;
+                nz = -g.gz / len;
+            }
+        }
+        if (valid) {
+            out_n[3 * at] = nx;
+            out_n[3 * at + 1] = ny;
+            out_n[3 * at + 2] = nz;
+        }
+    }
+    if (valid && out_t) out_t[at] = st.t;
+}
+
+template <class Src, class Rays>
+void ray_cast_launch(hipStream_t s, const WsDev &d, const uint32_t *start, Src src, Rays rays,
+                     uint32_t lanes, const ws_ray_params &r, bool ieee, float *out_t, float *out_n)
+{
+    const dim3 grid(cdiv(lanes, WS_BLOCK));
+#define RC_LAUNCH(I, N) \
+    hipLaunchKernelGGL((k_ray_cast<I, N, Src, Rays>), grid, dim3(WS_BLOCK), 0, s, d, start, src, rays, r, out_t, out_n)
+    if (ieee) { if (out_n) RC_LAUNCH(true, true); else RC_LAUNCH(true, false); }
+    else { if (out_n) RC_LAUNCH(false, true); else RC_LAUNCH(false, false); }
+#undef RC_LAUNCH
+}
+
+void wsk_ray_cast(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, const float4 *smf,
+                  bool ieee, const ws_ray_params &r, const float *origin, const float *dir, uint32_t m,
+                  const ws_camera *cam, const uint32_t *size, float *out_t, float *out_n)
+{
+    if (cam) {
+        const uint32_t tx = cdiv(size[0], 8u), ty = cdiv(size[1], 8u);
+        const RayCamera rays = {*cam, size[0], size[1], tx, 2.0f / (float)size[0], 2.0f / (float)size[1]};
+        if (smf) ray_cast_launch(s, d, start, FieldAniso{spos, smf}, rays, tx * ty * 64u, r, ieee, out_t, out_n);
+        else ray_cast_launch(s, d, start, FieldIso{spos}, rays, tx * ty * 64u, r, ieee, out_t, out_n);
+    } else {
+        const RayList rays = {origin, dir, m};
+        if (smf) ray_cast_launch(s, d, start, FieldAniso{spos, smf}, rays, m, r, ieee, out_t, out_n);
+        else ray_cast_launch(s, d, start, FieldIso{spos}, rays, m, r, ieee, out_t, out_n);
+    }
+}
+
+// ---------------------------------------------------------------------------------
 // anisotropic kernels (ws_read_anisotropy / ws_sample_aniso_* / ws_extract_aniso_surface; never inside ws_step)
 //
 // k_aniso, the per-particle stage (include/wsfluid.h pins it bit for bit): one lane per particle in the sampler's cell

@@ -51,7 +51,7 @@ ABI_SYMBOLS = [
     "ws_grid_dims", "ws_read_stats", "ws_slab_assign", "ws_slab_create", "ws_slab_read_particles", "ws_slab_rebalance", "ws_slab_balanced_cuts",
     "ws_sample_density_grid", "ws_sample_density_points", "ws_extract_surface",
     "ws_default_aniso_params", "ws_read_anisotropy", "ws_sample_aniso_grid", "ws_sample_aniso_points",
-    "ws_extract_aniso_surface",
+    "ws_extract_aniso_surface", "ws_cast_rays", "ws_cast_camera",
 ]
 
 
@@ -81,6 +81,29 @@ class WsAnisoParams(C.Structure):
         ("max_ratio", C.c_float),
         ("lone_scale", C.c_float),
         ("min_neighbours", C.c_uint32),
+    ]
+
+
+class WsRayParams(C.Structure):
+    """ws_ray_params: the march of ws_cast_rays / ws_cast_camera (include/wsfluid.h)."""
+
+    _fields_ = [
+        ("t_start", C.c_float),
+        ("dt", C.c_float),
+        ("steps", C.c_uint32),
+        ("refine", C.c_uint32),
+        ("iso", C.c_float),
+    ]
+
+
+class WsCamera(C.Structure):
+    """ws_camera: pixel (i, j) looks along forward + u * right + w * up from eye (include/wsfluid.h)."""
+
+    _fields_ = [
+        ("eye", C.c_float * 3),
+        ("forward", C.c_float * 3),
+        ("right", C.c_float * 3),
+        ("up", C.c_float * 3),
     ]
 
 
@@ -180,6 +203,8 @@ def bind_library(path):
     L.ws_sample_aniso_grid.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.ws_sample_aniso_points.argtypes = [vp, vp, vp, u32, vp, vp]
     L.ws_extract_aniso_surface.argtypes = [vp, vp, vp, vp, vp, C.c_float, u32, u32, vp, vp, vp, vp, vp]
+    L.ws_cast_rays.argtypes = [vp, vp, vp, vp, vp, u32, vp, vp]
+    L.ws_cast_camera.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     return L
 
 
@@ -244,6 +269,49 @@ def aniso_params(**kw):
             raise AttributeError(k)
         setattr(p, k, v)
     return p
+
+
+def ray_params(t_start, dt, steps, refine, iso):
+    return WsRayParams(float(t_start), float(dt), int(steps), int(refine), float(iso))
+
+
+def camera(eye, forward, right, up):
+    cam = WsCamera()
+    for name, v in (("eye", eye), ("forward", forward), ("right", right), ("up", up)):
+        for k in range(3):
+            getattr(cam, name)[k] = float(v[k])
+    return cam
+
+
+def cast_rays(L, h, check, march, origins, directions, normals=True, want=True, aniso=None):
+    """ws_cast_rays: (t (m,) float32, +inf on a miss; normal (m, 3) float32 or None).  march: a WsRayParams; aniso=None:
+    the density field, else a WsAnisoParams.  want=False (slab handles): contribute and return (None, None)."""
+    o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+    v = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
+    assert o.shape == v.shape
+    m = o.shape[0]
+    a = None if aniso is None else C.byref(aniso)
+    if not want:
+        check(L.ws_cast_rays(h, a, C.byref(march), o.ctypes.data, v.ctypes.data, m, None, None))
+        return None, None
+    t = np.empty(m, np.float32)
+    n = np.empty((m, 3), np.float32) if normals else None
+    check(L.ws_cast_rays(h, a, C.byref(march), o.ctypes.data, v.ctypes.data, m, t.ctypes.data, n.ctypes.data if normals else None))
+    return t, n
+
+
+def cast_camera(L, h, check, march, cam, size, normals=True, want=True, aniso=None):
+    """ws_cast_camera: (t (H, W) float32, normal (H, W, 3) float32 or None) of a size = (W, H) image; cam: a WsCamera."""
+    sz = np.ascontiguousarray(size, np.uint32).reshape(2)
+    a = None if aniso is None else C.byref(aniso)
+    if not want:
+        check(L.ws_cast_camera(h, a, C.byref(march), C.byref(cam), sz.ctypes.data, None, None))
+        return None, None
+    wd, ht = int(sz[0]), int(sz[1])
+    t = np.empty((ht, wd), np.float32)
+    n = np.empty((ht, wd, 3), np.float32) if normals else None
+    check(L.ws_cast_camera(h, a, C.byref(march), C.byref(cam), sz.ctypes.data, t.ctypes.data, n.ctypes.data if normals else None))
+    return t, n
 
 
 def extract_surface(L, h, check, origin, spacing, dims, iso, normals=True, want=True, collective=False, cap=None,
@@ -513,6 +581,17 @@ class FluidWorker:
         nv, nt = len(mesh[0]), len(mesh[2])
         self._aniso_cap = (nv + nv // 4 + 4096, nt + nt // 4 + 8192)
         return mesh
+
+    def cast_rays(self, march, origins, directions, normals=True, aniso=None):
+        """Where each ray origin + t * direction first meets the surface field = march.iso: (t (m,), +inf on a miss;
+        unit normal (m, 3) or None).  march = ray_params(t_start, dt, steps, refine, iso); aniso=None casts at the density
+        field, a WsAnisoParams at the anisotropic one (include/wsfluid.h ws_cast_rays has the definition)."""
+        return cast_rays(self._L, self._h, self._check, march, origins, directions, normals, aniso=aniso)
+
+    def cast_camera(self, march, cam, size, normals=True, aniso=None):
+        """The same for one ray per pixel of a size = (W, H) image seen by cam = camera(eye, forward, right, up):
+        (t (H, W), normal (H, W, 3) or None)."""
+        return cast_camera(self._L, self._h, self._check, march, cam, size, normals, aniso=aniso)
 
     def steps_done(self):
         return int(self._L.ws_steps_done(self._h))

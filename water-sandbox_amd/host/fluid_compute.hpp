@@ -271,6 +271,31 @@ class FluidWorker {
         if (normals) normals->resize((size_t)nv * 3);
     }
 
+    // Where rays first meet the surface field = r.iso (ws_cast_rays; include/wsfluid.h has the march): one hit parameter
+    // per ray, +INFINITY on a miss; with a normals vector, 3 floats per ray.  origins / directions: one Vec3 per ray
+    // (directions are not normalised: t is in units of their length).  a = nullptr: the density field.
+    std::vector<float> cast_rays(const ws_ray_params &r, const std::vector<Vec3> &origins, const std::vector<Vec3> &directions,
+                                 std::vector<float> *normals = nullptr, const ws_aniso_params *a = nullptr)
+    {
+        if (origins.size() != directions.size()) throw std::runtime_error("cast_rays: one direction per origin");
+        std::vector<float> t(origins.size());
+        if (normals) normals->resize(origins.size() * 3);
+        check(ws_cast_rays(h_, a, &r, reinterpret_cast<const float *>(origins.data()),
+                           reinterpret_cast<const float *>(directions.data()), (uint32_t)origins.size(), t.data(),
+                           normals ? normals->data() : nullptr));
+        return t;
+    }
+    // The same for one ray per pixel of a width x height image (ws_cast_camera), x fastest.
+    std::vector<float> cast_camera(const ws_ray_params &r, const ws_camera &cam, uint32_t width, uint32_t height,
+                                   std::vector<float> *normals = nullptr, const ws_aniso_params *a = nullptr)
+    {
+        const uint32_t size[2] = {width, height};
+        std::vector<float> t((size_t)width * height);
+        if (normals) normals->resize(t.size() * 3);
+        check(ws_cast_camera(h_, a, &r, &cam, size, t.data(), normals ? normals->data() : nullptr));
+        return t;
+    }
+
     std::vector<float> read_speeds()
     {
         std::vector<float> out(n_);

@@ -405,6 +405,14 @@ class SlabWorker:
         return fluid.extract_surface(self._L, self._h, self._check, origin, spacing, dims, iso, normals, want,
                                      collective=True, aniso=aniso or fluid.aniso_params())
 
+    def cast_rays(self, march, origins, directions, normals=True, want=True, aniso=None):
+        """FluidWorker.cast_rays over the GLOBAL particle set (COLLECTIVE); want=False: only contribute (None, None)."""
+        return fluid.cast_rays(self._L, self._h, self._check, march, origins, directions, normals, want, aniso)
+
+    def cast_camera(self, march, cam, size, normals=True, want=True, aniso=None):
+        """FluidWorker.cast_camera over the GLOBAL particle set (COLLECTIVE); want=False: only contribute (None, None)."""
+        return fluid.cast_camera(self._L, self._h, self._check, march, cam, size, normals, want, aniso)
+
     def read_positions_begin(self, buf):
         assert buf.dtype == np.float32 and buf.shape == (self.n_global, 3) and buf.flags.c_contiguous
         self._check(self._L.ws_read_positions_begin(self._h, buf.ctypes.data))
