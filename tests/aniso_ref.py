@@ -12,6 +12,7 @@ from f64_step import U, accept
 F32 = np.float32
 GRID_PAD = 2  # empty cell layers around the container (the library's grid)
 CHUNK = 4096  # queries per numpy chunk
+CHUNK_MERGED = 256  # ... on a grid of merged cells, whose columns are many times longer
 
 
 def defaults():
@@ -24,24 +25,48 @@ def isotropic_limit():
 
 
 class Grid:
-    """The handle's cell grid (reference-sized cells over the container padded by GRID_PAD; no merged cells)."""
+    """The handle's cell grid: reference-sized cells (edge h) over the container padded by GRID_PAD, `merged` = (mx, my,
+    mz) of them per grid cell along each axis (stats()["cells_merged"] of the handle; the factors are the library's
+    choice and are not re-derived here).  fdim counts the reference-sized cells, dim = ceil(fdim / merged) the grid's."""
 
-    def __init__(self, params):
+    def __init__(self, params, merged=(1, 1, 1)):
         self.h = F32(params.smoothing_radius)
         mn = np.asarray(params.ext_min[:3], F32)
         mx = np.asarray(params.ext_max[:3], F32)
         self.org = np.floor(mn / self.h).astype(np.int64) - GRID_PAD
-        self.dim = np.floor(mx / self.h).astype(np.int64) + GRID_PAD - self.org + 1
-        assert np.prod(self.dim) <= max(1 << 24, 16 * 4096), "merged cells are not restated"
+        self.fdim = np.floor(mx / self.h).astype(np.int64) + GRID_PAD - self.org + 1
+        self.merged = np.asarray([int(m) for m in merged], np.int64)
+        assert self.merged.shape == (3,) and np.all(self.merged >= 1)
+        self.dim = -(-self.fdim // self.merged)
+        if np.all(self.merged == 1):
+            assert np.prod(self.dim) <= max(1 << 24, 16 * 4096), "the library merges cells here: pass its cells_merged"
+        else:  # (the restated table has one entry per merged cell)
+            assert np.prod(self.dim) <= 1 << 24, "the merged grid's table is too large to restate"
         self.d2_accept = accept(self.h)
 
     def cells(self, x):
-        """(n, 3) int64 cell coordinates: floorf(x / h) - org, clamped to the grid."""
+        """(n, 3) int64 cell coordinates: floorf(x / h) - org, clamped to the reference-sized grid, over the merge
+        factor (grid_cell / field_axis_cell)."""
         c = np.floor(np.asarray(x, F32) / self.h).astype(np.int64) - self.org
-        return np.clip(c, 0, self.dim - 1)
+        return np.clip(c, 0, self.fdim - 1) // self.merged
 
     def linear(self, c):
         return (c[:, 0] * self.dim[1] + c[:, 1]) * self.dim[2] + c[:, 2]
+
+    def chunk(self):
+        return CHUNK if np.all(self.merged == 1) else CHUNK_MERGED
+
+
+def _front(acc):
+    """Column indices (m, max count) that bring the accepted candidates of every row to the front in their order.
+    A rejected candidate adds nothing to a sum, so summing the accepted ones alone in this order is the same sequence
+    of float32 additions as walking all the columns."""
+    kmax = int(acc.sum(1).max()) if acc.size else 0
+    return np.argsort(~acc, axis=1, kind="stable")[:, :kmax]
+
+
+def _take(a, keep):
+    return np.take_along_axis(a, keep, 1)
 
 
 class Binned:
@@ -116,42 +141,38 @@ def jacobi(a, iterations=5):
     return np.stack(a[:3], 1), R
 
 
-def stage(params, x, aniso):
+def stage(params, x, aniso, merged=(1, 1, 1), ids=None):
     """The stage of the header for the float32 positions x (n, 3) by id: (centre (n, 3), M (n, 6), f (n,),
-    neighbours (n,) uint32), each float32 bit for bit."""
+    neighbours (n,) uint32), each float32 bit for bit.  With ids, the rows of those particles alone."""
     x = np.ascontiguousarray(x, F32).reshape(-1, 3)
     lam, kr, kn = F32(aniso["smoothing"]), F32(aniso["max_ratio"]), F32(aniso["lone_scale"])
     neps = int(aniso["min_neighbours"])
-    grid = Grid(params)
+    grid = Grid(params, merged)
     bins = Binned(grid, x)
-    n = len(x)
+    sel = np.arange(len(x)) if ids is None else np.asarray(ids, np.int64)
+    n = len(sel)
     cen = np.empty((n, 3), F32)
     mat = np.empty((n, 6), F32)
     det = np.empty(n, F32)
     cnt = np.empty(n, np.uint32)
-    for s0 in range(0, n, CHUNK):
-        ids = np.arange(s0, min(n, s0 + CHUNK))
-        xi = x[ids]
-        cols = bins.columns(xi)
-        valid = cols >= 0
-        xj = x[bins.order[np.where(valid, cols, 0)]]
-        e = (xj - xi[:, None, :]).astype(F32)
-        d2 = ((e[..., 0] * e[..., 0] + e[..., 1] * e[..., 1]) + e[..., 2] * e[..., 2]).astype(F32)
-        acc = valid & ~(d2 > grid.d2_accept)
+    for s0 in range(0, n, grid.chunk()):
+        rows = np.arange(s0, min(n, s0 + grid.chunk()))  # (rows of the outputs)
+        xi = x[sel[rows]]
+        _, acc, e, d2 = _near(grid, bins, x, xi)
         r = (np.sqrt(d2) / grid.h).astype(F32)
         w = (F32(1) - (r * r) * r).astype(F32)
         we = (w[..., None] * e).astype(F32)
         terms = [w, we[..., 0], we[..., 1], we[..., 2], we[..., 0] * e[..., 0], we[..., 1] * e[..., 1],
                  we[..., 2] * e[..., 2], we[..., 0] * e[..., 1], we[..., 0] * e[..., 2], we[..., 1] * e[..., 2]]
-        sums = [np.zeros(len(ids), F32) for _ in terms]
-        for k in range(cols.shape[1]):
+        sums = [np.zeros(len(rows), F32) for _ in terms]
+        for k in range(acc.shape[1]):
             a = acc[:, k]
             for t, sm in zip(terms, sums):
                 sm[...] = np.where(a, sm + t[:, k].astype(F32), sm)
         W, sx, sy, sz, qxx, qyy, qzz, qxy, qxz, qyz = sums
         nb = acc.sum(1).astype(np.uint32)
         mx, my, mz = sx / W, sy / W, sz / W
-        cen[ids] = np.stack([xi[:, 0] + lam * mx, xi[:, 1] + lam * my, xi[:, 2] + lam * mz], 1).astype(F32)
+        cen[rows] = np.stack([xi[:, 0] + lam * mx, xi[:, 1] + lam * my, xi[:, 2] + lam * mz], 1).astype(F32)
         cov = np.stack([qxx / W - mx * mx, qyy / W - my * my, qzz / W - mz * mz,
                         qxy / W - mx * my, qxz / W - mx * mz, qyz / W - my * mz], 1).astype(F32)
         sig, R = jacobi(cov)
@@ -161,16 +182,16 @@ def stage(params, x, aniso):
             fl = (smax / kr).astype(F32)
             s = (np.fmax(sig, fl[:, None]) / smax[:, None]).astype(F32)
             inv_s = (F32(1) / s).astype(F32)
-            M = np.zeros((len(ids), 6), F32)
+            M = np.zeros((len(rows), 6), F32)
             for col, (p, q) in enumerate(((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2))):
                 for k in range(3):
                     M[:, col] = M[:, col] + (inv_s[:, k] * R[:, p, k]) * R[:, q, k]
             f = (F32(1) / ((s[:, 0] * s[:, 1]) * s[:, 2])).astype(F32)
         inv = F32(F32(1) / kn)
         lone_m = np.array([inv, inv, inv, 0, 0, 0], F32)
-        mat[ids] = np.where(lone[:, None], lone_m[None, :], M)
-        det[ids] = np.where(lone, F32((inv * inv) * inv), f)
-        cnt[ids] = nb
+        mat[rows] = np.where(lone[:, None], lone_m[None, :], M)
+        det[rows] = np.where(lone, F32((inv * inv) * inv), f)
+        cnt[rows] = nb
     return cen, mat, det, cnt
 
 
@@ -183,32 +204,28 @@ def _kernel(params):
     return F32(params.smoothing_radius), F32(k.pow2), F32(k.pow2_der)
 
 
-def _candidates(params, cen, q):
-    grid = Grid(params)
+def _candidates(params, cen, q, merged=(1, 1, 1)):
+    grid = Grid(params, merged)
     bins = Binned(grid, cen)
     return grid, bins
 
 
-def field32(params, cen, mat, det, q, gradient=True):
+def field32(params, cen, mat, det, q, gradient=True, merged=(1, 1, 1)):
     """The field of the header at the points q (m, 3), float32 with correctly rounded sqrt and division (the library's
     WS_FLAG_IEEE_DIVISION form, bit for bit): (rho (m,), grad (m, 3) or None)."""
     h, p2, p2d = _kernel(params)
     cen = np.ascontiguousarray(cen, F32)
     q = np.ascontiguousarray(q, F32).reshape(-1, 3)
-    grid, bins = _candidates(params, cen, q)
+    grid, bins = _candidates(params, cen, q, merged)
     rho = np.zeros(len(q), F32)
     grad = np.zeros((len(q), 3), F32)
-    for s0 in range(0, len(q), CHUNK):
-        sl = slice(s0, min(len(q), s0 + CHUNK))
-        cols = bins.columns(q[sl])
-        valid = cols >= 0
-        j = bins.order[np.where(valid, cols, 0)]
-        e = (cen[j] - q[sl][:, None, :]).astype(F32)
-        d2 = ((e[..., 0] * e[..., 0] + e[..., 1] * e[..., 1]) + e[..., 2] * e[..., 2]).astype(F32)
+    for s0 in range(0, len(q), grid.chunk()):
+        sl = slice(s0, min(len(q), s0 + grid.chunk()))
+        j, near, e, d2 = _near(grid, bins, cen, q[sl])
         M = mat[j]
         u = _mul(M, e)
         dm2 = ((u[..., 0] * u[..., 0] + u[..., 1] * u[..., 1]) + u[..., 2] * u[..., 2]).astype(F32)
-        acc = valid & ~(d2 > grid.d2_accept) & ~(dm2 > grid.d2_accept)
+        acc = near & ~(dm2 > grid.d2_accept)
         dst = np.sqrt(dm2).astype(F32)
         f = det[j]
         v = (h - dst).astype(F32)
@@ -219,13 +236,30 @@ def field32(params, cen, mat, det, q, gradient=True):
             tg = (((-vv / dst[..., None]) * slope[..., None]) * f[..., None]).astype(F32)
         apart = dst > 0
         r, g = rho[sl].copy(), grad[sl].copy()
-        for k in range(cols.shape[1]):
+        for k in range(acc.shape[1]):
             a = acc[:, k]
             r = np.where(a, r + tr[:, k], r)
             if gradient:
                 g = np.where(a[:, None], g + np.where(apart[:, k, None], tg[:, k], F32(0)), g)
         rho[sl], grad[sl] = r, g
     return rho, (grad if gradient else None)
+
+
+def _near(grid, bins, cen, q):
+    """The candidates of the queries q that pass the distance test, in canonical order and brought to the front:
+    (particle ids (m, k), passed (m, k) bool, e = centre - q (m, k, 3) and |e|^2 (m, k) in float32)."""
+    cols = bins.columns(q)
+    valid = cols >= 0
+    j = bins.order[np.where(valid, cols, 0)]
+
+    def offsets(j):
+        e = (cen[j] - q[:, None, :]).astype(F32)
+        return e, ((e[..., 0] * e[..., 0] + e[..., 1] * e[..., 1]) + e[..., 2] * e[..., 2]).astype(F32)
+
+    near = valid & ~(offsets(j)[1] > grid.d2_accept)
+    keep = _front(near)
+    j = _take(j, keep)
+    return (j, _take(near, keep)) + offsets(j)
 
 
 def _mul(M, e):
@@ -236,30 +270,26 @@ def _mul(M, e):
                     -1).astype(F32)
 
 
-def iso_field32(params, x, q):
+def iso_field32(params, x, q, merged=(1, 1, 1)):
     """The density sampler's field (ws_sample_density_points, IEEE form) at q, float32: the isotropic reference."""
     h, p2, _ = _kernel(params)
     x = np.ascontiguousarray(x, F32)
     q = np.ascontiguousarray(q, F32).reshape(-1, 3)
-    grid, bins = _candidates(params, x, q)
+    grid, bins = _candidates(params, x, q, merged)
     rho = np.zeros(len(q), F32)
-    for s0 in range(0, len(q), CHUNK):
-        sl = slice(s0, min(len(q), s0 + CHUNK))
-        cols = bins.columns(q[sl])
-        valid = cols >= 0
-        e = (x[bins.order[np.where(valid, cols, 0)]] - q[sl][:, None, :]).astype(F32)
-        d2 = ((e[..., 0] * e[..., 0] + e[..., 1] * e[..., 1]) + e[..., 2] * e[..., 2]).astype(F32)
-        acc = valid & ~(d2 > grid.d2_accept)
+    for s0 in range(0, len(q), grid.chunk()):
+        sl = slice(s0, min(len(q), s0 + grid.chunk()))
+        _, acc, _, d2 = _near(grid, bins, x, q[sl])
         v = (h - np.sqrt(d2)).astype(F32)
         t = (v * v * p2).astype(F32)
         r = rho[sl].copy()
-        for k in range(cols.shape[1]):
+        for k in range(acc.shape[1]):
             r = np.where(acc[:, k], r + t[:, k], r)
         rho[sl] = r
     return rho
 
 
-def field64(params, cen, mat, det, q, c=4.0):
+def field64(params, cen, mat, det, q, c=4.0, merged=(1, 1, 1)):
     """The field at q in float64 over the float32 stage outputs, with the float32 accept decisions, and a per-point bound
     tol = c u [(n + 8) sum |t| + sum |dt/ddM| G] per component (G = |(sum_b |M_ab| |e_b|)_a| >= dM bounds the rounding
     of dM; for the gradient the analogous terms of v / dM): (rho, grad (m, 3), tol_rho, tol_grad (m, 3), n)."""
@@ -267,22 +297,18 @@ def field64(params, cen, mat, det, q, c=4.0):
     h, p2, p2d = float(h32), float(p2_32), float(p2d_32)
     cen = np.ascontiguousarray(cen, F32)
     q = np.ascontiguousarray(q, F32).reshape(-1, 3)
-    grid, bins = _candidates(params, cen, q)
+    grid, bins = _candidates(params, cen, q, merged)
     m = len(q)
     rho, grad = np.zeros(m), np.zeros((m, 3))
     tr, tg, nn = np.zeros(m), np.zeros((m, 3)), np.zeros(m)
     sr, sg = np.zeros(m), np.zeros((m, 3))
-    for s0 in range(0, m, CHUNK):
-        sl = slice(s0, min(m, s0 + CHUNK))
-        cols = bins.columns(q[sl])
-        valid = cols >= 0
-        j = bins.order[np.where(valid, cols, 0)]
-        e32 = (cen[j] - q[sl][:, None, :]).astype(F32)
-        d2 = ((e32[..., 0] * e32[..., 0] + e32[..., 1] * e32[..., 1]) + e32[..., 2] * e32[..., 2]).astype(F32)
+    for s0 in range(0, m, grid.chunk()):
+        sl = slice(s0, min(m, s0 + grid.chunk()))
+        j, near, e32, _ = _near(grid, bins, cen, q[sl])
         M32 = mat[j]
         u32 = _mul(M32, e32)
         dm2 = ((u32[..., 0] * u32[..., 0] + u32[..., 1] * u32[..., 1]) + u32[..., 2] * u32[..., 2]).astype(F32)
-        acc = valid & ~(d2 > grid.d2_accept) & ~(dm2 > grid.d2_accept)
+        acc = near & ~(dm2 > grid.d2_accept)
         e = cen[j].astype(np.float64) - q[sl][:, None, :].astype(np.float64)
         M = M32.astype(np.float64)
         f = det[j].astype(np.float64)
@@ -333,10 +359,10 @@ def grid_nodes(origin, spacing, dims):
     return np.stack([x.reshape(-1), y.reshape(-1), z.reshape(-1)], 1).astype(F32)
 
 
-def mesh(params, cen, mat, det, origin, spacing, dims, iso):
+def mesh(params, cen, mat, det, origin, spacing, dims, iso, merged=(1, 1, 1)):
     """The anisotropic surface of the header (IEEE field form) via surface_ref.extract: (xyz, normals, triangles)."""
     nx, ny, nz = (int(v) for v in dims)
-    rho, grad = field32(params, cen, mat, det, grid_nodes(origin, spacing, dims))
+    rho, grad = field32(params, cen, mat, det, grid_nodes(origin, spacing, dims), merged=merged)
     return S.extract(rho.reshape(nz, ny, nx), grad.reshape(nz, ny, nx, 3), origin, spacing, dims, iso)
 
 

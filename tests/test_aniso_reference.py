@@ -150,3 +150,120 @@ def test_the_c1_sheet_meshes_flatter_than_the_isotropic_surface(ws):
     assert np.all(m[interior, 2] == F32(kr))  # the normal axis is shortened k_r-fold
     rms_an, rms_iso = sheet_case(params, c, m, f, kr)
     assert rms_an <= 0.5 * rms_iso, (rms_an, rms_iso)
+
+
+# ---- the restatement on merged and off-centre grids ---------------------------------------------------------------------
+POSITIONS = {"centred": (0.0, 0.0, 0.0), "off-centre": (37.3, -21.7, 5.45)}
+
+
+def _no_divisor(f, least):
+    """The smallest factor >= least that does not divide f: the last merged cell is narrower than the others."""
+    return next(m for m in range(least, int(f)) if f % m)
+
+
+# merge factors per axis as functions of the reference-sized dims fdim (36 x 28 x 28 for the centred container)
+MERGES = {"z": lambda f: (1, 1, 4), "zy": lambda f: (1, 5, 9), "zyx": lambda f: (3, 5, 9),
+          "one-layer-x": lambda f: (int(f[0]), 9, 9),
+          "ragged": lambda f: (_no_divisor(f[0], 5), _no_divisor(f[1], 3), _no_divisor(f[2], 2))}
+
+
+def _grid_scene(ws, where, n=2000, seed=21):
+    """About 2 000 points in an 8 x 6 x 6 container: three Gaussian clusters (sigma 0.3) and a uniform rest; and 600
+    queries, half of them near points, the others uniform up to 1.5 beyond the container (clamped cells)."""
+    params = ws.make_params(container_size=(8.0, 6.0, 6.0), container_position=POSITIONS[where])
+    mn = np.asarray(params.ext_min[:3], np.float64)
+    mx = np.asarray(params.ext_max[:3], np.float64)
+    rng = np.random.default_rng(seed)
+    centres = mn + rng.random((3, 3)) * (mx - mn)
+    clustered = centres[rng.integers(0, 3, n * 3 // 5)] + rng.normal(0.0, 0.3, (n * 3 // 5, 3))
+    uniform = mn + rng.random((n - len(clustered), 3)) * (mx - mn)
+    x = np.clip(np.concatenate([clustered, uniform]), mn, mx).astype(F32)
+    near = x[rng.choice(n, 300, replace=False)] + rng.normal(0.0, 0.05, (300, 3))
+    wide = (mn - 1.5) + rng.random((300, 3)) * (mx - mn + 3.0)
+    return params, x, np.concatenate([near, wide]).astype(F32)
+
+
+def _candidates(bins, q, n):
+    """(len(q), n) bool: particle j is in the candidate columns of query i."""
+    cols = bins.columns(q)
+    out = np.zeros((len(q), n), bool)
+    rows = np.broadcast_to(np.arange(len(q))[:, None], cols.shape)
+    out[rows[cols >= 0], bins.order[cols[cols >= 0]]] = True
+    assert out.sum() == np.count_nonzero(cols >= 0)  # no particle twice in a query's columns
+    return out
+
+
+def _accepted(grid, x, q):
+    """(len(q), n) bool: the float32 distance test of the kernels on every pair."""
+    e = (x[None, :, :] - q[:, None, :]).astype(F32)
+    d2 = ((e[..., 0] * e[..., 0] + e[..., 1] * e[..., 1]) + e[..., 2] * e[..., 2]).astype(F32)
+    return ~(d2 > grid.d2_accept)
+
+
+@pytest.mark.parametrize("where", list(POSITIONS))
+def test_unit_merge_factors_bin_as_the_unmerged_restatement_did(ws, where):
+    params, x, _ = _grid_scene(ws, where)
+    g = A.Grid(params, merged=(1, 1, 1))
+    b = A.Binned(g, x)
+    # the restatement before it knew of merged cells, written out
+    h = F32(params.smoothing_radius)
+    org = np.floor(np.asarray(params.ext_min[:3], F32) / h).astype(np.int64) - A.GRID_PAD
+    dim = np.floor(np.asarray(params.ext_max[:3], F32) / h).astype(np.int64) + A.GRID_PAD - org + 1
+    c = np.clip(np.floor(x / h).astype(np.int64) - org, 0, dim - 1)
+    key = (c[:, 0] * dim[1] + c[:, 1]) * dim[2] + c[:, 2]
+    order = np.argsort(key, kind="stable")
+    start = np.searchsorted(key[order], np.arange(int(np.prod(dim)) + 1))
+    assert np.array_equal(g.dim, dim) and np.array_equal(g.fdim, dim) and np.array_equal(g.org, org)
+    assert np.array_equal(b.order, order) and np.array_equal(b.start, start)
+    assert np.array_equal(A.Binned(A.Grid(params), x).start, start)  # the default is the un-merged grid
+    if where == "off-centre":
+        assert np.all(np.abs(org) >= 8) and len(set(np.sign(org))) == 2  # far from 0, mixed signs
+
+
+@pytest.mark.parametrize("merge", list(MERGES))
+@pytest.mark.parametrize("where", list(POSITIONS))
+def test_merged_cells_hold_every_pair_within_h_and_accept_the_same_pairs(ws, where, merge):
+    params, x, q = _grid_scene(ws, where)
+    plain = A.Grid(params)
+    merged = MERGES[merge](plain.fdim)
+    g = A.Grid(params, merged)
+    assert np.array_equal(g.dim, -(-plain.fdim // np.asarray(merged))) and np.array_equal(g.org, plain.org)
+    if merge == "one-layer-x":
+        assert g.dim[0] == 1
+    if merge == "ragged":
+        assert np.all(plain.fdim % np.asarray(merged) != 0)
+    assert [m > 1 for m in merged] == {"z": [False, False, True], "zy": [False, True, True]}.get(merge, [True] * 3)
+    b, b0 = A.Binned(g, x), A.Binned(plain, x)
+    assert b.start[-1] == len(x) and len(b.start) == int(np.prod(g.dim)) + 1
+    n = len(x)
+    h = float(F32(params.smoothing_radius))
+    for pts in (x, q):
+        # the header's invariant: cell edges stay >= h, so every pair within h (float64, all pairs) is a candidate
+        d = np.sqrt(((pts[:, None, :].astype(np.float64) - x[None, :, :].astype(np.float64)) ** 2).sum(2))
+        cand = _candidates(b, pts, n)
+        assert np.all(cand[d <= h])
+        assert cand.sum() >= _candidates(b0, pts, n).sum()
+        # ... and the distance test decides: the accepted pairs are the un-merged grid's
+        acc = _accepted(g, x, pts)
+        assert np.array_equal(cand & acc, _candidates(b0, pts, n) & acc)
+        assert np.count_nonzero((cand & acc).sum(1) >= 8) >= len(pts) // 4
+    # the same through the restated stage and fields: counts equal, float64 equal up to its own summation order, and
+    # the float32 field of the merged order inside field64's bound
+    a = A.defaults()
+    s0 = A.stage(params, x, a)
+    s1 = A.stage(params, x, a, merged=merged)
+    assert np.array_equal(s1[3], s0[3]) and np.array_equal(s0[3], _accepted(g, x, x).sum(1))
+    assert np.any(s0[3] >= a["min_neighbours"]) and np.any(s0[3] < a["min_neighbours"])
+    # (the stage's float32 sums run in another order on the merged grid: the fields below take ONE stage as their input)
+    r0, g0, tr0, tg0, n0 = A.field64(params, s0[0], s0[1], s0[2], q)
+    r1, g1, tr1, tg1, n1 = A.field64(params, s0[0], s0[1], s0[2], q, merged=merged)
+    assert np.array_equal(n1, n0) and np.count_nonzero(n0) > len(q) // 4 and np.count_nonzero(n0 == 0) > len(q) // 20
+    # float64 sums of the same terms in two orders differ by at most n 2^-53 sum |t| <= 2^-29 of the float32 bound
+    assert np.all(np.abs(r1 - r0) <= tr0 * 2.0 ** -24) and np.all(np.abs(g1 - g0) <= tg0 * 2.0 ** -24)
+    assert np.allclose(tr1, tr0, rtol=1e-12, atol=0) and np.allclose(tg1, tg0, rtol=1e-12, atol=0)
+    rho, grad = A.field32(params, s0[0], s0[1], s0[2], q, merged=merged)
+    assert np.all(np.abs(rho - r0) <= tr0) and np.all(np.abs(grad - g0) <= tg0)
+    assert np.all(rho[n0 == 0] == 0) and np.all(grad[n0 == 0] == 0)
+    iso_m = A.iso_field32(params, x, q, merged=merged)
+    iso_0 = A.iso_field32(params, x, q)
+    assert np.array_equal(iso_m == 0, iso_0 == 0) and np.allclose(iso_m, iso_0, rtol=64 * 2.0 ** -24, atol=0)

@@ -82,12 +82,17 @@ def test_the_isotropic_limit_on_settled_c3_at_half_h(ws):
 
 
 # ---- 2. the stage bit for bit -------------------------------------------------------------------------------------------
-def _check_stage(ws, w, params, case):
+def _check_stage(ws, w, params, case, merged=(1, 1, 1), ids=None, restated=None):
+    """The handle's stage against the restatement on its grid (of `merged` cells), at every particle or at `ids`; the
+    restatement's own arrays go into the dict `restated` by parameter set."""
     x = w.read_positions()
     for name, d in (("defaults", A.defaults()), ("sheet", SHEET)):
         got = w.anisotropy(params_of(ws, d))
-        want = A.stage(params, x, d)
+        want = A.stage(params, x, d, merged=merged, ids=ids)
+        if restated is not None:
+            restated[name] = want
         for label, a, b in zip(("centre", "matrix", "scale", "neighbours"), got, want):
+            a = a if ids is None else a[ids]
             assert same_bits(a, b), "%s %s: %s differs in %d of %d" % (case, name, label,
                                                                        np.count_nonzero(a.view(np.uint32) != b.view(np.uint32)), a.size)
     return got
@@ -136,9 +141,9 @@ def test_the_stage_on_coincident_pairs_and_an_overflow_clump(ws):
 
 
 # ---- 3. the field against float64 -------------------------------------------------------------------------------------
-def _check_f64(params, stage, q, rho, grad, case):
+def _check_f64(params, stage, q, rho, grad, case, merged=(1, 1, 1)):
     c, m, f, _ = stage
-    r64, g64, tr, tg, _ = A.field64(params, c, m, f, q)
+    r64, g64, tr, tg, _ = A.field64(params, c, m, f, q, merged=merged)
     er = np.abs(rho.astype(np.float64) - r64)
     eg = np.abs(grad.astype(np.float64) - g64)
     assert np.all(er <= tr), "%s: density err/tol %.3g" % (case, np.max(er / np.maximum(tr, 1e-300)))
@@ -310,8 +315,8 @@ def test_anisotropic_calls_across_a_regrid_leave_the_trajectory_unchanged(ws):
 
 
 # ---- 7. slabs -----------------------------------------------------------------------------------------------------------
-def _slab_run(ws, params, pos, world, steps, body_calls):
-    owner = ws.slab.assign(params, pos, world)
+def _slab_run(ws, params, pos, world, steps, body_calls, **worker_args):
+    owner = ws.slab.assign(params, pos, world, worker_args.get("library"))
     hub = ws.slab.LoopbackHub(world)
     got = [None] * world
     errors = []
@@ -319,7 +324,7 @@ def _slab_run(ws, params, pos, world, steps, body_calls):
     def body(r):
         try:
             sel = np.flatnonzero(owner == r).astype(np.uint32)
-            s = ws.slab.SlabWorker(pos[sel], sel, pos.shape[0], params, r, world, hub.transport(r))
+            s = ws.slab.SlabWorker(pos[sel], sel, pos.shape[0], params, r, world, hub.transport(r), **worker_args)
             s.run(steps)
             got[r] = body_calls(s, r)
             s.run(2)  # nobody was left waiting

@@ -38,15 +38,17 @@ def _sphere(rng, n):
     return _unit(rng.normal(size=(n, 3)))
 
 
-def make_rays(cur, params, seed=7):
+def make_rays(cur, params, seed=7, radius=11.0, far=(60.0, 64.0), centre=None):
     """About 2 000 rays in six classes (the class of each ray in `cls`): (a) from a sphere around the container at a
     particle, (b) from a particle, (c) away from the container, (d) axis-parallel, (e) from 50 units outside the grid,
-    (f) grazing the container's faces.  Directions are deliberately not unit vectors."""
+    (f) grazing the container's faces.  Directions are deliberately not unit vectors.  The spheres have the radii
+    `radius` and `far` (for this file's 16 x 9 x 9 container) about `centre` (the origin)."""
     rng = np.random.default_rng(seed)
     mn = np.asarray(params.ext_min[:3], np.float64)
     mx = np.asarray(params.ext_max[:3], np.float64)
     h = float(params.smoothing_radius)
     O, V, cls = [], [], []
+    shift = np.zeros(3) if centre is None else np.asarray(centre, np.float64)
 
     def add(c, o, v):
         O.append(np.asarray(o, np.float64))
@@ -54,14 +56,14 @@ def make_rays(cur, params, seed=7):
         cls.extend([c] * len(o))
 
     # (a) radius 11 > the container's half diagonal (10.05); |v| >= 1.2 reaches 24 > 11 + 10.05 in 160 steps of h / 2
-    o = 11.0 * _sphere(rng, 700)
+    o = shift + radius * _sphere(rng, 700)
     target = cur[rng.choice(len(cur), 700, replace=False)].astype(np.float64)
     add("a", o, _unit(target - o) * rng.uniform(1.2, 1.6, (700, 1)))
     # (b) the origin IS a particle's position
     add("b", cur[rng.choice(len(cur), 200, replace=False)].astype(np.float64), _sphere(rng, 200) * rng.uniform(0.5, 1.5, (200, 1)))
     # (c) outwards from the same sphere
-    o = 11.0 * _sphere(rng, 300)
-    add("c", o, _unit(o) * rng.uniform(0.5, 1.5, (300, 1)))
+    o = radius * _sphere(rng, 300)
+    add("c", shift + o, _unit(o) * rng.uniform(0.5, 1.5, (300, 1)))
     # (d) two direction components exactly zero, from one unit outside a face towards it
     for axis in range(3):
         for sign in (-1.0, 1.0):
@@ -71,7 +73,7 @@ def make_rays(cur, params, seed=7):
             v[:, axis] = -sign * rng.uniform(0.6, 1.4, 50)
             add("d", o, v)
     # (e) 50 units and more outside the grid, at a point of the container: |v| = 3.6 reaches 72 in 160 steps
-    o = rng.uniform(60.0, 64.0, (200, 1)) * _sphere(rng, 200)
+    o = shift + rng.uniform(far[0], far[1], (200, 1)) * _sphere(rng, 200)
     target = mn + rng.random((200, 3)) * (mx - mn)
     add("e", o, _unit(target - o) * 3.6)
     # (f) along a face, within h of its plane (inside and outside), slightly tilted
