@@ -2,7 +2,7 @@
 # Registers / LDS / scratch of every kernel in ws_kernels.hip (device-only assembly, no GPU needed).
 # usage: tools/kernel_regs.sh [extra hipcc flags]   -> /tmp/ws_kernels.s + a table on stdout
 cd "$(dirname "$0")/.."
-/opt/rocm/bin/hipcc -x hip --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off --cuda-device-only -S \
+/opt/rocm/bin/hipcc -x hip --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize --cuda-device-only -S \
   -Iinclude -Iwater-sandbox_amd/csrc "$@" -o /tmp/ws_kernels.s water-sandbox_amd/csrc/ws_kernels.hip || exit 1
 python3 - <<'PY'
 import re

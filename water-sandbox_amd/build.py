@@ -19,8 +19,12 @@ REFCHECK_EXTRA = [os.path.join(REFCHECK_DIR, f) for f in ("ws_refcheck.inc", "ws
 
 # -ffp-contract=off: every float op in the kernels is one IEEE binary32 op, written in the
 # reference WGSL's evaluation order (no FMA contraction), see ws_kernels.hip.
+# -fno-slp-vectorize: the SLP vectoriser pairs adjacent scalar f32 multiplies and adds into v_pk_*_f32, which cost the
+# issue-bound neighbour kernels more cycles than the two scalar instructions each replaces (same IEEE operations either
+# way; HISTORY.md round 6).  tools/kernel_regs.sh and tools/ab_build.sh carry the same flags;
+# tests/test_kernel_instructions.py reads this list.
 HIPCC_FLAGS = [
-    "-x", "hip", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
+    "-x", "hip", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize",
     "-fPIC", "-shared", "-Wall", "-Wno-unused-value", "-Wno-unused-result",
 ]
 

@@ -13,6 +13,8 @@
 // the scalar factors of a pair collected before they meet the direction vector (force_pair).  What differs from
 // the reference otherwise is only the ORDER in which neighbours are visited (dense-grid order instead of
 // hashed-bucket order).  Every parity test applies ONE tolerance to both forms.
+// It is also compiled with -fno-slp-vectorize: adjacent scalar f32 multiplies and adds stay scalar instructions (same
+// rounding as their packed v_pk_*_f32 forms, fewer issue cycles in the neighbour kernels; build.py).
 #include <stdlib.h>
 
 #include <algorithm>
@@ -1028,7 +1030,7 @@ __device__ __forceinline__ void run_bounds(const uint32_t *__restrict__ start, i
 }
 
 // K4's phase 1 over one run on the planar arrays: 4 candidates per trip from three 16-B loads, the
-// squared distances as packed f32 vector arithmetic (same IEEE operations per candidate, same order).
+// squared distances in scalar f32 arithmetic (same IEEE operations per candidate, same order).
 // Lanes past their run's end keep loading in-bounds slots (the planes are padded) and are masked
 // out of the accept test.  note(nvalid, bits): the trip tested nvalid candidates, bit u = candidate u accepted.
 template <class Push, class Phase2, class Note>
@@ -1045,8 +1047,14 @@ __device__ __forceinline__ void nd_run_planar(const WsDev &d, float4 o, uint32_t
         const nd_f4 Y = *reinterpret_cast<const nd_f4u *>(reinterpret_cast<const char *>(p.y) + off);
         const nd_f4 Z = *reinterpret_cast<const nd_f4u *>(reinterpret_cast<const char *>(p.z) + off);
         __builtin_amdgcn_sched_barrier(0);  // the three loads are issued before any is consumed
-        const nd_f4 ex = X - o.x, ey = Y - o.y, ez = Z - o.z;
-        const nd_f4 d2 = ex * ex + ey * ey + ez * ez;
+        // per component, not as vector expressions: those came out as v_pk_*_f32, which cost more issue cycles here
+        // than the two scalar instructions each replaces (HISTORY.md round 6; the file is built without SLP too)
+        float d2[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const float ex = X[u] - o.x, ey = Y[u] - o.y, ez = Z[u] - o.z;
+            d2[u] = ex * ex + ey * ey + ez * ez;
+        }
         uint32_t bits = 0;
 #pragma unroll
         for (int u = 0; u < 4; u++) {
@@ -1097,6 +1105,9 @@ __device__ __forceinline__ void nd_tile(const WsDev &d, const uint32_t *__restri
     // bits that spilled over start the next one -- the crossing is the rare path, one trip in eight.
     uint32_t acc32 = 0;
     uint32_t pos = 0, word = 0;  // candidates seen so far = 32 * word + pos
+    // the row of mask word `word` for this particle: a running pointer, one stride further at each crossing (the word
+    // index only ever goes up by one; the product word * stride was a quarter-rate 64-bit multiply that some lane of
+    // the wave took on every trip).  It stops at row ND_MASK_WORDS, where nothing is stored any more.
     uint32_t *mrow = mask.words + (iv - d.base);
     auto push = [&](uint32_t slot, float d2) { list[slot * ND_P + tid] = d2; };
     auto phase2 = [&](uint32_t cnt) {
@@ -1112,7 +1123,10 @@ __device__ __forceinline__ void nd_tile(const WsDev &d, const uint32_t *__restri
         acc32 |= bits << pos;
         pos += nvalid;
         if (pos >= 32u) {  // pos was >= 28, so the shift below is by 1..4
-            if (word < ND_MASK_WORDS) mrow[(size_t)word * mask.stride] = acc32;
+            if (word < ND_MASK_WORDS) {
+                *mrow = acc32;
+                mrow += mask.stride;
+            }
             pos -= 32u;
             acc32 = bits >> (nvalid - pos);  // the bits that spilled over: the trip's last `pos` ones
             word++;
@@ -1140,7 +1154,7 @@ __device__ __forceinline__ void nd_tile(const WsDev &d, const uint32_t *__restri
     }
     phase2(cnt);
     if (valid) {
-        if (pos && word < ND_MASK_WORDS) mrow[(size_t)word * mask.stride] = acc32;
+        if (pos && word < ND_MASK_WORDS) *mrow = acc32;
         if (32u * word + pos > 32u * ND_MASK_WORDS) atomicAdd(&stats[0], 1u);  // rare by construction: one counter is enough
         density_store(density, near_density, i, srt);
     }
@@ -1320,6 +1334,7 @@ __device__ __forceinline__ void nf_tile(const WsDev &d, const uint32_t *__restri
         // when its word is fetched -- simulation.wgsl:232 `particle_index == neighbour_index`).
         uint32_t rest = 0, wbase = 0, widx = 0;
         uint32_t wnext = nwords ? mrow[0] : 0u;  // one mask word ahead
+        const uint32_t *mnext = mrow;            // ... and its row: a running pointer, one stride per word (no multiply in the loop)
         // One pending-bits register per lane: a neighbour is ffs + clear + one compare against the end of the current
         // run.  The two rare steps -- next mask word, next run -- are short and independent, so a wave in which some
         // lane takes one of them on almost every trip (9 words and 9 runs per lane in the dense state) pays ~15
@@ -1331,7 +1346,8 @@ __device__ __forceinline__ void nf_tile(const WsDev &d, const uint32_t *__restri
                 wbase = widx << 5;
                 if (widx == (self_s >> 5)) rest &= ~(1u << (self_s & 31u));
                 widx++;
-                wnext = widx < nwords ? mrow[(size_t)widx * mask.stride] : 0u;
+                mnext += mask.stride;
+                wnext = widx < nwords ? *mnext : 0u;
             }
             const uint32_t sc = wbase + (uint32_t)__ffs((int)rest) - 1u;
             rest &= rest - 1u;
