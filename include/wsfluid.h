@@ -248,7 +248,8 @@ ws_status ws_reset(ws_handle *h, const float *pos_xyz);
 ws_status ws_write_particles(ws_handle *h, const ws_particle80 *in);
 
 /* ---- the per-frame calls above on a SLAB handle (multi-GPU, below) ---------------------------------------------
- * ws_read_positions / _begin / _end, ws_read_speeds, ws_read_particles, ws_read_sort_view, ws_reset, ws_write_particles
+ * ws_read_positions / _begin / _end, ws_read_speeds, ws_read_velocities, ws_read_particles, ws_read_sort_view, ws_reset,
+ * ws_write_particles
  * and a ws_set_params that changes the smoothing radius or the container work on slab handles too, over GLOBAL,
  * id-ordered arrays (n_global entries), as COLLECTIVE calls: every rank makes the same call at the same point of its
  * frame, as the ranks of a multi-GPU host do anyway.
@@ -587,6 +588,57 @@ ws_status ws_cast_rays(ws_handle *h, const ws_aniso_params *a, const ws_ray_para
 /* One ray per pixel of a size[0] x size[1] (W x H) image. */
 ws_status ws_cast_camera(ws_handle *h, const ws_aniso_params *a, const ws_ray_params *r, const ws_camera *cam,
                          const uint32_t size[2], float *out_t, float *out_normal);
+
+/* ---- the fluid's velocity as a field, and tracers carried by it (no reference counterpart) ----------
+ * The calls above read positions only.  These give the other half of the state by place, not by particle: colour the
+ * extracted mesh by flow speed (the reference's commented-out speed colouring, src/fluid_compute.rs:489-502, moved from
+ * the particles to the surface), draw streamlines, carry foam, dye or debris with the water, probe the flow at a point.
+ *
+ * ws_read_velocities: n*3 floats in ORIGINAL-ID order (n = ws_num_particles, or the global count on slab handles), the
+ *   companion of ws_read_positions: the velocities the enqueued steps leave; before the first step zeros, or what
+ *   ws_write_particles loaded.  Slab handles: COLLECTIVE, out_xyz == NULL only contributes.
+ *
+ * Velocity field at a node or point o (ws_sample_velocity_grid / _points): the node formula, node order, accept test,
+ *   27-cell stencil of the clamped cell, canonical summation order and argument errors of ws_sample_density_grid /
+ *   _points.  Per accepted candidate j, in canonical order:
+ *     d = sqrt(d2) (the handle's sqrt), w = (h - d)^2 * pow2 -- the density sampler's term, the same bits;
+ *     rho += w; M_a += fl(w * v_j,a) for a = x, y, z: each product rounded, then each sum; all four sums start at 0.
+ *   After the sweep u_a = M_a / rho, correctly rounded whatever the handle's flags, if rho > 0; otherwise u = (+0, +0, +0).
+ *   Only the sqrt inside w follows WS_FLAG_IEEE_DIVISION (the split the surface normals use).
+ *   out_velocity: 3 floats per node or point (u); out_density: rho, BIT-IDENTICAL to what ws_sample_density_grid /
+ *   _points return for the same query.  v_j is what ws_read_velocities returns for particle j, x_j what
+ *   ws_read_positions returns.  Either output may be NULL, not both on a single handle.  The field is isotropic.
+ *
+ * ws_advect_points moves m tracer points through the FROZEN field of the current state (the fluid does not move during
+ *   the call).  Per point, independently of the other points, `substeps` times (midpoint rule; hdt = fl(0.5f * dt)):
+ *     1. (u1, rho1) = the field at p exactly as ws_sample_velocity_points defines it.  rho1 == 0: the tracer is outside
+ *        the fluid; p stays and the loop ends.
+ *     2. q_a = fl(p_a + fl(hdt * u1_a)); (u2, rho2) = the field at q.  rho2 == 0: u2 = u1 (the midpoint left the fluid:
+ *        an Euler step).
+ *     3. p_a = fl(p_a + fl(dt * u2_a)).
+ *   out_xyz (required on a rank that wants output): the final p, m*3 floats; xyz and out_xyz may be the same buffer.
+ *   out_velocity / out_density (optional): the field at the final p, from one more sweep.  There is no container clamp.
+ *   A host that performs this march itself with ws_sample_velocity_points and float arithmetic gets the same bits, in
+ *   either arithmetic of the handle.
+ * All of them wait for enqueued steps, write nothing ws_step reads, recompute the binning from the current state on every
+ * call and keep their scratch in the sampler's (grow-only, freed by ws_destroy; the velocity arrays are allocated on the
+ * first velocity call only).  Slab handles: COLLECTIVE on the gathered global set (one gather of {position, velocity}),
+ * the same bits as a single handle; a rank that passes every output NULL only contributes, and a rank validates its query
+ * only after the gather, so a refused rank leaves no peer waiting.
+ * Errors: as ws_sample_density_grid / _points; WS_ERR_UNSUPPORTED (WS_FLAG_REFERENCE_ORDER handles, ws_read_velocities
+ * included); WS_ERR_HIP on an unusable handle; ws_advect_points also WS_ERR_INVALID_ARG for: NULL a; substeps outside
+ * 1 .. 4096; dt non-finite or |dt| > 1e6 (0 and negative dt are allowed: backward tracing); NULL xyz; a non-finite
+ * coordinate or |coordinate| > 1e15; m == 0, more than 2^28 points; NULL out_xyz with another output given. */
+typedef struct ws_advect_params {
+    float dt;          /* time the tracers travel per substep (any sign)                             */
+    uint32_t substeps; /* midpoint steps of dt each, 1 .. 4096                                       */
+} ws_advect_params;
+ws_status ws_read_velocities(ws_handle *h, float *out_xyz);
+ws_status ws_sample_velocity_grid(ws_handle *h, const float origin[3], const float spacing[3], const uint32_t dims[3],
+                                  float *out_velocity, float *out_density);
+ws_status ws_sample_velocity_points(ws_handle *h, const float *xyz, uint32_t m, float *out_velocity, float *out_density);
+ws_status ws_advect_points(ws_handle *h, const ws_advect_params *a, const float *xyz, uint32_t m, float *out_xyz,
+                           float *out_velocity, float *out_density);
 
 /* ---- introspection ------------------------------------------------------------- */
 const char *ws_last_error(ws_handle *h);

@@ -29,7 +29,7 @@ ws_status slab_gather_by_id(ws_handle *h, int kind);
 ws_status slab_reset(ws_handle *h, const float *pos_xyz);
 ws_status slab_write_particles(ws_handle *h, const ws_particle80 *in);
 ws_status slab_regrid(ws_handle *h, const ws_params *params, bool rebalance);
-ws_status slab_field_positions(ws_handle *h, const float **xyz, WsDev *global);
+ws_status slab_field_positions(ws_handle *h, const float **xyz, WsDev *global, bool with_vel = false);
 
 ws_status fail(ws_handle *h, ws_status st, const char *what, hipError_t e = hipSuccess)
 {
@@ -653,6 +653,10 @@ void free_field(ws_handle *h, bool all)
     F.mxyz = F.mnrm = nullptr;
     F.code_bytes = F.vbase_bytes = F.bcnt_bytes = F.bstart_bytes = F.bstate_bytes = F.tri_bytes = 0;
     F.mxyz_bytes = F.mnrm_bytes = 0;
+    hipFree(F.vxyz); hipFree(F.vpos); hipFree(F.svel);
+    F.vxyz = F.vpos = nullptr;
+    F.svel = nullptr;
+    F.vxyz_bytes = F.vpos_bytes = F.svel_bytes = 0;
     hipFree(F.cxyz); hipFree(F.amf); hipFree(F.smf); hipFree(F.anb);
     F.cxyz = nullptr;
     F.amf = F.smf = nullptr;
@@ -1245,6 +1249,38 @@ ws_status ws_read_speeds(ws_handle *h, float *out_speed)
     return WS_OK;
 }
 
+// The velocities by id, ws_read_positions' companion.  A slab gathers {position, velocity} records (the velocity field's
+// one collective) and keeps the velocity half.
+ws_status ws_read_velocities(ws_handle *h, float *out_xyz)
+{
+    if (!h || (!out_xyz && !h->slab)) return WS_ERR_INVALID_ARG;
+    WS_DEAD_CHECK(h);
+    if (h->flags & WS_FLAG_REFERENCE_ORDER) return fail(h, WS_ERR_UNSUPPORTED, "velocities: not in the reference-order validation mode");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const uint32_t n = h->slab ? h->slab->n_global : h->n;
+    const size_t bytes = (size_t)n * 12;
+    if (h->slab) {
+        ws_status st = slab_gather_by_id(h, WS_PACK_POSVEL_H);
+        if (st) return st;
+        if (out_xyz) {
+            if ((st = ensure_stage(h, bytes))) return st;
+            wsk_field_split(h->stream, reinterpret_cast<const float *>(h->slab->g_out), nullptr, (float *)h->stage, n);
+            HIP_TRY(h, hipGetLastError());
+            HIP_TRY(h, hipMemcpyAsync(out_xyz, h->stage, bytes, hipMemcpyDeviceToHost, h->stream));
+        }
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        return WS_OK;
+    }
+    ws_status st = ensure_stage(h, bytes);
+    if (st) return st;
+    wsk_gather_velocities(h->stream, h->cur, (float *)h->stage, n);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(out_xyz, h->stage, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    drain_profile(h);
+    return WS_OK;
+}
+
 // Page-lock / release a host buffer the caller owns and keeps alive (e.g. the Vec update() reads positions
 // into every frame): a device->host copy into pinned memory runs at PCIe rate (C3: 0.97 ms for 50 MB) instead
 // of through the runtime's pageable staging (9.8 ms).  Explicit on purpose: pinning caller memory behind its
@@ -1412,10 +1448,13 @@ ws_status field_check(ws_handle *h, const float *xyz, uint32_t m, const float *g
 // F.amf, F.anb by id), then the centres binned the same way (F.spos, F.smf); stage_only: stop after the stage.
 // bin_out != nullptr: stop after the binning (F.start, F.spos and with ap F.smf are what a field kernel reads) and
 // return the grid the particles were binned on -- the ray calls sample with a kernel of their own.
+// vel (with bin_out, without ap): the velocities too, by id in F.vxyz and in F.spos' order in F.svel; a slab gathers
+// {position, velocity} records once and splits them.
 template <class Check>
 ws_status field_sample_device(ws_handle *h, const float *xyz, uint32_t m, const float *grid6, const uint32_t *dims,
                               bool want, bool rho_on, bool grad_on, Check check, bool *contributed,
-                              const ws_aniso_params *ap = nullptr, bool stage_only = false, WsDev *bin_out = nullptr)
+                              const ws_aniso_params *ap = nullptr, bool stage_only = false, WsDev *bin_out = nullptr,
+                              bool vel = false)
 {
     *contributed = false;
     if (!h->slab && want) {
@@ -1429,7 +1468,7 @@ ws_status field_sample_device(ws_handle *h, const float *xyz, uint32_t m, const 
     const float *pos = nullptr;
     uint32_t n = h->n;
     if (h->slab) {
-        ws_status st = slab_field_positions(h, &pos, &d);
+        ws_status st = slab_field_positions(h, &pos, &d, vel);
         if (st) return st;
         n = h->slab->n_global;
         if (!want) {
@@ -1450,6 +1489,17 @@ ws_status field_sample_device(ws_handle *h, const float *xyz, uint32_t m, const 
         wsk_gather_positions(s, h->cur, F.xyz, n);
         pos = F.xyz;
     }
+    if (vel) {
+        if ((st = field_grow(h, &F.vxyz, &F.vxyz_bytes, (size_t)n * 12))) return st;
+        if ((st = field_grow(h, &F.svel, &F.svel_bytes, (size_t)n * 16))) return st;
+        if (h->slab) {
+            if ((st = field_grow(h, &F.vpos, &F.vpos_bytes, (size_t)n * 12))) return st;
+            wsk_field_split(s, pos, F.vpos, F.vxyz, n);
+            pos = F.vpos;
+        } else {
+            wsk_gather_velocities(s, h->cur, F.vxyz, n);
+        }
+    }
     // counting sort by cell, ascending id inside a cell (the sort view's passes on the sampler's own arrays)
     wsk_field_keys(s, d, pos, F.keys, n);
     HIP_TRY(h, hipMemsetAsync(F.count, 0, (size_t)d.ncells * 4, s));
@@ -1458,6 +1508,7 @@ ws_status field_sample_device(ws_handle *h, const float *xyz, uint32_t m, const 
     wsk_scatter(s, F.keys, F.cursor, F.tmp, n, nullptr);
     wsk_view_fix(s, F.tmp, F.keys, F.start, F.perm, n);
     wsk_field_gather(s, F.perm, pos, F.spos, n);
+    if (vel) wsk_field_gather_vel(s, F.perm, F.vxyz, F.svel, n);
     HIP_TRY(h, hipGetLastError());
     if (ap) {
         if ((st = field_grow(h, &F.cxyz, &F.cxyz_bytes, (size_t)n * 12))) return st;
@@ -1726,6 +1777,88 @@ ws_status cast_rays(ws_handle *h, const ws_aniso_params *ap, const ws_ray_params
     return WS_OK;
 }
 
+// ws_sample_velocity_grid / _points: the sampler's binning with the velocities beside the positions, the velocity
+// kernel, the results copied out.  The query is the density sampler's, errors included.
+ws_status sample_velocity(ws_handle *h, const float *xyz, uint32_t m, const float *grid6, const uint32_t *dims, float *out_vel,
+                          float *out_rho)
+{
+    WS_DEAD_CHECK(h);
+    if (h->flags & WS_FLAG_REFERENCE_ORDER) return fail(h, WS_ERR_UNSUPPORTED, "velocity field: not in the reference-order validation mode");
+    const bool want = out_vel || out_rho;
+    if (!want && !h->slab) return fail(h, WS_ERR_INVALID_ARG, "velocity field: both outputs are NULL");
+    bool contributed = false;
+    auto check = [&]() -> ws_status { return field_check(h, xyz, m, grid6, dims); };
+    WsDev d;
+    ws_status st = field_sample_device(h, nullptr, 0, nullptr, nullptr, want, false, false, check, &contributed, nullptr, false,
+                                       &d, true);
+    if (st || contributed) return st;
+    hipStream_t s = h->stream;
+    auto &F = h->field;
+    const uint64_t nq = grid6 ? (uint64_t)dims[0] * dims[1] * dims[2] : m;
+    if (!grid6) {
+        if ((st = field_grow(h, &F.q, &F.q_bytes, (size_t)m * 12))) return st;
+        HIP_TRY(h, hipMemcpyAsync(F.q, xyz, (size_t)m * 12, hipMemcpyHostToDevice, s));
+    }
+    if (out_rho && (st = field_grow(h, &F.rho, &F.rho_bytes, (size_t)nq * 4))) return st;
+    if (out_vel && (st = field_grow(h, &F.grad, &F.grad_bytes, (size_t)nq * 12))) return st;
+    // the brick kernel from one node per cell up, as the density sampler; the points form below
+    const bool bricks = grid6 && grid6[3] <= d.h && grid6[4] <= d.h && grid6[5] <= d.h;
+    wsk_velocity_sample(s, d, F.start, F.spos, F.svel, h->ieee, F.q, (uint32_t)nq, grid6, dims, bricks,
+                        out_vel ? F.grad : nullptr, out_rho ? F.rho : nullptr);
+    HIP_TRY(h, hipGetLastError());
+    if (out_rho) HIP_TRY(h, hipMemcpyAsync(out_rho, F.rho, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+    if (out_vel) HIP_TRY(h, hipMemcpyAsync(out_vel, F.grad, (size_t)nq * 12, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    drain_profile(h);
+    return WS_OK;
+}
+
+// The query of ws_advect_points (include/wsfluid.h).
+ws_status advect_check(ws_handle *h, const ws_advect_params *a, const float *xyz, uint32_t m, const float *out_xyz)
+{
+    if (!a) return fail(h, WS_ERR_INVALID_ARG, "advection: the parameters are required");
+    if (a->substeps < 1u || a->substeps > 4096u) return fail(h, WS_ERR_INVALID_ARG, "advection: substeps must lie in 1 .. 4096");
+    if (!isfinite(a->dt) || fabsf(a->dt) > 1e6f) return fail(h, WS_ERR_INVALID_ARG, "advection: dt must be finite and within 1e6");
+    if (!xyz || m == 0u) return fail(h, WS_ERR_INVALID_ARG, "advection: no points");
+    if (m > (1u << 28)) return fail(h, WS_ERR_INVALID_ARG, "advection: more than 2^28 points");
+    if (!out_xyz) return fail(h, WS_ERR_INVALID_ARG, "advection: out_xyz is required");
+    for (size_t t = 0; t < (size_t)m * 3; t++)
+        if (!isfinite(xyz[t]) || fabsf(xyz[t]) > 1e15f)
+            return fail(h, WS_ERR_INVALID_ARG, "advection: points must be finite and within 1e15");
+    return WS_OK;
+}
+
+// ws_advect_points: the binning with velocities, the march kernel (in place on the uploaded points), the results out.
+ws_status advect_points(ws_handle *h, const ws_advect_params *a, const float *xyz, uint32_t m, float *out_xyz, float *out_vel,
+                        float *out_rho)
+{
+    WS_DEAD_CHECK(h);
+    if (h->flags & WS_FLAG_REFERENCE_ORDER) return fail(h, WS_ERR_UNSUPPORTED, "advection: not in the reference-order validation mode");
+    const bool want = out_xyz || out_vel || out_rho;
+    if (!want && !h->slab) return fail(h, WS_ERR_INVALID_ARG, "advection: every output is NULL");
+    bool contributed = false;
+    auto check = [&]() -> ws_status { return advect_check(h, a, xyz, m, out_xyz); };
+    WsDev d;
+    ws_status st = field_sample_device(h, nullptr, 0, nullptr, nullptr, want, false, false, check, &contributed, nullptr, false,
+                                       &d, true);
+    if (st || contributed) return st;
+    hipStream_t s = h->stream;
+    auto &F = h->field;
+    if ((st = field_grow(h, &F.q, &F.q_bytes, (size_t)m * 12))) return st;
+    if (out_rho && (st = field_grow(h, &F.rho, &F.rho_bytes, (size_t)m * 4))) return st;
+    if (out_vel && (st = field_grow(h, &F.grad, &F.grad_bytes, (size_t)m * 12))) return st;
+    HIP_TRY(h, hipMemcpyAsync(F.q, xyz, (size_t)m * 12, hipMemcpyHostToDevice, s));
+    wsk_advect(s, d, F.start, F.spos, F.svel, h->ieee, F.q, m, a->dt, a->substeps, out_vel ? F.grad : nullptr,
+               out_rho ? F.rho : nullptr);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(out_xyz, F.q, (size_t)m * 12, hipMemcpyDeviceToHost, s));
+    if (out_rho) HIP_TRY(h, hipMemcpyAsync(out_rho, F.rho, (size_t)m * 4, hipMemcpyDeviceToHost, s));
+    if (out_vel) HIP_TRY(h, hipMemcpyAsync(out_vel, F.grad, (size_t)m * 12, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    drain_profile(h);
+    return WS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1852,6 +1985,39 @@ ws_status ws_cast_camera(ws_handle *h, const ws_aniso_params *a, const ws_ray_pa
 {
     if (!h) return WS_ERR_INVALID_ARG;
     return cast_rays(h, a, r, true, nullptr, nullptr, 0, cam, size, out_t, out_normal);
+}
+
+// ======================================================================================
+// velocity field and tracer advection (include/wsfluid.h defines the field and the march)
+// ======================================================================================
+ws_status ws_sample_velocity_grid(ws_handle *h, const float origin[3], const float spacing[3], const uint32_t dims[3],
+                                  float *out_velocity, float *out_density)
+{
+    if (!h) return WS_ERR_INVALID_ARG;
+    if ((out_velocity || out_density || !h->slab) && (!origin || !spacing || !dims))
+        return fail(h, WS_ERR_INVALID_ARG, "velocity field: origin, spacing and dims are required");
+    float g6[6] = {0.f, 0.f, 0.f, 1.f, 1.f, 1.f};
+    const uint32_t one[3] = {1u, 1u, 1u};
+    if (origin && spacing && dims) {
+        for (int k = 0; k < 3; k++) {
+            g6[k] = origin[k];
+            g6[3 + k] = spacing[k];
+        }
+    }
+    return sample_velocity(h, nullptr, 0, g6, dims ? dims : one, out_velocity, out_density);
+}
+
+ws_status ws_sample_velocity_points(ws_handle *h, const float *xyz, uint32_t m, float *out_velocity, float *out_density)
+{
+    if (!h) return WS_ERR_INVALID_ARG;
+    return sample_velocity(h, xyz, m, nullptr, nullptr, out_velocity, out_density);
+}
+
+ws_status ws_advect_points(ws_handle *h, const ws_advect_params *a, const float *xyz, uint32_t m, float *out_xyz,
+                           float *out_velocity, float *out_density)
+{
+    if (!h) return WS_ERR_INVALID_ARG;
+    return advect_points(h, a, xyz, m, out_xyz, out_velocity, out_density);
 }
 
 // ======================================================================================

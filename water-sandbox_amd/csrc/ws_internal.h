@@ -248,6 +248,12 @@ struct ws_handle {
         float *mxyz = nullptr, *mnrm = nullptr;
         size_t code_bytes = 0, vbase_bytes = 0, bcnt_bytes = 0, bstart_bytes = 0, bstate_bytes = 0, tri_bytes = 0,
                mxyz_bytes = 0, mnrm_bytes = 0;
+        // velocity field (ws_sample_velocity_*, ws_advect_points), grow-only, allocated on the first velocity call: the
+        // velocities by id and in cell order beside spos, and on slab handles the gathered positions by id (the
+        // gather brings {position, velocity} records, split into vpos / vxyz)
+        float *vxyz = nullptr, *vpos = nullptr;
+        float4 *svel = nullptr;
+        size_t vxyz_bytes = 0, vpos_bytes = 0, svel_bytes = 0;
         // anisotropic kernels (ws_read_anisotropy, ws_sample_aniso_*, ws_extract_aniso_surface), grow-only: centres,
         // ellipsoids and neighbour counts by id, the centres' ellipsoids in their cell order (their {c, id} reuse spos)
         float *cxyz = nullptr;
@@ -411,6 +417,7 @@ void wsk_force(hipStream_t s, const WsDev &d, const uint32_t *start, const uint3
                WsMask mask, bool accel_only, const WsEventPair *ev = nullptr, WsSched sched = WsSched{});
 void wsk_gather_positions(hipStream_t s, WsSoA cur, float *out_xyz, uint32_t n);
 void wsk_gather_speeds(hipStream_t s, WsSoA cur, float *out, uint32_t n);
+void wsk_gather_velocities(hipStream_t s, WsSoA cur, float *out_xyz, uint32_t n);
 void wsk_gather_particles(hipStream_t s, const WsDev &d, WsSoA cur, WsSorted srt, const float4 *accel, bool have_step,
                           ws_particle80 *out, uint32_t n);
 // reference-layout view
@@ -429,6 +436,16 @@ void wsk_field_gather(hipStream_t s, const uint32_t *perm, const float *xyz, flo
 void wsk_field_sample(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, const float4 *smf, bool ieee,
                       bool grad_on, const float *xyz, uint32_t m, const float *grid6, const uint32_t *dims, bool bricks,
                       float *rho, float *grad);
+// velocity field (ws_sample_velocity_* / ws_advect_points): pv = n gathered {position, velocity} records by id, split
+// into pos (may be nullptr) and vel; svel = the velocities in spos' order; the sampler (vel or rho may be nullptr; grid6
+// and bricks as wsk_field_sample) and the tracer march (pts: m points in, their final positions out)
+void wsk_field_split(hipStream_t s, const float *pv, float *pos, float *vel, uint32_t n);
+void wsk_field_gather_vel(hipStream_t s, const uint32_t *perm, const float *vxyz, float4 *svel, uint32_t n);
+void wsk_velocity_sample(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, const float4 *svel, bool ieee,
+                         const float *xyz, uint32_t m, const float *grid6, const uint32_t *dims, bool bricks, float *vel,
+                         float *rho);
+void wsk_advect(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, const float4 *svel, bool ieee,
+                float *pts, uint32_t m, float dt, uint32_t substeps, float *vel, float *rho);
 // anisotropic kernels (ws_read_anisotropy / ws_sample_aniso_* / ws_extract_aniso_surface): the per-particle stage over
 // the sampler's binning of the positions (by id: centres, ellipsoids as 2 float4, neighbour counts), then the records
 // of the centres in their own cell order
@@ -472,7 +489,7 @@ void wsk_gather_slab(hipStream_t s, const WsDev &d, WsSoA cur, WsSorted srt, con
                      ws_particle80 *out, uint32_t *ids);
 void wsk_upload_positions_ids(hipStream_t s, const float *xyz_dev, const uint32_t *ids_dev, WsSoA cur, uint32_t n);
 // id-ordered global views / loads of slab handles (ws_kernels.hip "slab handles: the id-ordered GLOBAL views")
-enum { WS_PACK_POS_H = 0, WS_PACK_SPEED_H = 1, WS_PACK_RECORD_H = 2, WS_PACK_STATE_H = 3, WS_PACK_KEY_H = 4 };
+enum { WS_PACK_POS_H = 0, WS_PACK_SPEED_H = 1, WS_PACK_RECORD_H = 2, WS_PACK_STATE_H = 3, WS_PACK_KEY_H = 4, WS_PACK_POSVEL_H = 5 };
 uint32_t wsk_pack_words(int kind);  // payload words per record (the record carries one more: the particle id)
 void wsk_slab_pack(hipStream_t s, const WsDev &d, int kind, WsSoA cur, WsSorted srt, const float4 *accel, bool have_step,
                    uint32_t *out);

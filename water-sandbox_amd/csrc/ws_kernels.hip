@@ -1717,6 +1717,23 @@ void wsk_gather_speeds(hipStream_t s, WsSoA cur, float *out, uint32_t n)
     hipLaunchKernelGGL(k_gather_speeds, dim3(cdiv(n, WS_BLOCK)), dim3(WS_BLOCK), 0, s, cur, out, n);
 }
 
+// the velocities by id (ws_read_velocities; the velocity field's input)
+__global__ void __launch_bounds__(WS_BLOCK) k_gather_velocities(WsSoA cur, float *__restrict__ out, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * WS_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const float4 v = cur.vel(i);
+    const size_t id = __float_as_uint(cur.pos(i).w);
+    out[3 * id] = v.x;
+    out[3 * id + 1] = v.y;
+    out[3 * id + 2] = v.z;
+}
+
+void wsk_gather_velocities(hipStream_t s, WsSoA cur, float *out_xyz, uint32_t n)
+{
+    hipLaunchKernelGGL(k_gather_velocities, dim3(cdiv(n, WS_BLOCK)), dim3(WS_BLOCK), 0, s, cur, out_xyz, n);
+}
+
 __global__ void __launch_bounds__(WS_BLOCK) k_gather_particles(WsDev d, WsSoA cur, WsSorted srt,
                                                                const float4 *__restrict__ accel, int have_step,
                                                                ws_particle80 *__restrict__ out, uint32_t n)
@@ -2453,10 +2470,11 @@ __device__ __forceinline__ uint32_t slab_owner(const WsDev &d, const uint32_t *_
 }
 
 // payload of one gathered record (after its id word)
-enum { WS_PACK_POS = 0, WS_PACK_SPEED = 1, WS_PACK_RECORD = 2, WS_PACK_STATE = 3, WS_PACK_KEY = 4 };
+enum { WS_PACK_POS = 0, WS_PACK_SPEED = 1, WS_PACK_RECORD = 2, WS_PACK_STATE = 3, WS_PACK_KEY = 4, WS_PACK_POSVEL = 5 };
 __host__ __device__ constexpr uint32_t ws_pack_words(int kind)
 {
-    return kind == WS_PACK_POS ? 3u : kind == WS_PACK_SPEED ? 1u : kind == WS_PACK_RECORD ? 20u : kind == WS_PACK_STATE ? 9u : 1u;
+    return kind == WS_PACK_POS ? 3u : kind == WS_PACK_SPEED ? 1u : kind == WS_PACK_RECORD ? 20u : kind == WS_PACK_STATE ? 9u :
+           kind == WS_PACK_POSVEL ? 6u : 1u;
 }
 uint32_t wsk_pack_words(int kind) { return ws_pack_words(kind); }
 
@@ -2484,6 +2502,10 @@ __global__ void __launch_bounds__(WS_BLOCK) k_slab_pack(WsDev d, WsSoA cur, WsSo
     } else if constexpr (KIND == WS_PACK_SPEED) {
         const float4 v = cur.vel(i);
         f[0] = sqrtf(v.x * v.x + v.y * v.y + v.z * v.z);
+    } else if constexpr (KIND == WS_PACK_POSVEL) {  // the velocity field's input: one gather brings both
+        const float4 v = cur.vel(i);
+        f[0] = p.x; f[1] = p.y; f[2] = p.z;
+        f[3] = v.x; f[4] = v.y; f[5] = v.z;
     } else if constexpr (KIND == WS_PACK_STATE) {
         const float4 v = cur.vel(i), q = cur.pred[i];
         f[0] = p.x; f[1] = p.y; f[2] = p.z;
@@ -2518,6 +2540,7 @@ void wsk_slab_pack(hipStream_t s, const WsDev &d, int kind, WsSoA cur, WsSorted 
         case WS_PACK_SPEED: hipLaunchKernelGGL(k_slab_pack<WS_PACK_SPEED>, g, b, 0, s, d, cur, srt, accel, hs, out); break;
         case WS_PACK_RECORD: hipLaunchKernelGGL(k_slab_pack<WS_PACK_RECORD>, g, b, 0, s, d, cur, srt, accel, hs, out); break;
         case WS_PACK_STATE: hipLaunchKernelGGL(k_slab_pack<WS_PACK_STATE>, g, b, 0, s, d, cur, srt, accel, hs, out); break;
+        case WS_PACK_POSVEL: hipLaunchKernelGGL(k_slab_pack<WS_PACK_POSVEL>, g, b, 0, s, d, cur, srt, accel, hs, out); break;
         default: hipLaunchKernelGGL(k_slab_pack<WS_PACK_KEY>, g, b, 0, s, d, cur, srt, accel, hs, out); break;
     }
 }
@@ -2963,6 +2986,273 @@ void wsk_field_sample(hipStream_t s, const WsDev &d, const uint32_t *start, cons
     // in LDS, M and f loaded for accepted pairs) lost to the points form on sparse C3 at spacing h.
     if (smf) field_sample_launch(s, d, start, FieldAniso{spos, smf}, ieee, grad_on, xyz, m, grid6, dims, false, rho, grad);
     else field_sample_launch(s, d, start, FieldIso{spos}, ieee, grad_on, xyz, m, grid6, dims, bricks, rho, grad);
+}
+
+// ---------------------------------------------------------------------------------
+// velocity field and tracer advection (ws_sample_velocity_grid / _points, ws_advect_points; never inside ws_step)
+//
+// include/wsfluid.h pins the field: per accepted candidate w = the density sampler's term, rho += w, M_a += w * v_a
+// (product rounded, then the sum), u = M / rho correctly rounded where rho > 0 and +0 elsewhere.  The momentum sums
+// ride in FieldAcc's gradient lanes through field_sweep (GRAD = the momentum is wanted), so rho is the density sampler's
+// bits by construction: the same operations on the same candidates in the same order.
+// ---------------------------------------------------------------------------------
+// a slab's gathered {position, velocity} records by id (WS_PACK_POSVEL: 6 floats) as two arrays of 3 (pos may be nullptr)
+__global__ void __launch_bounds__(WS_BLOCK) k_field_split(const float *__restrict__ pv, float *__restrict__ pos,
+                                                          float *__restrict__ vel, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * WS_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const float *r = pv + 6 * (size_t)i;
+    if (pos) {
+        pos[3 * (size_t)i] = r[0];
+        pos[3 * (size_t)i + 1] = r[1];
+        pos[3 * (size_t)i + 2] = r[2];
+    }
+    vel[3 * (size_t)i] = r[3];
+    vel[3 * (size_t)i + 1] = r[4];
+    vel[3 * (size_t)i + 2] = r[5];
+}
+
+void wsk_field_split(hipStream_t s, const float *pv, float *pos, float *vel, uint32_t n)
+{
+    hipLaunchKernelGGL(k_field_split, dim3(cdiv(n, WS_BLOCK)), dim3(WS_BLOCK), 0, s, pv, pos, vel, n);
+}
+
+// k_field_gather's companion: svel[j] = velocity of particle perm[j], beside spos[j]
+__global__ void __launch_bounds__(WS_BLOCK) k_field_gather_vel(const uint32_t *__restrict__ perm, const float *__restrict__ vxyz,
+                                                               float4 *__restrict__ svel, uint32_t n)
+{
+    const uint32_t j = blockIdx.x * WS_BLOCK + threadIdx.x;
+    if (j >= n) return;
+    const size_t id = perm[j];
+    svel[j] = make_float4(vxyz[3 * id], vxyz[3 * id + 1], vxyz[3 * id + 2], 0.f);
+}
+
+void wsk_field_gather_vel(hipStream_t s, const uint32_t *perm, const float *vxyz, float4 *svel, uint32_t n)
+{
+    hipLaunchKernelGGL(k_field_gather_vel, dim3(cdiv(n, WS_BLOCK)), dim3(WS_BLOCK), 0, s, perm, vxyz, svel, n);
+}
+
+// The candidate source of the velocity field: FieldIso's positions and the velocities in the same order.  GRAD = the
+// momentum sums are wanted; they take the accumulator's gradient lanes.
+struct FieldVel {
+    const float4 *__restrict__ spos;
+    const float4 *__restrict__ svel;
+    __device__ __forceinline__ float4 at(uint32_t j) const { return spos[j]; }
+    template <bool IEEE, bool GRAD>
+    __device__ __forceinline__ void pair(const WsDev &d, uint32_t j, float, float, float, float d2, FieldAcc &a) const
+    {
+        const float w = sk_density(d, ws_sqrt<IEEE>(d2));
+        a.rho += w;
+        if constexpr (GRAD) {
+            const float4 v = svel[j];
+            a.gx += w * v.x;
+            a.gy += w * v.y;
+            a.gz += w * v.z;
+        }
+    }
+};
+
+// u = M / rho (correctly rounded whatever the handle's flags) where rho > 0, else (+0, +0, +0)
+__device__ __forceinline__ float4 field_velocity(const FieldAcc &a)
+{
+    if (!(a.rho > 0.f)) return make_float4(0.f, 0.f, 0.f, 0.f);
+    return make_float4(a.gx / a.rho, a.gy / a.rho, a.gz / a.rho, 0.f);
+}
+
+__device__ __forceinline__ void field_store3(float *__restrict__ out, size_t at, const float4 &v)
+{
+    out[3 * at] = v.x;
+    out[3 * at + 1] = v.y;
+    out[3 * at + 2] = v.z;
+}
+
+// Points form (the definition), one lane per query: the m points of xyz or (GRID) the nodes of g, x fastest.  VEL: the
+// velocity is wanted (vel != nullptr); rho may be nullptr.
+template <bool IEEE, bool VEL, bool GRID>
+__global__ void __launch_bounds__(WS_BLOCK) k_velocity_points(WsDev d, const uint32_t *__restrict__ start, FieldVel src,
+                                                              const float *__restrict__ xyz, WsFieldGrid g, uint32_t m,
+                                                              float *__restrict__ vel, float *__restrict__ rho)
+{
+    const uint32_t t = blockIdx.x * WS_BLOCK + threadIdx.x;
+    if (t >= m) return;
+    float4 o;
+    if constexpr (GRID) {
+        const uint32_t i = t % g.nx, r = t / g.nx;
+        o = field_node(g, i, r % g.ny, r / g.ny);
+    } else {
+        o = make_float4(xyz[3 * (size_t)t], xyz[3 * (size_t)t + 1], xyz[3 * (size_t)t + 2], 0.f);
+    }
+    const FieldAcc a = field_sweep<IEEE, VEL>(d, start, src, o);
+    if (rho) rho[t] = a.rho;
+    if constexpr (VEL) field_store3(vel, t, field_velocity(a));
+}
+
+// Grid form: k_field_bricks with the velocities staged beside the positions -- one wave per 4 x 4 x 4 brick of nodes, the
+// brick's support runs staged into LDS in canonical order a chunk at a time, every lane testing every staged candidate,
+// a candidate counting for a node iff it passes the distance test and lies in the node's own 27 cells: each node sums
+// the points form's terms in its order, bit-identically.  A staged candidate is 32 B here (position + cell code, and
+// the velocity), so the chunk is 256 candidates: 8 KiB of LDS per wave, what the density brick stages, and with the run
+// tables 18 one-wave workgroups per CU of 160 KiB -- the residency the density brick runs at.
+#define FBV_CHUNK 256
+
+template <bool IEEE, bool VEL>
+__global__ void __launch_bounds__(64) k_velocity_bricks(WsDev d, const uint32_t *__restrict__ start, FieldVel src, WsFieldGrid g,
+                                                        uint32_t bx_n, uint32_t by_n, float *__restrict__ vel,
+                                                        float *__restrict__ rho)
+{
+    __shared__ float4 s_q[FBV_CHUNK], s_v[VEL ? FBV_CHUNK : 1];
+    __shared__ uint32_t s_pre[FB_COLS + 1], s_b[FB_COLS];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t bid = blockIdx.x;
+    const uint32_t bi = bid % bx_n, bj = (bid / bx_n) % by_n, bk = bid / (bx_n * by_n);
+    const uint32_t i0 = bi * 4u, j0 = bj * 4u, k0 = bk * 4u;
+    const uint32_t i = i0 + (lane & 3u), j = j0 + ((lane >> 2) & 3u), k = k0 + (lane >> 4);
+    const bool valid = i < g.nx && j < g.ny && k < g.nz;
+    const float4 o = field_node(g, i, j, k);
+    // the brick's cell box from its first and last VALID node (wave-uniform)
+    const uint32_t il = min(i0 + 3u, g.nx - 1u), jl = min(j0 + 3u, g.ny - 1u), kl = min(k0 + 3u, g.nz - 1u);
+    const float4 lo = field_node(g, i0, j0, k0), hi = field_node(g, il, jl, kl);
+    const int x0 = max(field_axis_cell(d, 0, lo.x) - 1, 0), x1 = min(field_axis_cell(d, 0, hi.x) + 1, d.dim[0] - 1);
+    const int y0 = max(field_axis_cell(d, 1, lo.y) - 1, 0), y1 = min(field_axis_cell(d, 1, hi.y) + 1, d.dim[1] - 1);
+    const int z0 = max(field_axis_cell(d, 2, lo.z) - 1, 0), z1 = min(field_axis_cell(d, 2, hi.z) + 1, d.dim[2] - 1);
+    const int ny_c = y1 - y0 + 1;
+    const int ncol = (x1 - x0 + 1) * ny_c;
+    const size_t at = ((size_t)k * g.ny + j) * g.nx + i;
+    FieldAcc a = {0.f, 0.f, 0.f, 0.f};
+    if (ncol > FB_COLS) {  // (a spacing the host would not send here: take the points form, lane by lane)
+        if (valid) a = field_sweep<IEEE, VEL>(d, start, src, o);
+    } else {
+        // the runs: lane c = column c (x slower), then an exclusive scan of their lengths
+        uint32_t len = 0, b = 0;
+        if ((int)lane < ncol) {
+            const int x = x0 + (int)lane / ny_c, y = y0 + (int)lane % ny_c;
+            const uint32_t col = (uint32_t)(x * d.dim[1] + y) * (uint32_t)d.dim[2];
+            b = start[col + z0];
+            len = start[col + z1 + 1] - b;
+        }
+        const uint32_t incl = wave_incl_scan(len);
+        const uint32_t total = __shfl(incl, 63, 64);
+        if (total != 0u) {
+            s_pre[lane] = incl - len;
+            s_b[lane] = b;
+            if (lane == 0) s_pre[FB_COLS] = total;
+            const uint32_t own = (uint32_t)((field_axis_cell(d, 0, o.x) - x0) << 16 | (field_axis_cell(d, 1, o.y) - y0) << 8 |
+                                            (field_axis_cell(d, 2, o.z) - z0));
+            for (uint32_t base = 0; base < total; base += FBV_CHUNK) {
+                const uint32_t cnt = min((uint32_t)FBV_CHUNK, total - base);
+                __syncthreads();  // (the previous chunk has been consumed; s_pre / s_b are written)
+                for (uint32_t t = lane; t < cnt; t += 64u) {
+                    const uint32_t v = base + t;
+                    int lo_c = 0, hi_c = ncol - 1;  // last column whose prefix is <= v (empty columns share a prefix)
+                    while (lo_c < hi_c) {
+                        const int mid = (lo_c + hi_c + 1) >> 1;
+                        if (s_pre[mid] <= v) lo_c = mid;
+                        else hi_c = mid - 1;
+                    }
+                    const uint32_t idx = s_b[lo_c] + (v - s_pre[lo_c]);
+                    const float4 q = src.spos[idx];
+                    const uint32_t code = field_pack_cell(lo_c / ny_c, lo_c % ny_c, field_axis_cell(d, 2, q.z) - z0);
+                    s_q[t] = make_float4(q.x, q.y, q.z, __uint_as_float(code));
+                    if constexpr (VEL) s_v[t] = src.svel[idx];
+                }
+                __syncthreads();
+                for (uint32_t t = 0; t < cnt; t++) {
+                    const float4 q = s_q[t];
+                    const float ex = q.x - o.x, ey = q.y - o.y, ez = q.z - o.z;
+                    const float d2 = ex * ex + ey * ey + ez * ez;
+                    if (d2 > d.d2_accept) continue;
+                    // in the node's 27 cells: every byte of code - own lies in [0, 2] (k_field_bricks)
+                    if ((((__float_as_uint(q.w) | 0x808080u) - own) & 0xFCFCFCu) != 0x808080u) continue;
+                    const float w = sk_density(d, ws_sqrt<IEEE>(d2));
+                    a.rho += w;
+                    if constexpr (VEL) {
+                        const float4 pv = s_v[t];
+                        a.gx += w * pv.x;
+                        a.gy += w * pv.y;
+                        a.gz += w * pv.z;
+                    }
+                }
+            }
+        }
+    }
+    if (!valid) return;
+    if (rho) rho[at] = a.rho;
+    if constexpr (VEL) field_store3(vel, at, field_velocity(a));
+}
+
+// bricks: the brick kernel (grid only; the host sends grids of spacing <= h on every axis there)
+void wsk_velocity_sample(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, const float4 *svel, bool ieee,
+                         const float *xyz, uint32_t m, const float *grid6, const uint32_t *dims, bool bricks, float *vel,
+                         float *rho)
+{
+    WsFieldGrid g = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0u, 0u, 0u};
+    if (grid6) g = {grid6[0], grid6[1], grid6[2], grid6[3], grid6[4], grid6[5], dims[0], dims[1], dims[2]};
+    const FieldVel src = {spos, svel};
+    if (grid6 && bricks) {
+        const uint32_t bx = cdiv(dims[0], 4u), by = cdiv(dims[1], 4u), bz = cdiv(dims[2], 4u);
+        const dim3 bgrid(bx * by * bz);
+#define VB_LAUNCH(I, V) hipLaunchKernelGGL((k_velocity_bricks<I, V>), bgrid, dim3(64), 0, s, d, start, src, g, bx, by, vel, rho)
+        if (ieee) { if (vel) VB_LAUNCH(true, true); else VB_LAUNCH(true, false); }
+        else { if (vel) VB_LAUNCH(false, true); else VB_LAUNCH(false, false); }
+#undef VB_LAUNCH
+        return;
+    }
+    const dim3 grid(cdiv(m, WS_BLOCK));
+#define VP_LAUNCH(I, V, R) \
+    hipLaunchKernelGGL((k_velocity_points<I, V, R>), grid, dim3(WS_BLOCK), 0, s, d, start, src, xyz, g, m, vel, rho)
+    if (grid6) {
+        if (ieee) { if (vel) VP_LAUNCH(true, true, true); else VP_LAUNCH(true, false, true); }
+        else { if (vel) VP_LAUNCH(false, true, true); else VP_LAUNCH(false, false, true); }
+    } else {
+        if (ieee) { if (vel) VP_LAUNCH(true, true, false); else VP_LAUNCH(true, false, false); }
+        else { if (vel) VP_LAUNCH(false, true, false); else VP_LAUNCH(false, false, false); }
+    }
+#undef VP_LAUNCH
+}
+
+// k_advect, one lane per tracer: a plain loop of midpoint steps through the frozen field, each sample one field_sweep --
+// the points sampler's own definition, so a host that marches with ws_sample_velocity_points gets the same bits
+// (include/wsfluid.h pins every rounding).  pts holds the tracers on entry and the final positions on return; a lane
+// reads and writes its own slot only.  A tracer can leave the container or, with large velocities, reach +-inf or NaN:
+// field_axis_cell's fminf / fmaxf clamp maps any float (NaN to cell 0) into the grid, so every sweep stays in bounds.
+template <bool IEEE, bool FIELD>
+__global__ void __launch_bounds__(WS_BLOCK) k_advect(WsDev d, const uint32_t *__restrict__ start, FieldVel src, float *pts,
+                                                     uint32_t m, float dt, float hdt, uint32_t substeps,
+                                                     float *__restrict__ vel, float *__restrict__ rho)
+{
+    const uint32_t t = blockIdx.x * WS_BLOCK + threadIdx.x;
+    if (t >= m) return;
+    float4 p = make_float4(pts[3 * (size_t)t], pts[3 * (size_t)t + 1], pts[3 * (size_t)t + 2], 0.f);
+    for (uint32_t k = 0; k < substeps; k++) {
+        const FieldAcc a1 = field_sweep<IEEE, true>(d, start, src, p);
+        if (a1.rho == 0.f) break;  // in the air: the tracer stays, and would at every later substep
+        const float4 u1 = field_velocity(a1);
+        const float4 q = make_float4(p.x + hdt * u1.x, p.y + hdt * u1.y, p.z + hdt * u1.z, 0.f);
+        const FieldAcc a2 = field_sweep<IEEE, true>(d, start, src, q);
+        const float4 u2 = a2.rho == 0.f ? u1 : field_velocity(a2);  // the midpoint left the fluid: an Euler step
+        p = make_float4(p.x + dt * u2.x, p.y + dt * u2.y, p.z + dt * u2.z, 0.f);
+    }
+    field_store3(pts, t, p);
+    if constexpr (FIELD) {
+        const FieldAcc a = field_sweep<IEEE, true>(d, start, src, p);
+        if (rho) rho[t] = a.rho;
+        if (vel) field_store3(vel, t, field_velocity(a));
+    }
+}
+
+void wsk_advect(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, const float4 *svel, bool ieee,
+                float *pts, uint32_t m, float dt, uint32_t substeps, float *vel, float *rho)
+{
+    const FieldVel src = {spos, svel};
+    const float hdt = 0.5f * dt;
+    const dim3 grid(cdiv(m, WS_BLOCK));
+#define AD_LAUNCH(I, F) \
+    hipLaunchKernelGGL((k_advect<I, F>), grid, dim3(WS_BLOCK), 0, s, d, start, src, pts, m, dt, hdt, substeps, vel, rho)
+    const bool field = vel || rho;
+    if (ieee) { if (field) AD_LAUNCH(true, true); else AD_LAUNCH(true, false); }
+    else { if (field) AD_LAUNCH(false, true); else AD_LAUNCH(false, false); }
+#undef AD_LAUNCH
 }
 
 // ---------------------------------------------------------------------------------

@@ -1143,10 +1143,11 @@ ws_status slab_regrid(ws_handle *h, const ws_params *params, bool rebalance)
 // (what ws_read_positions does) and the GLOBAL single-GPU grid, so that the single-GPU binning and sampler run on the
 // whole particle set -- bit-identical to a single handle by construction.  (A ghost-layer sampler that avoids the
 // all-gather is the scale-out follow-up: DESIGN.md 8.)
-ws_status slab_field_positions(ws_handle *h, const float **xyz, WsDev *global)
+// with_vel (the velocity calls): {position, velocity} records instead, 6 floats per id, for wsk_field_split.
+ws_status slab_field_positions(ws_handle *h, const float **xyz, WsDev *global, bool with_vel)
 {
     WsSlab *S = h->slab;
-    ws_status st = slab_gather_by_id(h, WS_PACK_POS_H);
+    ws_status st = slab_gather_by_id(h, with_vel ? WS_PACK_POSVEL_H : WS_PACK_POS_H);
     if (st) return st;
     st = global_grid(&h->params, S->n_global, global);
     if (st) return fail(h, st, g_create_error.c_str());

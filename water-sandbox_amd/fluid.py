@@ -52,6 +52,7 @@ ABI_SYMBOLS = [
     "ws_sample_density_grid", "ws_sample_density_points", "ws_extract_surface",
     "ws_default_aniso_params", "ws_read_anisotropy", "ws_sample_aniso_grid", "ws_sample_aniso_points",
     "ws_extract_aniso_surface", "ws_cast_rays", "ws_cast_camera",
+    "ws_read_velocities", "ws_sample_velocity_grid", "ws_sample_velocity_points", "ws_advect_points",
 ]
 
 
@@ -94,6 +95,12 @@ class WsRayParams(C.Structure):
         ("refine", C.c_uint32),
         ("iso", C.c_float),
     ]
+
+
+class WsAdvectParams(C.Structure):
+    """ws_advect_params: the march of ws_advect_points (include/wsfluid.h)."""
+
+    _fields_ = [("dt", C.c_float), ("substeps", C.c_uint32)]
 
 
 class WsCamera(C.Structure):
@@ -205,6 +212,10 @@ def bind_library(path):
     L.ws_extract_aniso_surface.argtypes = [vp, vp, vp, vp, vp, C.c_float, u32, u32, vp, vp, vp, vp, vp]
     L.ws_cast_rays.argtypes = [vp, vp, vp, vp, vp, u32, vp, vp]
     L.ws_cast_camera.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.ws_read_velocities.argtypes = [vp, vp]
+    L.ws_sample_velocity_grid.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.ws_sample_velocity_points.argtypes = [vp, vp, u32, vp, vp]
+    L.ws_advect_points.argtypes = [vp, vp, vp, u32, vp, vp, vp]
     return L
 
 
@@ -312,6 +323,67 @@ def cast_camera(L, h, check, march, cam, size, normals=True, want=True, aniso=No
     n = np.empty((ht, wd, 3), np.float32) if normals else None
     check(L.ws_cast_camera(h, a, C.byref(march), C.byref(cam), sz.ctypes.data, t.ctypes.data, n.ctypes.data if normals else None))
     return t, n
+
+
+def read_velocities(L, h, check, n, want=True):
+    """ws_read_velocities: (n, 3) float32 in original-id order.  want=False (slab handles): contribute, return None."""
+    if not want:
+        check(L.ws_read_velocities(h, None))
+        return None
+    out = np.empty((n, 3), np.float32)
+    check(L.ws_read_velocities(h, out.ctypes.data))
+    return out
+
+
+def sample_velocity_grid(L, h, check, origin, spacing, dims, density=True, want=True):
+    """ws_sample_velocity_grid: (velocity (nz, ny, nx, 3), density (nz, ny, nx) or None); dims = (nx, ny, nz).
+    want=False (slab handles): contribute to the collective call and return (None, None)."""
+    o = np.ascontiguousarray(origin, np.float32).reshape(3)
+    sp = np.ascontiguousarray(spacing, np.float32).reshape(3)
+    d = np.ascontiguousarray(dims, np.uint32).reshape(3)
+    if not want:
+        check(L.ws_sample_velocity_grid(h, o.ctypes.data, sp.ctypes.data, d.ctypes.data, None, None))
+        return None, None
+    nx, ny, nz = (int(v) for v in d)
+    u = np.empty((nz, ny, nx, 3), np.float32)
+    rho = np.empty((nz, ny, nx), np.float32) if density else None
+    check(L.ws_sample_velocity_grid(h, o.ctypes.data, sp.ctypes.data, d.ctypes.data, u.ctypes.data,
+                                    rho.ctypes.data if density else None))
+    return u, rho
+
+
+def sample_velocity_points(L, h, check, xyz, density=True, want=True):
+    """ws_sample_velocity_points: (velocity (m, 3), density (m,) or None)."""
+    q = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    m = q.shape[0]
+    if not want:
+        check(L.ws_sample_velocity_points(h, q.ctypes.data, m, None, None))
+        return None, None
+    u = np.empty((m, 3), np.float32)
+    rho = np.empty(m, np.float32) if density else None
+    check(L.ws_sample_velocity_points(h, q.ctypes.data, m, u.ctypes.data, rho.ctypes.data if density else None))
+    return u, rho
+
+
+def advect_params(dt, substeps=1):
+    return WsAdvectParams(float(dt), int(substeps))
+
+
+def advect_points(L, h, check, march, xyz, field=False, want=True):
+    """ws_advect_points: the tracers xyz (m, 3) after march.substeps midpoint steps of march.dt through the frozen velocity
+    field: (xyz (m, 3), velocity (m, 3) or None, density (m,) or None), the last two -- the field at the final positions --
+    with field=True.  march: a WsAdvectParams.  want=False (slab handles): contribute and return (None, None, None)."""
+    q = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    m = q.shape[0]
+    if not want:
+        check(L.ws_advect_points(h, C.byref(march), q.ctypes.data, m, None, None, None))
+        return None, None, None
+    out = np.empty((m, 3), np.float32)
+    u = np.empty((m, 3), np.float32) if field else None
+    rho = np.empty(m, np.float32) if field else None
+    check(L.ws_advect_points(h, C.byref(march), q.ctypes.data, m, out.ctypes.data, u.ctypes.data if field else None,
+                             rho.ctypes.data if field else None))
+    return out, u, rho
 
 
 def extract_surface(L, h, check, origin, spacing, dims, iso, normals=True, want=True, collective=False, cap=None,
@@ -592,6 +664,29 @@ class FluidWorker:
         """The same for one ray per pixel of a size = (W, H) image seen by cam = camera(eye, forward, right, up):
         (t (H, W), normal (H, W, 3) or None)."""
         return cast_camera(self._L, self._h, self._check, march, cam, size, normals, aniso=aniso)
+
+    def read_velocities(self):
+        """The velocities in original-id order, (n, 3) float32: read_positions' companion."""
+        return read_velocities(self._L, self._h, self._check, self.n)
+
+    def sample_velocity_grid(self, origin, spacing, dims, density=False):
+        """The fluid's velocity field (the kernel-weighted mean of the particles' velocities, zero in the air) at the nodes
+        origin + (i, j, k) * spacing, dims = (nx, ny, nz): float32 (nz, ny, nx, 3); with density=True also the density
+        field (nz, ny, nx), the bits sample_density_grid returns."""
+        u, rho = sample_velocity_grid(self._L, self._h, self._check, origin, spacing, dims, density)
+        return (u, rho) if density else u
+
+    def sample_velocity_points(self, xyz, density=False):
+        """The same field at m points (xyz: (m, 3)): (m, 3), with density=True also (m,)."""
+        u, rho = sample_velocity_points(self._L, self._h, self._check, xyz, density)
+        return (u, rho) if density else u
+
+    def advect_points(self, march, xyz, field=False):
+        """Tracers (foam, dye, streamline points) carried through the frozen velocity field of the current state:
+        march = advect_params(dt, substeps).  The final positions (m, 3); with field=True (positions, velocity (m, 3),
+        density (m,)) there (include/wsfluid.h ws_advect_points has the definition)."""
+        out, u, rho = advect_points(self._L, self._h, self._check, march, xyz, field)
+        return (out, u, rho) if field else out
 
     def steps_done(self):
         return int(self._L.ws_steps_done(self._h))

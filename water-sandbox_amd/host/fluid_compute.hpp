@@ -296,6 +296,32 @@ class FluidWorker {
         return t;
     }
 
+    // The velocities in original-id order (ws_read_velocities), read_positions' companion.
+    std::vector<Vec3> read_velocities()
+    {
+        std::vector<Vec3> out(n_);
+        check(ws_read_velocities(h_, reinterpret_cast<float *>(out.data())));
+        return out;
+    }
+    // The fluid's velocity field at points (ws_sample_velocity_points): one Vec3 per point, zero in the air; with a
+    // density vector also the density field there.
+    std::vector<Vec3> sample_velocity_points(const std::vector<Vec3> &points, std::vector<float> *density = nullptr)
+    {
+        std::vector<Vec3> u(points.size());
+        if (density) density->resize(points.size());
+        check(ws_sample_velocity_points(h_, reinterpret_cast<const float *>(points.data()), (uint32_t)points.size(),
+                                        reinterpret_cast<float *>(u.data()), density ? density->data() : nullptr));
+        return u;
+    }
+    // Tracers (foam, dye, streamline points) carried through the frozen velocity field, in place: `substeps` midpoint
+    // steps of dt each (ws_advect_points; include/wsfluid.h has the march).
+    void advect_points(std::vector<Vec3> &points, float dt, uint32_t substeps = 1)
+    {
+        const ws_advect_params a = {dt, substeps};
+        float *p = reinterpret_cast<float *>(points.data());
+        check(ws_advect_points(h_, &a, p, (uint32_t)points.size(), p, nullptr, nullptr));
+    }
+
     std::vector<float> read_speeds()
     {
         std::vector<float> out(n_);

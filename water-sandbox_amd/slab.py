@@ -413,6 +413,25 @@ class SlabWorker:
         """FluidWorker.cast_camera over the GLOBAL particle set (COLLECTIVE); want=False: only contribute (None, None)."""
         return fluid.cast_camera(self._L, self._h, self._check, march, cam, size, normals, want, aniso)
 
+    def read_velocities(self, want=True):
+        """FluidWorker.read_velocities of the GLOBAL particle set (COLLECTIVE); want=False: only contribute (None)."""
+        return fluid.read_velocities(self._L, self._h, self._check, self.n_global, want)
+
+    def sample_velocity_grid(self, origin, spacing, dims, density=False, want=True):
+        """FluidWorker.sample_velocity_grid over the GLOBAL particle set (COLLECTIVE); want=False: only contribute."""
+        u, rho = fluid.sample_velocity_grid(self._L, self._h, self._check, origin, spacing, dims, density, want)
+        return (u, rho) if density else u
+
+    def sample_velocity_points(self, xyz, density=False, want=True):
+        """FluidWorker.sample_velocity_points over the GLOBAL particle set (COLLECTIVE); want=False: only contribute."""
+        u, rho = fluid.sample_velocity_points(self._L, self._h, self._check, xyz, density, want)
+        return (u, rho) if density else u
+
+    def advect_points(self, march, xyz, field=False, want=True):
+        """FluidWorker.advect_points over the GLOBAL particle set (COLLECTIVE); want=False: only contribute."""
+        out, u, rho = fluid.advect_points(self._L, self._h, self._check, march, xyz, field, want)
+        return (out, u, rho) if field else out
+
     def read_positions_begin(self, buf):
         assert buf.dtype == np.float32 and buf.shape == (self.n_global, 3) and buf.flags.c_contiguous
         self._check(self._L.ws_read_positions_begin(self._h, buf.ctypes.data))
