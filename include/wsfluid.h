@@ -640,6 +640,111 @@ ws_status ws_sample_velocity_points(ws_handle *h, const float *xyz, uint32_t m, 
 ws_status ws_advect_points(ws_handle *h, const ws_advect_params *a, const float *xyz, uint32_t m, float *out_xyz,
                            float *out_velocity, float *out_density);
 
+/* ---- whitewater: where foam, spray and bubbles are born, and how they move (no reference counterpart) --
+ * The diffuse-particle model of Ihmsen, Akinci, Akinci and Teschner, "Unified spray, foam and air bubbles for
+ * particle-based fluids" (2012), on the state the step leaves: ws_read_whitewater gives every fluid particle its
+ * potentials, ws_emit_whitewater turns them into new diffuse particles, ws_step_whitewater classifies and moves diffuse
+ * particles by one time step.  The HOST owns the diffuse particles; the library keeps none between calls.
+ * All three wait for enqueued steps, write nothing ws_step reads, recompute the sampler's binning from the current state
+ * on every call and keep their scratch in the sampler's (grow-only, freed by ws_destroy; the whitewater arrays are
+ * allocated on the first whitewater call only).  Slab handles: COLLECTIVE on the gathered global {position, velocity}
+ * set, the same bits as a single handle; a rank that passes every output NULL only contributes, and a rank validates
+ * its arguments only after the gather, so a refused rank leaves no peer waiting.
+ * Below fl() is a rounding to float; every operation is rounded once, nothing is contracted; x_j, v_j are what
+ * ws_read_positions / ws_read_velocities return for particle j; dot(a, b) = fl(fl(fl(a.x*b.x) + fl(a.y*b.y)) + fl(a.z*b.z)).
+ *
+ * ws_read_whitewater: the per-particle stage, n entries in ORIGINAL-ID order.  IEEE arithmetic whatever the handle's
+ *   flags (correctly rounded sqrt and division), as the anisotropy stage.  The candidates of particle i are those the
+ *   density sampler's sweep visits around x_i and accepts: the 27 cells of the clamped cell in increasing linear id,
+ *   ids ascending inside a cell, e = x_j - x_i, d2 = dot(e, e), rejected iff d2 > d2_accept.  d = sqrt(d2).  A candidate
+ *   at d == 0 (i itself, a coincident particle) contributes to nothing below.  All sums start at +0 and take their
+ *   terms in that order.
+ *   Pass A: g_i = the gradient ws_sample_density_points returns at x_i in its WS_FLAG_IEEE_DIVISION form;
+ *     gg = dot(g, g); nh_i = -g / sqrt(gg) per axis, (0, 0, 0) where gg == 0 -- ws_extract_surface's normal rule.
+ *   Pass B, per contributing candidate j (d > 0): xh_a = (-e_a) / d (the unit vector from j to i); w = 1 - d / h;
+ *     r_a = v_i,a - v_j,a; s = sqrt(dot(r, r));
+ *     trapped air:  if s > 0:  rh_a = r_a / s;  T_i += (s * (1 - dot(rh, xh))) * w;
+ *     crest:        m_a = -xh_a;  if dot(m, nh_i) < 0:  K_i += (1 - dot(nh_i, nh_j)) * w;
+ *     count:        c_i += 1.
+ *   After the sweep: vv = dot(v_i, v_i); E_i = 0.5 * vv; sv = sqrt(vv);
+ *     alignment a_i = dot(v_i / sv, nh_i) (each component divided first) if sv > 0, else +0.
+ *   Outputs, any of which may be NULL (all NULL: WS_ERR_INVALID_ARG on a single handle, contribute-only on a slab):
+ *     out_trapped n (T), out_crest n (K, not gated by the alignment), out_align n (a), out_energy n (E),
+ *     out_normal n*3 (nh), out_neighbours n (c).
+ *
+ * ws_emit_whitewater: new diffuse particles from the stage (which it runs itself).  With
+ *     clamp(I, lo, hi) = (fminf(I, hi) - fminf(I, lo)) / (hi - lo)                   (in [0, 1]; three roundings)
+ *     rate_i = (clamp(E_i, tau_energy) * (k_trapped * clamp(T_i, tau_trapped) + C_i)) * dt,
+ *     C_i = k_crest * clamp(K_i, tau_crest) if a_i >= crest_align, else +0,
+ *   particle i emits m_i = 0 if sv == 0 (it has no axis), else with f = floorf(rate_i + U(i, 0)): 0 unless f >= 1,
+ *   max_per_particle if f >= max_per_particle, else (uint32_t)f -- a stochastic, deterministic rounding of the rate.
+ *   Random numbers are counter-based, in 32-bit unsigned arithmetic (wrapping):
+ *     mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16;
+ *     word(i, c) = mix(mix(seed + i * 0x9E3779B9) + c);  U(i, c) = (float)(word(i, c) >> 8) * 2^-24, in [0, 1).
+ *   Counter 0 rounds the count.  Spawn k of particle i (k < m_i) owns the 18 counters from b = 1 + 18 * k:
+ *     b: U_h (the height along the axis), b + 1: U_l (the lifetime), b + 2 + 2 t and b + 3 + 2 t (t = 0 .. 7): the disc.
+ *   Axis vh_a = v_i,a / sv.  Let q be the axis of the smallest |vh_q| (the lowest axis on a tie, strict <) and
+ *     c = (0, -vh_z, vh_y) for q = x, (vh_z, 0, -vh_x) for q = y, (-vh_y, vh_x, 0) for q = z;
+ *     e1 = c / sqrt(dot(c, c)) per axis;  e2 = vh x e1: e2_x = vh_y * e1_z - vh_z * e1_y, and cyclically.
+ *   Disc point (a, b) by rejection: for t = 0 .. 7, a = 2 * U(i, b + 2 + 2 t) - 1, b likewise from the next counter;
+ *     the first t with a * a + b * b <= 1 is taken; none: (a, b) = (0, 0).  There is no trigonometry.
+ *   o_a = radius * (a * e1_a + b * e2_a);  p_a = (x_i,a + o_a) + (U_h * dt) * v_i,a;  v_a = v_i,a + o_a;
+ *   life = lifetime[0] + U_l * (lifetime[1] - lifetime[0]).
+ *   Spawns are ordered by particle id, then k (their offsets are an exclusive scan of m_i), so the order does not depend
+ *   on the launch shape or the slab count.  Counts and capacity, like snprintf (ws_extract_surface): on WS_OK
+ *   *n_emitted holds the full count; out_xyz and out_velocity (3 floats per spawn), out_life and out_source (the emitting
+ *   id, uint32_t), each of which may be NULL, are written only when the count fits max_emitted.
+ *
+ * ws_step_whitewater: m host-owned diffuse particles, one dt.  Per particle, independently of the others:
+ *   (u, rho) = the field at p exactly as ws_sample_velocity_points defines it in the HANDLE's arithmetic; c = the number
+ *   of candidates that sweep accepted (d == 0 included); g = the handle's gravity.  Then
+ *     spray  (c < spray_max):   v_a = v_a + dt * g_a;                                      p_a = p_a + dt * v_a;
+ *     bubble (c > bubble_min):  v_a = (v_a + dt * ((-buoyancy) * g_a)) + drag * (u_a - v_a);   p_a = p_a + dt * v_a;
+ *     foam   (otherwise):       v_a = u_a;  p_a = p_a + dt * u_a;  life = life - dt;
+ *   then the step's own container rule, per axis: nd = -1 * collision_damping; if p_a < ext_min_a: v_a = v_a * nd,
+ *   p_a = ext_min_a; else if p_a > ext_max_a: v_a = v_a * nd, p_a = ext_max_a.
+ *   Class: 3 (dead; the host drops it) if life <= 0 after the above, else 0 spray, 1 foam, 2 bubble.
+ *   xyz, velocity and life hold the m particles on entry; out_xyz, out_velocity, out_life receive them and may be the
+ *   same buffers; out_class holds m bytes.  Any output may be NULL, not all on a single handle.
+ * Errors: WS_ERR_INVALID_ARG (NULL handle; every output NULL on a single handle; ws_emit_whitewater: NULL e or
+ *   n_emitted on a rank that wants output, a tau pair that is not finite with 0 <= tau[0] < tau[1], a rate that is not
+ *   finite and >= 0, crest_align not finite, dt or radius not finite and > 0, lifetime not finite with
+ *   0 <= lifetime[0] <= lifetime[1], max_per_particle outside 1 .. 64; ws_step_whitewater: NULL p, xyz, velocity or life,
+ *   dt not finite and > 0, buoyancy not finite, drag outside [0, 1], m == 0 or more than 2^28, a non-finite coordinate,
+ *   velocity or life, a |coordinate| or |velocity| > 1e15); WS_ERR_UNSUPPORTED (WS_FLAG_REFERENCE_ORDER handles);
+ *   WS_ERR_OUT_OF_MEMORY (scratch allocation failed: the handle stays usable); WS_ERR_HIP on an unusable handle. */
+typedef struct ws_whitewater_emit_params {
+    float tau_trapped[2]; /* T below [0] emits nothing, above [1] at the full rate                    */
+    float tau_crest[2];   /* the same for K                                                           */
+    float tau_energy[2];  /* ... and for E, which scales both                                         */
+    float k_trapped;      /* diffuse particles per second at full trapped-air potential               */
+    float k_crest;        /* ... at full crest potential                                              */
+    float crest_align;    /* a crest counts where a_i >= this (0.6)                                   */
+    float dt;             /* the time the rates are integrated over                                   */
+    float radius;         /* radius of the spawn cylinder around x_i, along v_i                       */
+    float lifetime[2];    /* a spawn's lifetime is uniform in [[0], [1])                              */
+    uint32_t max_per_particle; /* 1 .. 64                                                             */
+    uint32_t seed;
+} ws_whitewater_emit_params;
+typedef struct ws_whitewater_step_params {
+    float dt;
+    uint32_t spray_max;   /* fewer accepted fluid neighbours than this: spray (6)                     */
+    uint32_t bubble_min;  /* more than this: a bubble (20); in between: foam                          */
+    float buoyancy;       /* k_b: bubbles accelerate by -k_b * gravity                                */
+    float drag;           /* k_d in [0, 1]: the share of (u - v) a bubble takes per step              */
+} ws_whitewater_step_params;
+/* Host-only (no device needed; WS_ERR_INVALID_ARG for NULL): taus (5, 50) (0.5, 4) (1, 25), rates 400 and 400, crest_align 0.6, dt 1/60, radius 0.1,
+ * lifetime (2, 5), max_per_particle 8, seed 0; dt 1/60, spray_max 6, bubble_min 20, buoyancy 2, drag 0.5. */
+ws_status ws_default_whitewater_emit_params(ws_whitewater_emit_params *out);
+ws_status ws_default_whitewater_step_params(ws_whitewater_step_params *out);
+ws_status ws_read_whitewater(ws_handle *h, float *out_trapped, float *out_crest, float *out_align, float *out_energy,
+                             float *out_normal, uint32_t *out_neighbours);
+ws_status ws_emit_whitewater(ws_handle *h, const ws_whitewater_emit_params *e, uint32_t max_emitted, float *out_xyz,
+                             float *out_velocity, float *out_life, uint32_t *out_source, uint32_t *n_emitted);
+ws_status ws_step_whitewater(ws_handle *h, const ws_whitewater_step_params *p, const float *xyz, const float *velocity,
+                             const float *life, uint32_t m, float *out_xyz, float *out_velocity, float *out_life,
+                             uint8_t *out_class);
+
 /* ---- introspection ------------------------------------------------------------- */
 const char *ws_last_error(ws_handle *h);
 uint32_t ws_num_particles(ws_handle *h);

@@ -657,6 +657,12 @@ void free_field(ws_handle *h, bool all)
     F.vxyz = F.vpos = nullptr;
     F.svel = nullptr;
     F.vxyz_bytes = F.vpos_bytes = F.svel_bytes = 0;
+    hipFree(F.wnrm); hipFree(F.wst); hipFree(F.wout); hipFree(F.wpt); hipFree(F.wnb); hipFree(F.wcnt); hipFree(F.woff);
+    hipFree(F.wstate);
+    F.wnrm = nullptr;
+    F.wst = F.wout = F.wpt = nullptr;
+    F.wnb = F.wcnt = F.woff = F.wstate = nullptr;
+    F.wnrm_bytes = F.wst_bytes = F.wout_bytes = F.wpt_bytes = F.wnb_bytes = F.wcnt_bytes = F.woff_bytes = F.wstate_bytes = 0;
     hipFree(F.cxyz); hipFree(F.amf); hipFree(F.smf); hipFree(F.anb);
     F.cxyz = nullptr;
     F.amf = F.smf = nullptr;
@@ -1859,6 +1865,176 @@ ws_status advect_points(ws_handle *h, const ws_advect_params *a, const float *xy
     return WS_OK;
 }
 
+// ---- whitewater (include/wsfluid.h defines the stage, the emission and the step) ----
+// The binning with velocities for a whitewater call (field_sample_device: collective on slabs, check() after the gather).
+template <class Check>
+ws_status whitewater_bin(ws_handle *h, const char *what, bool want, Check check, bool *contributed, WsDev *d)
+{
+    *contributed = false;
+    if (h->flags & WS_FLAG_REFERENCE_ORDER) return fail(h, WS_ERR_UNSUPPORTED, "whitewater: not in the reference-order validation mode");
+    if (!want && !h->slab) return fail(h, WS_ERR_INVALID_ARG, what);
+    return field_sample_device(h, nullptr, 0, nullptr, nullptr, want, false, false, check, contributed, nullptr, false, d, true);
+}
+
+// The per-particle stage into F.wst (T, K, a, E: n floats each, then the normals) and F.wnb, by id.
+ws_status whitewater_stage(ws_handle *h, const WsDev &d)
+{
+    auto &F = h->field;
+    const size_t n = F.n;
+    ws_status st;
+    if ((st = field_grow(h, &F.wnrm, &F.wnrm_bytes, n * 16))) return st;
+    if ((st = field_grow(h, &F.wst, &F.wst_bytes, n * 28))) return st;
+    if ((st = field_grow(h, &F.wnb, &F.wnb_bytes, n * 4))) return st;
+    wsk_whitewater_stage(h->stream, d, F.start, F.spos, F.svel, F.wnrm, F.wst, F.wst + n, F.wst + 2 * n, F.wst + 3 * n,
+                         F.wst + 4 * n, F.wnb, (uint32_t)n);
+    HIP_TRY(h, hipGetLastError());
+    return WS_OK;
+}
+
+ws_status read_whitewater(ws_handle *h, float *out_t, float *out_k, float *out_a, float *out_e, float *out_nrm, uint32_t *out_nb)
+{
+    WS_DEAD_CHECK(h);
+    const bool want = out_t || out_k || out_a || out_e || out_nrm || out_nb;
+    bool contributed = false;
+    WsDev d;
+    ws_status st = whitewater_bin(h, "whitewater: every output is NULL", want, []() { return WS_OK; }, &contributed, &d);
+    if (st || contributed) return st;
+    if ((st = whitewater_stage(h, d))) return st;
+    hipStream_t s = h->stream;
+    auto &F = h->field;
+    const size_t n = F.n;
+    float *const outs[4] = {out_t, out_k, out_a, out_e};
+    for (int k = 0; k < 4; k++)
+        if (outs[k]) HIP_TRY(h, hipMemcpyAsync(outs[k], F.wst + k * n, n * 4, hipMemcpyDeviceToHost, s));
+    if (out_nrm) HIP_TRY(h, hipMemcpyAsync(out_nrm, F.wst + 4 * n, n * 12, hipMemcpyDeviceToHost, s));
+    if (out_nb) HIP_TRY(h, hipMemcpyAsync(out_nb, F.wnb, n * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    drain_profile(h);
+    return WS_OK;
+}
+
+ws_status whitewater_emit_check(ws_handle *h, const ws_whitewater_emit_params *e, const uint32_t *n_emitted)
+{
+    if (!e) return fail(h, WS_ERR_INVALID_ARG, "whitewater: the emission parameters are required");
+    if (!n_emitted) return fail(h, WS_ERR_INVALID_ARG, "whitewater: n_emitted is required");
+    for (const float *tau : {e->tau_trapped, e->tau_crest, e->tau_energy})
+        if (!isfinite(tau[0]) || !isfinite(tau[1]) || !(tau[0] >= 0.0f) || !(tau[0] < tau[1]))
+            return fail(h, WS_ERR_INVALID_ARG, "whitewater: a tau pair must be finite with 0 <= tau[0] < tau[1]");
+    if (!isfinite(e->k_trapped) || !isfinite(e->k_crest) || !(e->k_trapped >= 0.0f) || !(e->k_crest >= 0.0f))
+        return fail(h, WS_ERR_INVALID_ARG, "whitewater: the rates must be finite and >= 0");
+    if (!isfinite(e->crest_align)) return fail(h, WS_ERR_INVALID_ARG, "whitewater: crest_align must be finite");
+    if (!isfinite(e->dt) || !(e->dt > 0.0f)) return fail(h, WS_ERR_INVALID_ARG, "whitewater: dt must be finite and > 0");
+    if (!isfinite(e->radius) || !(e->radius > 0.0f)) return fail(h, WS_ERR_INVALID_ARG, "whitewater: radius must be finite and > 0");
+    if (!isfinite(e->lifetime[0]) || !isfinite(e->lifetime[1]) || !(e->lifetime[0] >= 0.0f) || !(e->lifetime[0] <= e->lifetime[1]))
+        return fail(h, WS_ERR_INVALID_ARG, "whitewater: lifetime must be finite with 0 <= lifetime[0] <= lifetime[1]");
+    if (e->max_per_particle < 1u || e->max_per_particle > 64u)
+        return fail(h, WS_ERR_INVALID_ARG, "whitewater: max_per_particle must lie in 1 .. 64");
+    return WS_OK;
+}
+
+// ws_emit_whitewater: the stage, the counts by id, their scan (n + 1 entries: the last is the total), the total back to
+// the host and -- when the caller's buffers hold them -- the spawns.
+ws_status emit_whitewater(ws_handle *h, const ws_whitewater_emit_params *e, uint32_t max_emitted, float *out_xyz, float *out_vel,
+                          float *out_life, uint32_t *out_src, uint32_t *n_emitted)
+{
+    WS_DEAD_CHECK(h);
+    const bool want = out_xyz || out_vel || out_life || out_src || n_emitted;
+    bool contributed = false;
+    WsDev d;
+    ws_status st = whitewater_bin(h, "whitewater: every output is NULL", want,
+                                  [&]() { return whitewater_emit_check(h, e, n_emitted); }, &contributed, &d);
+    if (st || contributed) return st;
+    if ((st = whitewater_stage(h, d))) return st;
+    hipStream_t s = h->stream;
+    auto &F = h->field;
+    const size_t n = F.n;
+    if (n * e->max_per_particle > 0xFFFFFFFFull) return fail(h, WS_ERR_INVALID_ARG, "whitewater: n * max_per_particle exceeds 2^32 - 1");
+    const size_t words = (n + 1 + 3) & ~(size_t)3;  // whole uint4 for the scan
+    const size_t sw = (size_t)wsk_scan_state_words((uint32_t)n + 1u) * 4;
+    if ((st = field_grow(h, &F.wcnt, &F.wcnt_bytes, words * 4))) return st;
+    if ((st = field_grow(h, &F.woff, &F.woff_bytes, words * 4))) return st;
+    if ((st = field_grow(h, &F.wstate, &F.wstate_bytes, sw))) return st;
+    // (the scan's tickets number its launches on a state buffer of a fixed length: fresh state for every call)
+    HIP_TRY(h, hipMemsetAsync(F.wstate, 0, sw, s));
+    HIP_TRY(h, hipMemsetAsync(F.wcnt, 0, words * 4, s));
+    const WsWhiteEmit we = {e->tau_trapped[0], e->tau_trapped[1], e->tau_crest[0], e->tau_crest[1], e->tau_energy[0],
+                            e->tau_energy[1], e->k_trapped,     e->k_crest,      e->crest_align,  e->dt,
+                            e->radius,         e->lifetime[0],  e->lifetime[1],  e->max_per_particle, e->seed};
+    wsk_whitewater_count(s, we, F.vxyz, F.wst, F.wst + n, F.wst + 2 * n, F.wst + 3 * n, F.wcnt, (uint32_t)n);
+    wsk_scan(s, F.wcnt, F.woff, nullptr, F.wstate, (uint32_t)n + 1u, false, 0);
+    HIP_TRY(h, hipGetLastError());
+    uint32_t total = 0;
+    HIP_TRY(h, hipMemcpyAsync(&total, F.woff + n, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    *n_emitted = total;
+    if ((out_xyz || out_vel || out_life || out_src) && total != 0u && total <= max_emitted) {
+        const size_t T = total;
+        if ((st = field_grow(h, &F.wout, &F.wout_bytes, T * 32))) return st;
+        float *xyz = F.wout, *vel = F.wout + 3 * T, *life = F.wout + 6 * T;
+        uint32_t *src = reinterpret_cast<uint32_t *>(F.wout + 7 * T);
+        wsk_whitewater_spawn(s, we, h->slab ? F.vpos : F.xyz, F.vxyz, F.wcnt, F.woff, out_xyz ? xyz : nullptr,
+                             out_vel ? vel : nullptr, out_life ? life : nullptr, out_src ? src : nullptr, (uint32_t)n);
+        HIP_TRY(h, hipGetLastError());
+        if (out_xyz) HIP_TRY(h, hipMemcpyAsync(out_xyz, xyz, T * 12, hipMemcpyDeviceToHost, s));
+        if (out_vel) HIP_TRY(h, hipMemcpyAsync(out_vel, vel, T * 12, hipMemcpyDeviceToHost, s));
+        if (out_life) HIP_TRY(h, hipMemcpyAsync(out_life, life, T * 4, hipMemcpyDeviceToHost, s));
+        if (out_src) HIP_TRY(h, hipMemcpyAsync(out_src, src, T * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+    }
+    drain_profile(h);
+    return WS_OK;
+}
+
+ws_status whitewater_step_check(ws_handle *h, const ws_whitewater_step_params *p, const float *xyz, const float *vel,
+                                const float *life, uint32_t m)
+{
+    if (!p) return fail(h, WS_ERR_INVALID_ARG, "whitewater: the step parameters are required");
+    if (!isfinite(p->dt) || !(p->dt > 0.0f)) return fail(h, WS_ERR_INVALID_ARG, "whitewater: dt must be finite and > 0");
+    if (!isfinite(p->buoyancy)) return fail(h, WS_ERR_INVALID_ARG, "whitewater: buoyancy must be finite");
+    if (!(p->drag >= 0.0f && p->drag <= 1.0f)) return fail(h, WS_ERR_INVALID_ARG, "whitewater: drag must lie in [0, 1]");
+    if (!xyz || !vel || !life || m == 0u) return fail(h, WS_ERR_INVALID_ARG, "whitewater: no diffuse particles");
+    if (m > (1u << 28)) return fail(h, WS_ERR_INVALID_ARG, "whitewater: more than 2^28 diffuse particles");
+    for (size_t t = 0; t < (size_t)m * 3; t++)
+        if (!isfinite(xyz[t]) || fabsf(xyz[t]) > 1e15f || !isfinite(vel[t]) || fabsf(vel[t]) > 1e15f)
+            return fail(h, WS_ERR_INVALID_ARG, "whitewater: positions and velocities must be finite and within 1e15");
+    for (size_t t = 0; t < m; t++)
+        if (!isfinite(life[t])) return fail(h, WS_ERR_INVALID_ARG, "whitewater: lifetimes must be finite");
+    return WS_OK;
+}
+
+// ws_step_whitewater: the binning with velocities, the particles up, one kernel in place, the results out.
+ws_status step_whitewater(ws_handle *h, const ws_whitewater_step_params *p, const float *xyz, const float *vel, const float *life,
+                          uint32_t m, float *out_xyz, float *out_vel, float *out_life, uint8_t *out_class)
+{
+    WS_DEAD_CHECK(h);
+    const bool want = out_xyz || out_vel || out_life || out_class;
+    bool contributed = false;
+    WsDev d;
+    ws_status st = whitewater_bin(h, "whitewater: every output is NULL", want,
+                                  [&]() { return whitewater_step_check(h, p, xyz, vel, life, m); }, &contributed, &d);
+    if (st || contributed) return st;
+    hipStream_t s = h->stream;
+    auto &F = h->field;
+    const size_t M = m;
+    if ((st = field_grow(h, &F.wpt, &F.wpt_bytes, M * 28 + M))) return st;
+    float *dp = F.wpt, *dv = F.wpt + 3 * M, *dl = F.wpt + 6 * M;
+    uint8_t *dc = reinterpret_cast<uint8_t *>(F.wpt + 7 * M);
+    HIP_TRY(h, hipMemcpyAsync(dp, xyz, M * 12, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(dv, vel, M * 12, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(dl, life, M * 4, hipMemcpyHostToDevice, s));
+    const WsWhiteStep sp = {p->dt, p->spray_max, p->bubble_min, p->buoyancy, p->drag};
+    wsk_whitewater_step(s, d, F.start, F.spos, F.svel, h->ieee, sp, dp, dv, dl, dc, m);
+    HIP_TRY(h, hipGetLastError());
+    // (the uploads have left the caller's buffers before the kernel runs: outputs may alias inputs)
+    if (out_xyz) HIP_TRY(h, hipMemcpyAsync(out_xyz, dp, M * 12, hipMemcpyDeviceToHost, s));
+    if (out_vel) HIP_TRY(h, hipMemcpyAsync(out_vel, dv, M * 12, hipMemcpyDeviceToHost, s));
+    if (out_life) HIP_TRY(h, hipMemcpyAsync(out_life, dl, M * 4, hipMemcpyDeviceToHost, s));
+    if (out_class) HIP_TRY(h, hipMemcpyAsync(out_class, dc, M, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    drain_profile(h);
+    return WS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2018,6 +2194,59 @@ ws_status ws_advect_points(ws_handle *h, const ws_advect_params *a, const float 
 {
     if (!h) return WS_ERR_INVALID_ARG;
     return advect_points(h, a, xyz, m, out_xyz, out_velocity, out_density);
+}
+
+// ======================================================================================
+// whitewater: foam, spray and bubbles (include/wsfluid.h defines the stage, the emission and the step)
+// ======================================================================================
+ws_status ws_default_whitewater_emit_params(ws_whitewater_emit_params *out)
+{
+    if (!out) return WS_ERR_INVALID_ARG;
+    out->tau_trapped[0] = 5.0f;  out->tau_trapped[1] = 50.0f;
+    out->tau_crest[0] = 0.5f;    out->tau_crest[1] = 4.0f;
+    out->tau_energy[0] = 1.0f;   out->tau_energy[1] = 25.0f;
+    out->k_trapped = 400.0f;
+    out->k_crest = 400.0f;
+    out->crest_align = 0.6f;
+    out->dt = 1.0f / 60.0f;
+    out->radius = 0.1f;
+    out->lifetime[0] = 2.0f;     out->lifetime[1] = 5.0f;
+    out->max_per_particle = 8u;
+    out->seed = 0u;
+    return WS_OK;
+}
+
+ws_status ws_default_whitewater_step_params(ws_whitewater_step_params *out)
+{
+    if (!out) return WS_ERR_INVALID_ARG;
+    out->dt = 1.0f / 60.0f;
+    out->spray_max = 6u;
+    out->bubble_min = 20u;
+    out->buoyancy = 2.0f;
+    out->drag = 0.5f;
+    return WS_OK;
+}
+
+ws_status ws_read_whitewater(ws_handle *h, float *out_trapped, float *out_crest, float *out_align, float *out_energy,
+                             float *out_normal, uint32_t *out_neighbours)
+{
+    if (!h) return WS_ERR_INVALID_ARG;
+    return read_whitewater(h, out_trapped, out_crest, out_align, out_energy, out_normal, out_neighbours);
+}
+
+ws_status ws_emit_whitewater(ws_handle *h, const ws_whitewater_emit_params *e, uint32_t max_emitted, float *out_xyz,
+                             float *out_velocity, float *out_life, uint32_t *out_source, uint32_t *n_emitted)
+{
+    if (!h) return WS_ERR_INVALID_ARG;
+    return emit_whitewater(h, e, max_emitted, out_xyz, out_velocity, out_life, out_source, n_emitted);
+}
+
+ws_status ws_step_whitewater(ws_handle *h, const ws_whitewater_step_params *p, const float *xyz, const float *velocity,
+                             const float *life, uint32_t m, float *out_xyz, float *out_velocity, float *out_life,
+                             uint8_t *out_class)
+{
+    if (!h) return WS_ERR_INVALID_ARG;
+    return step_whitewater(h, p, xyz, velocity, life, m, out_xyz, out_velocity, out_life, out_class);
 }
 
 // ======================================================================================

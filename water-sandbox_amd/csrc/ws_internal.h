@@ -254,6 +254,15 @@ struct ws_handle {
         float *vxyz = nullptr, *vpos = nullptr;
         float4 *svel = nullptr;
         size_t vxyz_bytes = 0, vpos_bytes = 0, svel_bytes = 0;
+        // whitewater (ws_read_whitewater, ws_emit_whitewater, ws_step_whitewater), grow-only, allocated on the first
+        // whitewater call: the normals in spos' order, the stage by id (trapped, crest, align, energy, normal x 3 as one
+        // array of 7 n floats; the neighbour counts), the emission counts, their scan and its state, the spawns
+        // (xyz, velocity: 3 floats, life, source: 1 word each, as one array), a step's particles (7 floats + 1 byte each)
+        float4 *wnrm = nullptr;
+        float *wst = nullptr, *wout = nullptr, *wpt = nullptr;
+        uint32_t *wnb = nullptr, *wcnt = nullptr, *woff = nullptr, *wstate = nullptr;
+        size_t wnrm_bytes = 0, wst_bytes = 0, wout_bytes = 0, wpt_bytes = 0, wnb_bytes = 0, wcnt_bytes = 0, woff_bytes = 0,
+               wstate_bytes = 0;
         // anisotropic kernels (ws_read_anisotropy, ws_sample_aniso_*, ws_extract_aniso_surface), grow-only: centres,
         // ellipsoids and neighbour counts by id, the centres' ellipsoids in their cell order (their {c, id} reuse spos)
         float *cxyz = nullptr;
@@ -446,6 +455,27 @@ void wsk_velocity_sample(hipStream_t s, const WsDev &d, const uint32_t *start, c
                          float *rho);
 void wsk_advect(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, const float4 *svel, bool ieee,
                 float *pts, uint32_t m, float dt, uint32_t substeps, float *vel, float *rho);
+// whitewater (ws_read_whitewater / ws_emit_whitewater / ws_step_whitewater) over the velocity field's binning: the stage
+// (pass A into snrm, in spos' order; pass B by id), the emission counts by id and -- after a wsk_scan of them -- the
+// spawns (outputs may be nullptr), and one step of m diffuse particles in place (pts, vel, life; cls = m bytes)
+struct WsWhiteEmit {
+    float tt0, tt1, tc0, tc1, te0, te1, kt, kc, align, dt, radius, l0, l1;
+    uint32_t maxpp, seed;
+};
+struct WsWhiteStep {
+    float dt;
+    uint32_t spray_max, bubble_min;
+    float buoyancy, drag;
+};
+void wsk_whitewater_stage(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, const float4 *svel,
+                          float4 *snrm, float *trapped, float *crest, float *align, float *energy, float *normal, uint32_t *nb,
+                          uint32_t n);
+void wsk_whitewater_count(hipStream_t s, const WsWhiteEmit &e, const float *vxyz, const float *trapped, const float *crest,
+                          const float *align, const float *energy, uint32_t *cnt, uint32_t n);
+void wsk_whitewater_spawn(hipStream_t s, const WsWhiteEmit &e, const float *pxyz, const float *vxyz, const uint32_t *cnt,
+                          const uint32_t *off, float *out_xyz, float *out_vel, float *out_life, uint32_t *out_src, uint32_t n);
+void wsk_whitewater_step(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, const float4 *svel, bool ieee,
+                         const WsWhiteStep &sp, float *pts, float *vel, float *life, uint8_t *cls, uint32_t m);
 // anisotropic kernels (ws_read_anisotropy / ws_sample_aniso_* / ws_extract_aniso_surface): the per-particle stage over
 // the sampler's binning of the positions (by id: centres, ellipsoids as 2 float4, neighbour counts), then the records
 // of the centres in their own cell order

@@ -2808,10 +2808,11 @@ struct FieldAniso {
 
 // The definition: the 27 cells around the query's (clamped) cell, as 9 contiguous z-runs in increasing cell id.
 // start has ncells + 1 entries (start[ncells] = n).
-template <bool IEEE, bool GRAD, class Src>
-__device__ __forceinline__ FieldAcc field_sweep(const WsDev &d, const uint32_t *__restrict__ start, const Src &src, float4 o)
+// Acc: the accumulator the source's pair() adds to (FieldAcc; the whitewater sources carry lanes of their own), zeroed here.
+template <bool IEEE, bool GRAD, class Src, class Acc = FieldAcc>
+__device__ __forceinline__ Acc field_sweep(const WsDev &d, const uint32_t *__restrict__ start, const Src &src, float4 o)
 {
-    FieldAcc a = {0.f, 0.f, 0.f, 0.f};
+    Acc a = {};
     const int cx = field_axis_cell(d, 0, o.x), cy = field_axis_cell(d, 1, o.y), cz = field_axis_cell(d, 2, o.z);
     const int z0 = max(cz - 1, 0), z1 = min(cz + 1, d.dim[2] - 1);
     for (int x = max(cx - 1, 0); x <= min(cx + 1, d.dim[0] - 1); x++) {
@@ -3253,6 +3254,295 @@ void wsk_advect(hipStream_t s, const WsDev &d, const uint32_t *start, const floa
     if (ieee) { if (field) AD_LAUNCH(true, true); else AD_LAUNCH(true, false); }
     else { if (field) AD_LAUNCH(false, true); else AD_LAUNCH(false, false); }
 #undef AD_LAUNCH
+}
+
+// ---------------------------------------------------------------------------------
+// whitewater (ws_read_whitewater / ws_emit_whitewater / ws_step_whitewater; never inside ws_step)
+//
+// include/wsfluid.h pins every operation.  The per-particle stage is two kernels, one lane per particle in the sampler's
+// cell order (neighbouring lanes share candidates), each one field_sweep: k_whitewater_normals (pass A: the density
+// gradient at x_i, IEEE form, as a unit normal beside spos) and k_whitewater_stage (pass B, which needs every neighbour's
+// normal: trapped air, crest, alignment, energy, count, scattered by id).  The stage is IEEE arithmetic whatever the
+// handle's flags.  Emission: k_whitewater_count (m_i by id), k_scan over m_i, k_whitewater_spawn (one lane per emitter,
+// its spawns at its scanned offset).  k_whitewater_step: one lane per diffuse particle, the velocity field's sweep with
+// a count lane, in the handle's arithmetic.  No LDS: the candidates come through the caches, as in k_aniso / k_advect.
+// ---------------------------------------------------------------------------------
+__device__ __forceinline__ float ww_dot(float ax, float ay, float az, float bx, float by, float bz)
+{
+    return ax * bx + ay * by + az * bz;
+}
+
+__global__ void __launch_bounds__(WS_BLOCK) k_whitewater_normals(WsDev d, const uint32_t *__restrict__ start,
+                                                                 const float4 *__restrict__ spos, float4 *__restrict__ snrm,
+                                                                 uint32_t n)
+{
+    const uint32_t i = blockIdx.x * WS_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const FieldAcc g = field_sweep<true, true>(d, start, FieldIso{spos}, spos[i]);
+    const float gg = g.gx * g.gx + g.gy * g.gy + g.gz * g.gz;
+    float nx = 0.f, ny = 0.f, nz = 0.f;
+    if (gg != 0.f) {
+        const float len = sqrtf(gg);
+        nx = -g.gx / len;
+        ny = -g.gy / len;
+        nz = -g.gz / len;
+    }
+    snrm[i] = make_float4(nx, ny, nz, 0.f);
+}
+
+// Pass B's accumulator and candidate source: positions, velocities and normals in cell order, and the query particle's
+// own velocity and normal.
+struct WhiteAcc {
+    float t, k;
+    uint32_t c;
+};
+struct FieldWhite {
+    const float4 *__restrict__ spos;
+    const float4 *__restrict__ svel;
+    const float4 *__restrict__ snrm;
+    float4 vi, ni;
+    __device__ __forceinline__ float4 at(uint32_t j) const { return spos[j]; }
+    template <bool IEEE, bool GRAD>
+    __device__ __forceinline__ void pair(const WsDev &d, uint32_t j, float ex, float ey, float ez, float d2, WhiteAcc &a) const
+    {
+        const float dst = sqrtf(d2);
+        if (!(dst > 0.f)) return;  // i itself, a coincident particle
+        const float xx = -ex / dst, xy = -ey / dst, xz = -ez / dst;
+        const float w = 1.f - dst / d.h;
+        const float4 vj = svel[j];
+        const float rx = vi.x - vj.x, ry = vi.y - vj.y, rz = vi.z - vj.z;
+        const float s = sqrtf(ww_dot(rx, ry, rz, rx, ry, rz));
+        if (s > 0.f) a.t += (s * (1.f - ww_dot(rx / s, ry / s, rz / s, xx, xy, xz))) * w;
+        if (ww_dot(-xx, -xy, -xz, ni.x, ni.y, ni.z) < 0.f) {
+            const float4 nj = snrm[j];
+            a.k += (1.f - ww_dot(ni.x, ni.y, ni.z, nj.x, nj.y, nj.z)) * w;
+        }
+        a.c++;
+    }
+};
+
+// by id: trapped[n], crest[n], align[n], energy[n], normal[3 n], nb[n]
+__global__ void __launch_bounds__(WS_BLOCK) k_whitewater_stage(WsDev d, const uint32_t *__restrict__ start,
+                                                               const float4 *__restrict__ spos, const float4 *__restrict__ svel,
+                                                               const float4 *__restrict__ snrm, float *__restrict__ trapped,
+                                                               float *__restrict__ crest, float *__restrict__ align,
+                                                               float *__restrict__ energy, float *__restrict__ normal,
+                                                               uint32_t *__restrict__ nb, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * WS_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const float4 o = spos[i], v = svel[i], nh = snrm[i];
+    const size_t id = __float_as_uint(o.w);
+    const FieldWhite src = {spos, svel, snrm, v, nh};
+    const WhiteAcc a = field_sweep<true, false, FieldWhite, WhiteAcc>(d, start, src, o);
+    const float vv = ww_dot(v.x, v.y, v.z, v.x, v.y, v.z);
+    const float sv = sqrtf(vv);
+    trapped[id] = a.t;
+    crest[id] = a.k;
+    align[id] = sv > 0.f ? ww_dot(v.x / sv, v.y / sv, v.z / sv, nh.x, nh.y, nh.z) : 0.f;
+    energy[id] = 0.5f * vv;
+    nb[id] = a.c;
+    field_store3(normal, id, nh);
+}
+
+void wsk_whitewater_stage(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, const float4 *svel,
+                          float4 *snrm, float *trapped, float *crest, float *align, float *energy, float *normal, uint32_t *nb,
+                          uint32_t n)
+{
+    const dim3 grid(cdiv(n, WS_BLOCK)), block(WS_BLOCK);
+    hipLaunchKernelGGL(k_whitewater_normals, grid, block, 0, s, d, start, spos, snrm, n);
+    hipLaunchKernelGGL(k_whitewater_stage, grid, block, 0, s, d, start, spos, svel, snrm, trapped, crest, align, energy, normal,
+                       nb, n);
+}
+
+// the counter-based random numbers of the header: pure 32-bit integer arithmetic
+__device__ __forceinline__ uint32_t ww_mix(uint32_t x)
+{
+    x ^= x >> 16;
+    x *= 0x7feb352du;
+    x ^= x >> 15;
+    x *= 0x846ca68bu;
+    x ^= x >> 16;
+    return x;
+}
+__device__ __forceinline__ float ww_uniform(uint32_t seed, uint32_t id, uint32_t c)
+{
+    const uint32_t word = ww_mix(ww_mix(seed + id * 0x9E3779B9u) + c);
+    return (float)(word >> 8) * 0x1p-24f;
+}
+__device__ __forceinline__ float ww_clamp(float v, float lo, float hi) { return (fminf(v, hi) - fminf(v, lo)) / (hi - lo); }
+
+// m_i by id: the stochastic rounding of the emission rate
+__global__ void __launch_bounds__(WS_BLOCK) k_whitewater_count(WsWhiteEmit e, const float *__restrict__ vxyz,
+                                                               const float *__restrict__ trapped, const float *__restrict__ crest,
+                                                               const float *__restrict__ align, const float *__restrict__ energy,
+                                                               uint32_t *__restrict__ cnt, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * WS_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const float vx = vxyz[3 * (size_t)i], vy = vxyz[3 * (size_t)i + 1], vz = vxyz[3 * (size_t)i + 2];
+    const float sv = sqrtf(ww_dot(vx, vy, vz, vx, vy, vz));
+    uint32_t m = 0;
+    if (sv != 0.f) {
+        const float c = align[i] >= e.align ? e.kc * ww_clamp(crest[i], e.tc0, e.tc1) : 0.f;
+        const float rate = (ww_clamp(energy[i], e.te0, e.te1) * (e.kt * ww_clamp(trapped[i], e.tt0, e.tt1) + c)) * e.dt;
+        const float f = floorf(rate + ww_uniform(e.seed, i, 0u));
+        if (f >= (float)e.maxpp) m = e.maxpp;
+        else if (f >= 1.f) m = (uint32_t)f;
+    }
+    cnt[i] = m;
+}
+
+// One lane per emitter: its cnt[i] spawns at off[i] .. (ids ascending, then k).  Outputs may be nullptr.
+__global__ void __launch_bounds__(WS_BLOCK) k_whitewater_spawn(WsWhiteEmit e, const float *__restrict__ pxyz,
+                                                               const float *__restrict__ vxyz, const uint32_t *__restrict__ cnt,
+                                                               const uint32_t *__restrict__ off, float *__restrict__ out_xyz,
+                                                               float *__restrict__ out_vel, float *__restrict__ out_life,
+                                                               uint32_t *__restrict__ out_src, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * WS_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t m = cnt[i];
+    if (m == 0u) return;
+    const float px = pxyz[3 * (size_t)i], py = pxyz[3 * (size_t)i + 1], pz = pxyz[3 * (size_t)i + 2];
+    const float vx = vxyz[3 * (size_t)i], vy = vxyz[3 * (size_t)i + 1], vz = vxyz[3 * (size_t)i + 2];
+    const float sv = sqrtf(ww_dot(vx, vy, vz, vx, vy, vz));
+    const float hx = vx / sv, hy = vy / sv, hz = vz / sv;
+    // e1 from the axis of the smallest |component| (lowest axis on a tie), e2 = vh x e1
+    const float ax = fabsf(hx), ay = fabsf(hy), az = fabsf(hz);
+    int q = 0;
+    float least = ax;
+    if (ay < least) { q = 1; least = ay; }
+    if (az < least) q = 2;
+    float cx, cy, cz;
+    if (q == 0) { cx = 0.f; cy = -hz; cz = hy; }
+    else if (q == 1) { cx = hz; cy = 0.f; cz = -hx; }
+    else { cx = -hy; cy = hx; cz = 0.f; }
+    const float cl = sqrtf(ww_dot(cx, cy, cz, cx, cy, cz));
+    const float e1x = cx / cl, e1y = cy / cl, e1z = cz / cl;
+    const float e2x = hy * e1z - hz * e1y, e2y = hz * e1x - hx * e1z, e2z = hx * e1y - hy * e1x;
+    const float span = e.l1 - e.l0;
+    const size_t first = off[i];
+    for (uint32_t k = 0; k < m; k++) {
+        const uint32_t b = 1u + 18u * k;
+        const float uh = ww_uniform(e.seed, i, b), ul = ww_uniform(e.seed, i, b + 1u);
+        float da = 0.f, db = 0.f;
+        for (uint32_t t = 0; t < 8u; t++) {
+            const float a = 2.f * ww_uniform(e.seed, i, b + 2u + 2u * t) - 1.f;
+            const float c = 2.f * ww_uniform(e.seed, i, b + 3u + 2u * t) - 1.f;
+            if (a * a + c * c <= 1.f) {
+                da = a;
+                db = c;
+                break;
+            }
+        }
+        const float ox = e.radius * (da * e1x + db * e2x);
+        const float oy = e.radius * (da * e1y + db * e2y);
+        const float oz = e.radius * (da * e1z + db * e2z);
+        const float along = uh * e.dt;
+        const size_t at = first + k;
+        if (out_xyz) field_store3(out_xyz, at, make_float4((px + ox) + along * vx, (py + oy) + along * vy, (pz + oz) + along * vz, 0.f));
+        if (out_vel) field_store3(out_vel, at, make_float4(vx + ox, vy + oy, vz + oz, 0.f));
+        if (out_life) out_life[at] = e.l0 + ul * span;
+        if (out_src) out_src[at] = i;
+    }
+}
+
+void wsk_whitewater_count(hipStream_t s, const WsWhiteEmit &e, const float *vxyz, const float *trapped, const float *crest,
+                          const float *align, const float *energy, uint32_t *cnt, uint32_t n)
+{
+    hipLaunchKernelGGL(k_whitewater_count, dim3(cdiv(n, WS_BLOCK)), dim3(WS_BLOCK), 0, s, e, vxyz, trapped, crest, align, energy,
+                       cnt, n);
+}
+
+void wsk_whitewater_spawn(hipStream_t s, const WsWhiteEmit &e, const float *pxyz, const float *vxyz, const uint32_t *cnt,
+                          const uint32_t *off, float *out_xyz, float *out_vel, float *out_life, uint32_t *out_src, uint32_t n)
+{
+    hipLaunchKernelGGL(k_whitewater_spawn, dim3(cdiv(n, WS_BLOCK)), dim3(WS_BLOCK), 0, s, e, pxyz, vxyz, cnt, off, out_xyz,
+                       out_vel, out_life, out_src, n);
+}
+
+// The velocity field's source with a count lane: FieldVel's terms, the same bits, and the number of accepted candidates.
+struct WhiteVelAcc {
+    float rho, gx, gy, gz;
+    uint32_t c;
+};
+struct FieldVelCount {
+    const float4 *__restrict__ spos;
+    const float4 *__restrict__ svel;
+    __device__ __forceinline__ float4 at(uint32_t j) const { return spos[j]; }
+    template <bool IEEE, bool GRAD>
+    __device__ __forceinline__ void pair(const WsDev &d, uint32_t j, float, float, float, float d2, WhiteVelAcc &a) const
+    {
+        const float w = sk_density(d, ws_sqrt<IEEE>(d2));
+        const float4 v = svel[j];
+        a.rho += w;
+        a.gx += w * v.x;
+        a.gy += w * v.y;
+        a.gz += w * v.z;
+        a.c++;
+    }
+};
+
+// One lane per diffuse particle; a lane reads and writes its own slots only (pts, vel, life in place).  A particle may
+// lie anywhere: field_axis_cell clamps any float into the grid (k_advect).
+template <bool IEEE>
+__global__ void __launch_bounds__(WS_BLOCK) k_whitewater_step(WsDev d, const uint32_t *__restrict__ start, FieldVelCount src,
+                                                              WsWhiteStep sp, float *pts, float *vel, float *life,
+                                                              uint8_t *__restrict__ cls, uint32_t m)
+{
+    const uint32_t t = blockIdx.x * WS_BLOCK + threadIdx.x;
+    if (t >= m) return;
+    float p[3] = {pts[3 * (size_t)t], pts[3 * (size_t)t + 1], pts[3 * (size_t)t + 2]};
+    float v[3] = {vel[3 * (size_t)t], vel[3 * (size_t)t + 1], vel[3 * (size_t)t + 2]};
+    float l = life[t];
+    const WhiteVelAcc a = field_sweep<IEEE, true, FieldVelCount, WhiteVelAcc>(d, start, src, make_float4(p[0], p[1], p[2], 0.f));
+    const float4 u4 = field_velocity(FieldAcc{a.rho, a.gx, a.gy, a.gz});
+    const float u[3] = {u4.x, u4.y, u4.z};
+    uint32_t kind;
+    if (a.c < sp.spray_max) {
+        kind = 0u;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            v[k] = v[k] + sp.dt * d.grav[k];
+            p[k] = p[k] + sp.dt * v[k];
+        }
+    } else if (a.c > sp.bubble_min) {
+        kind = 2u;
+        const float nb = -sp.buoyancy;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            v[k] = (v[k] + sp.dt * (nb * d.grav[k])) + sp.drag * (u[k] - v[k]);
+            p[k] = p[k] + sp.dt * v[k];
+        }
+    } else {
+        kind = 1u;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            v[k] = u[k];
+            p[k] = p[k] + sp.dt * u[k];
+        }
+        l = l - sp.dt;
+    }
+    const float nd = -1.f * d.damping;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        if (p[k] < d.ext_min[k]) { v[k] *= nd; p[k] = d.ext_min[k]; } else if (p[k] > d.ext_max[k]) { v[k] *= nd; p[k] = d.ext_max[k]; }
+    }
+    if (l <= 0.f) kind = 3u;
+    field_store3(pts, t, make_float4(p[0], p[1], p[2], 0.f));
+    field_store3(vel, t, make_float4(v[0], v[1], v[2], 0.f));
+    life[t] = l;
+    cls[t] = (uint8_t)kind;
+}
+
+void wsk_whitewater_step(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, const float4 *svel, bool ieee,
+                         const WsWhiteStep &sp, float *pts, float *vel, float *life, uint8_t *cls, uint32_t m)
+{
+    const FieldVelCount src = {spos, svel};
+    const dim3 grid(cdiv(m, WS_BLOCK)), block(WS_BLOCK);
+    if (ieee) hipLaunchKernelGGL(k_whitewater_step<true>, grid, block, 0, s, d, start, src, sp, pts, vel, life, cls, m);
+    else hipLaunchKernelGGL(k_whitewater_step<false>, grid, block, 0, s, d, start, src, sp, pts, vel, life, cls, m);
 }
 
 // ---------------------------------------------------------------------------------

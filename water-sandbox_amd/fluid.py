@@ -53,6 +53,8 @@ ABI_SYMBOLS = [
     "ws_default_aniso_params", "ws_read_anisotropy", "ws_sample_aniso_grid", "ws_sample_aniso_points",
     "ws_extract_aniso_surface", "ws_cast_rays", "ws_cast_camera",
     "ws_read_velocities", "ws_sample_velocity_grid", "ws_sample_velocity_points", "ws_advect_points",
+    "ws_default_whitewater_emit_params", "ws_default_whitewater_step_params", "ws_read_whitewater", "ws_emit_whitewater",
+    "ws_step_whitewater",
 ]
 
 
@@ -101,6 +103,36 @@ class WsAdvectParams(C.Structure):
     """ws_advect_params: the march of ws_advect_points (include/wsfluid.h)."""
 
     _fields_ = [("dt", C.c_float), ("substeps", C.c_uint32)]
+
+
+class WsWhitewaterEmitParams(C.Structure):
+    """ws_whitewater_emit_params: thresholds, rates and the spawn cylinder of ws_emit_whitewater (include/wsfluid.h)."""
+
+    _fields_ = [
+        ("tau_trapped", C.c_float * 2),
+        ("tau_crest", C.c_float * 2),
+        ("tau_energy", C.c_float * 2),
+        ("k_trapped", C.c_float),
+        ("k_crest", C.c_float),
+        ("crest_align", C.c_float),
+        ("dt", C.c_float),
+        ("radius", C.c_float),
+        ("lifetime", C.c_float * 2),
+        ("max_per_particle", C.c_uint32),
+        ("seed", C.c_uint32),
+    ]
+
+
+class WsWhitewaterStepParams(C.Structure):
+    """ws_whitewater_step_params: the classes and forces of ws_step_whitewater (include/wsfluid.h)."""
+
+    _fields_ = [
+        ("dt", C.c_float),
+        ("spray_max", C.c_uint32),
+        ("bubble_min", C.c_uint32),
+        ("buoyancy", C.c_float),
+        ("drag", C.c_float),
+    ]
 
 
 class WsCamera(C.Structure):
@@ -216,6 +248,11 @@ def bind_library(path):
     L.ws_sample_velocity_grid.argtypes = [vp, vp, vp, vp, vp, vp]
     L.ws_sample_velocity_points.argtypes = [vp, vp, u32, vp, vp]
     L.ws_advect_points.argtypes = [vp, vp, vp, u32, vp, vp, vp]
+    L.ws_default_whitewater_emit_params.argtypes = [vp]
+    L.ws_default_whitewater_step_params.argtypes = [vp]
+    L.ws_read_whitewater.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.ws_emit_whitewater.argtypes = [vp, vp, u32, vp, vp, vp, vp, vp]
+    L.ws_step_whitewater.argtypes = [vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]
     return L
 
 
@@ -384,6 +421,90 @@ def advect_points(L, h, check, march, xyz, field=False, want=True):
     check(L.ws_advect_points(h, C.byref(march), q.ctypes.data, m, out.ctypes.data, u.ctypes.data if field else None,
                              rho.ctypes.data if field else None))
     return out, u, rho
+
+
+def _whitewater_params(cls, default, fields):
+    p = cls()
+    status = default(C.byref(p))
+    assert status == 0, status
+    for k, v in fields.items():
+        cur = getattr(p, k)  # (an unknown name raises)
+        if isinstance(cur, C.Array):
+            for t, x in enumerate(v):
+                cur[t] = x
+        else:
+            setattr(p, k, v)
+    return p
+
+
+def whitewater_emit_params(**fields):
+    """ws_default_whitewater_emit_params with the given fields replaced (tau_trapped=(lo, hi), seed=7, ...)."""
+    return _whitewater_params(WsWhitewaterEmitParams, load_library().ws_default_whitewater_emit_params, fields)
+
+
+def whitewater_step_params(**fields):
+    """ws_default_whitewater_step_params with the given fields replaced."""
+    return _whitewater_params(WsWhitewaterStepParams, load_library().ws_default_whitewater_step_params, fields)
+
+
+def read_whitewater(L, h, check, n, want=True):
+    """ws_read_whitewater: a dict of the stage by id -- trapped, crest, align, energy (n,) float32, normal (n, 3),
+    neighbours (n,) uint32.  want=False (slab handles): contribute, return None."""
+    if not want:
+        check(L.ws_read_whitewater(h, None, None, None, None, None, None))
+        return None
+    out = {k: np.empty(n, np.float32) for k in ("trapped", "crest", "align", "energy")}
+    out["normal"] = np.empty((n, 3), np.float32)
+    out["neighbours"] = np.empty(n, np.uint32)
+    check(L.ws_read_whitewater(h, *(out[k].ctypes.data for k in ("trapped", "crest", "align", "energy", "normal",
+                                                                  "neighbours"))))
+    return out
+
+
+def emit_whitewater(L, h, check, emit, cap=None, want=True):
+    """ws_emit_whitewater: a dict of the new diffuse particles -- xyz, velocity (k, 3) float32, life (k,), source (k,)
+    uint32 (the emitting particle's id), count = k.  cap: the capacity offered; None asks for the count first.  When the
+    count exceeds cap the arrays are None and count says what to offer.  want=False (slab handles): contribute."""
+    if not want:
+        check(L.ws_emit_whitewater(h, C.byref(emit), 0, None, None, None, None, None))
+        return None
+    k = C.c_uint32(0)
+    if cap is None:
+        check(L.ws_emit_whitewater(h, C.byref(emit), 0, None, None, None, None, C.byref(k)))
+        cap = k.value
+    xyz = np.empty((cap, 3), np.float32)
+    vel = np.empty((cap, 3), np.float32)
+    life = np.empty(cap, np.float32)
+    src = np.empty(cap, np.uint32)
+    check(L.ws_emit_whitewater(h, C.byref(emit), cap, xyz.ctypes.data, vel.ctypes.data, life.ctypes.data, src.ctypes.data,
+                               C.byref(k)))
+    if k.value > cap:
+        return dict(xyz=None, velocity=None, life=None, source=None, count=k.value)
+    return dict(xyz=xyz[:k.value], velocity=vel[:k.value], life=life[:k.value], source=src[:k.value], count=k.value)
+
+
+def step_whitewater(L, h, check, step, xyz, velocity, life, in_place=False, want=True):
+    """ws_step_whitewater: (xyz (m, 3), velocity (m, 3), life (m,), class (m,) uint8: 0 spray, 1 foam, 2 bubble, 3 dead)
+    after one step.dt.  in_place: xyz, velocity and life must be contiguous float32 arrays and are overwritten (and
+    returned).  want=False (slab handles): contribute and return None."""
+    if in_place:
+        for a in (xyz, velocity, life):
+            assert a.dtype == np.float32 and a.flags.c_contiguous
+        p, v, l = xyz.reshape(-1, 3), velocity.reshape(-1, 3), life.reshape(-1)
+    else:
+        p = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        v = np.ascontiguousarray(velocity, np.float32).reshape(-1, 3)
+        l = np.ascontiguousarray(life, np.float32).reshape(-1)
+    m = p.shape[0]
+    assert v.shape[0] == m and l.shape[0] == m
+    if not want:
+        check(L.ws_step_whitewater(h, C.byref(step), p.ctypes.data, v.ctypes.data, l.ctypes.data, m, None, None, None, None))
+        return None
+    op, ov, ol = (p, v, l) if in_place else (np.empty_like(p), np.empty_like(v), np.empty_like(l))
+    cls = np.empty(m, np.uint8)
+    check(L.ws_step_whitewater(h, C.byref(step), p.ctypes.data, v.ctypes.data, l.ctypes.data, m, op.ctypes.data,
+                               ov.ctypes.data, ol.ctypes.data, cls.ctypes.data))
+    return op, ov, ol, cls
 
 
 def extract_surface(L, h, check, origin, spacing, dims, iso, normals=True, want=True, collective=False, cap=None,
@@ -687,6 +808,22 @@ class FluidWorker:
         density (m,)) there (include/wsfluid.h ws_advect_points has the definition)."""
         out, u, rho = advect_points(self._L, self._h, self._check, march, xyz, field)
         return (out, u, rho) if field else out
+
+    def read_whitewater(self):
+        """The whitewater potentials of every fluid particle, by id (Ihmsen et al. 2012): a dict of trapped (trapped-air
+        potential), crest (wave-crest curvature), align (velocity . normal), energy (kinetic, per unit mass), normal
+        (n, 3) and neighbours (include/wsfluid.h ws_read_whitewater has the definition)."""
+        return read_whitewater(self._L, self._h, self._check, self.n)
+
+    def emit_whitewater(self, emit, cap=None):
+        """New diffuse particles born from the current state: emit = whitewater_emit_params(...).  A dict of xyz,
+        velocity, life, source and count; with a cap that is too small the arrays are None and count says what to offer."""
+        return emit_whitewater(self._L, self._h, self._check, emit, cap)
+
+    def step_whitewater(self, step, xyz, velocity, life, in_place=False):
+        """Classify the host's diffuse particles against the current fluid (spray / foam / bubble / dead) and move them by
+        step.dt: step = whitewater_step_params(...).  (xyz, velocity, life, class)."""
+        return step_whitewater(self._L, self._h, self._check, step, xyz, velocity, life, in_place)
 
     def steps_done(self):
         return int(self._L.ws_steps_done(self._h))

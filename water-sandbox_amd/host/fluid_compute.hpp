@@ -322,6 +322,36 @@ class FluidWorker {
         check(ws_advect_points(h_, &a, p, (uint32_t)points.size(), p, nullptr, nullptr));
     }
 
+    // Whitewater (include/wsfluid.h: Ihmsen et al. 2012).  The host owns the diffuse particles.
+    struct Diffuse {
+        std::vector<Vec3> xyz, velocity;
+        std::vector<float> life;
+        std::vector<uint8_t> kind;  // 0 spray, 1 foam, 2 bubble, 3 dead (after step_whitewater)
+    };
+    // New diffuse particles born from the current state (ws_emit_whitewater), appended to `into`; returns how many.
+    uint32_t emit_whitewater(const ws_whitewater_emit_params &e, Diffuse &into)
+    {
+        uint32_t k = 0;
+        check(ws_emit_whitewater(h_, &e, 0, nullptr, nullptr, nullptr, nullptr, &k));
+        const size_t at = into.xyz.size();
+        into.xyz.resize(at + k);
+        into.velocity.resize(at + k);
+        into.life.resize(at + k);
+        into.kind.resize(at + k, 0);
+        if (k)
+            check(ws_emit_whitewater(h_, &e, k, reinterpret_cast<float *>(into.xyz.data() + at),
+                                     reinterpret_cast<float *>(into.velocity.data() + at), into.life.data() + at, nullptr, &k));
+        return k;
+    }
+    // Classify and move the diffuse particles by one p.dt, in place (ws_step_whitewater); the caller drops kind == 3.
+    void step_whitewater(const ws_whitewater_step_params &p, Diffuse &d)
+    {
+        if (d.xyz.empty()) return;
+        d.kind.resize(d.xyz.size());
+        float *x = reinterpret_cast<float *>(d.xyz.data()), *v = reinterpret_cast<float *>(d.velocity.data());
+        check(ws_step_whitewater(h_, &p, x, v, d.life.data(), (uint32_t)d.xyz.size(), x, v, d.life.data(), d.kind.data()));
+    }
+
     std::vector<float> read_speeds()
     {
         std::vector<float> out(n_);

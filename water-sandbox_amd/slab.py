@@ -432,6 +432,19 @@ class SlabWorker:
         out, u, rho = fluid.advect_points(self._L, self._h, self._check, march, xyz, field, want)
         return (out, u, rho) if field else out
 
+    def read_whitewater(self, want=True):
+        """FluidWorker.read_whitewater of the GLOBAL particle set (COLLECTIVE); want=False: only contribute (None)."""
+        return fluid.read_whitewater(self._L, self._h, self._check, self.n_global, want)
+
+    def emit_whitewater(self, emit, cap=None, want=True):
+        """FluidWorker.emit_whitewater over the GLOBAL particle set (COLLECTIVE: with cap=None two collective calls, the
+        count and the spawns; a contributing peer mirrors that with two calls of want=False)."""
+        return fluid.emit_whitewater(self._L, self._h, self._check, emit, cap, want)
+
+    def step_whitewater(self, step, xyz, velocity, life, in_place=False, want=True):
+        """FluidWorker.step_whitewater over the GLOBAL particle set (COLLECTIVE); want=False: only contribute (None)."""
+        return fluid.step_whitewater(self._L, self._h, self._check, step, xyz, velocity, life, in_place, want)
+
     def read_positions_begin(self, buf):
         assert buf.dtype == np.float32 and buf.shape == (self.n_global, 3) and buf.flags.c_contiguous
         self._check(self._L.ws_read_positions_begin(self._h, buf.ctypes.data))
