@@ -29,7 +29,9 @@ ws_status slab_gather_by_id(ws_handle *h, int kind);
 ws_status slab_reset(ws_handle *h, const float *pos_xyz);
 ws_status slab_write_particles(ws_handle *h, const ws_particle80 *in);
 ws_status slab_regrid(ws_handle *h, const ws_params *params, bool rebalance);
-ws_status slab_field_positions(ws_handle *h, const float **xyz, WsDev *global, bool with_vel = false);
+ws_status slab_field_positions(ws_handle *h, const float **xyz, WsDev *global, bool with_vel);
+// ws_field.inc
+void free_field(ws_handle *h);
 
 ws_status fail(ws_handle *h, ws_status st, const char *what, hipError_t e = hipSuccess)
 {
@@ -630,109 +632,6 @@ void free_particle_arrays(ws_handle *h)
     h->mask = WsMask{nullptr, 0};
 }
 
-// The density field sampler's scratch (ws_handle::field).  Per particle: 12 B positions by id (single-GPU handles),
-// 3 x 4 B keys / tentative slots / sorted ids, 16 B sorted {position, id} = 40 B; per cell: count, cursor and start
-// (4 B each) and the scan state; plus the queries and results of the largest call so far.  
-void free_field(ws_handle *h, bool all)
-{
-    auto &F = h->field;
-    hipFree(F.count); hipFree(F.cursor); hipFree(F.start); hipFree(F.bsum);
-    F.count = F.cursor = F.start = F.bsum = nullptr;
-    F.cells = 0;
-    if (!all) return;
-    hipFree(F.xyz); hipFree(F.keys); hipFree(F.tmp); hipFree(F.perm); hipFree(F.spos);
-    hipFree(F.q); hipFree(F.rho); hipFree(F.grad);
-    F.xyz = nullptr; F.keys = F.tmp = F.perm = nullptr; F.spos = nullptr;
-    F.q = F.rho = F.grad = nullptr;
-    F.n = 0;
-    F.q_bytes = F.rho_bytes = F.grad_bytes = 0;
-    hipFree(F.code); hipFree(F.vbase); hipFree(F.bcnt); hipFree(F.bstart); hipFree(F.bstate); hipFree(F.tri);
-    hipFree(F.mxyz); hipFree(F.mnrm);
-    F.code = nullptr;
-    F.vbase = F.bcnt = F.bstart = F.bstate = F.tri = nullptr;
-    F.mxyz = F.mnrm = nullptr;
-    F.code_bytes = F.vbase_bytes = F.bcnt_bytes = F.bstart_bytes = F.bstate_bytes = F.tri_bytes = 0;
-    F.mxyz_bytes = F.mnrm_bytes = 0;
-    hipFree(F.vxyz); hipFree(F.vpos); hipFree(F.svel);
-    F.vxyz = F.vpos = nullptr;
-    F.svel = nullptr;
-    F.vxyz_bytes = F.vpos_bytes = F.svel_bytes = 0;
-    hipFree(F.wnrm); hipFree(F.wst); hipFree(F.wout); hipFree(F.wpt); hipFree(F.wnb); hipFree(F.wcnt); hipFree(F.woff);
-    hipFree(F.wstate);
-    F.wnrm = nullptr;
-    F.wst = F.wout = F.wpt = nullptr;
-    F.wnb = F.wcnt = F.woff = F.wstate = nullptr;
-    F.wnrm_bytes = F.wst_bytes = F.wout_bytes = F.wpt_bytes = F.wnb_bytes = F.wcnt_bytes = F.woff_bytes = F.wstate_bytes = 0;
-    hipFree(F.cxyz); hipFree(F.amf); hipFree(F.smf); hipFree(F.anb);
-    F.cxyz = nullptr;
-    F.amf = F.smf = nullptr;
-    F.anb = nullptr;
-    F.cxyz_bytes = F.amf_bytes = F.smf_bytes = F.anb_bytes = 0;
-    hipFree(F.rays); hipFree(F.ray_t); hipFree(F.ray_n);
-    F.rays = F.ray_t = F.ray_n = nullptr;
-    F.rays_bytes = F.ray_t_bytes = F.ray_n_bytes = 0;
-}
-
-// An allocation of the sampler: a failure is WS_ERR_OUT_OF_MEMORY and leaves no sticky HIP error behind (the next
-// ws_step checks hipGetLastError), so the handle stays usable.
-ws_status field_malloc(ws_handle *h, void **p, size_t bytes)
-{
-    const hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 4));
-    if (e == hipSuccess) return WS_OK;
-    (void)hipGetLastError();
-    *p = nullptr;
-    return fail(h, WS_ERR_OUT_OF_MEMORY, "density field scratch", e);
-}
-
-template <class T>
-ws_status field_grow(ws_handle *h, T **p, size_t *have, size_t need)
-{
-    if (*have >= need) return WS_OK;
-    hipFree(*p);
-    *p = nullptr;
-    *have = 0;
-    const ws_status st = field_malloc(h, reinterpret_cast<void **>(p), need);
-    if (!st) *have = need;
-    return st;
-}
-
-ws_status field_alloc(ws_handle *h, uint32_t n, uint32_t ncells)
-{
-    auto &F = h->field;
-    ws_status st = WS_OK;
-    if (F.n != n) {
-        free_field(h, true);
-        if (!h->slab) st = field_malloc(h, reinterpret_cast<void **>(&F.xyz), (size_t)n * 12);
-        if (!st) st = field_malloc(h, reinterpret_cast<void **>(&F.keys), (size_t)n * 4);
-        if (!st) st = field_malloc(h, reinterpret_cast<void **>(&F.tmp), (size_t)n * 4);
-        if (!st) st = field_malloc(h, reinterpret_cast<void **>(&F.perm), (size_t)n * 4);
-        if (!st) st = field_malloc(h, reinterpret_cast<void **>(&F.spos), (size_t)n * 16);
-        if (st) {
-            free_field(h, true);
-            return st;
-        }
-        F.n = n;
-    }
-    if (F.cells != ncells) {  // (new handle, or a re-grid since the last sample call)
-        free_field(h, false);
-        const size_t sw = (size_t)wsk_scan_state_words(ncells) * 4;
-        st = field_malloc(h, reinterpret_cast<void **>(&F.count), (size_t)ncells * 4);
-        if (!st) st = field_malloc(h, reinterpret_cast<void **>(&F.cursor), (size_t)ncells * 4);
-        if (!st) st = field_malloc(h, reinterpret_cast<void **>(&F.start), ((size_t)ncells + 1) * 4);
-        if (!st) st = field_malloc(h, reinterpret_cast<void **>(&F.bsum), sw);
-        if (!st && hipMemsetAsync(F.bsum, 0, sw, h->stream) != hipSuccess) st = fail(h, WS_ERR_HIP, "density field scan state");
-        if (!st && hipMemcpyAsync(F.start + ncells, &n, 4, hipMemcpyHostToDevice, h->stream) != hipSuccess)
-            st = fail(h, WS_ERR_HIP, "density field cell starts");
-        if (!st && hipStreamSynchronize(h->stream) != hipSuccess) st = fail(h, WS_ERR_HIP, "density field scratch");
-        if (st) {
-            free_field(h, false);
-            return st;
-        }
-        F.cells = ncells;
-    }
-    return WS_OK;
-}
-
 void free_all(ws_handle *h)
 {
     if (h->stream) hipStreamSynchronize(h->stream);
@@ -753,7 +652,7 @@ void free_all(ws_handle *h)
     hipFree(h->stats); hipFree(h->mult); hipFree(h->stage);
     hipFree(h->v_keys); hipFree(h->v_perm); hipFree(h->v_tmp); hipFree(h->v_count);
     hipFree(h->v_cursor); hipFree(h->v_start); hipFree(h->v_bsum); hipFree(h->v_off);
-    free_field(h, true);
+    free_field(h);
 #ifdef WS_WITH_REFCHECK
     ref_free(h);
 #endif
@@ -1419,837 +1318,6 @@ ws_status ws_read_sort_view(ws_handle *h, uint32_t *keys_by_id, uint32_t *perm, 
 }
 
 // ======================================================================================
-// density field (readback / render coupling)
-// ======================================================================================
-}  // extern "C"
-
-namespace {
-
-// The query of a sample call.  grid6 = origin + spacing and dims (grid call) or nullptr (m points of xyz).
-ws_status field_check(ws_handle *h, const float *xyz, uint32_t m, const float *grid6, const uint32_t *dims)
-{
-    if (grid6) {
-        uint64_t nodes = 1;
-        for (int a = 0; a < 3; a++) {
-            if (!isfinite(grid6[a])) return fail(h, WS_ERR_INVALID_ARG, "density field: origin must be finite");
-            if (!(grid6[3 + a] > 0.0f) || !isfinite(grid6[3 + a]))
-                return fail(h, WS_ERR_INVALID_ARG, "density field: spacing must be finite and > 0");
-            if (dims[a] == 0u) return fail(h, WS_ERR_INVALID_ARG, "density field: dims must be >= 1");
-            nodes *= dims[a];
-        }
-        if (nodes > (1ull << 31)) return fail(h, WS_ERR_INVALID_ARG, "density field: more than 2^31 nodes");
-    } else {
-        if (!xyz || m == 0u) return fail(h, WS_ERR_INVALID_ARG, "density field: no points");
-        for (size_t t = 0; t < (size_t)m * 3; t++)
-            if (!isfinite(xyz[t])) return fail(h, WS_ERR_INVALID_ARG, "density field: points must be finite");
-    }
-    return WS_OK;
-}
-
-// Bin the current positions and sample the field into device scratch: F.rho (rho_on) and F.grad (grad_on), nodes x
-// fastest or the m points.  check() validates the query: before anything else on a single handle, after the collective
-// gather on a slab rank (a rank with a bad query leaves no peer waiting).  *contributed: a slab rank that wants nothing
-// took part in the gather and has nothing more to do.  The caller has checked h and its mode.
-// ap != nullptr (checked by check()): the anisotropic field -- the per-particle stage over the binned positions (F.cxyz,
-// F.amf, F.anb by id), then the centres binned the same way (F.spos, F.smf); stage_only: stop after the stage.
-// bin_out != nullptr: stop after the binning (F.start, F.spos and with ap F.smf are what a field kernel reads) and
-// return the grid the particles were binned on -- the ray calls sample with a kernel of their own.
-// vel (with bin_out, without ap): the velocities too, by id in F.vxyz and in F.spos' order in F.svel; a slab gathers
-// {position, velocity} records once and splits them.
-template <class Check>
-ws_status field_sample_device(ws_handle *h, const float *xyz, uint32_t m, const float *grid6, const uint32_t *dims,
-                              bool want, bool rho_on, bool grad_on, Check check, bool *contributed,
-                              const ws_aniso_params *ap = nullptr, bool stage_only = false, WsDev *bin_out = nullptr,
-                              bool vel = false)
-{
-    *contributed = false;
-    if (!h->slab && want) {
-        const ws_status st = check();
-        if (st) return st;
-    }
-    HIP_TRY(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    // the current positions by id, and the grid they are binned on
-    WsDev d = h->dev;
-    const float *pos = nullptr;
-    uint32_t n = h->n;
-    if (h->slab) {
-        ws_status st = slab_field_positions(h, &pos, &d, vel);
-        if (st) return st;
-        n = h->slab->n_global;
-        if (!want) {
-            HIP_TRY(h, hipStreamSynchronize(s));
-            *contributed = true;
-            return WS_OK;
-        }
-        st = check();
-        if (st) {
-            HIP_TRY(h, hipStreamSynchronize(s));
-            return st;
-        }
-    }
-    auto &F = h->field;
-    ws_status st = field_alloc(h, n, d.ncells);
-    if (st) return st;
-    if (!h->slab) {
-        wsk_gather_positions(s, h->cur, F.xyz, n);
-        pos = F.xyz;
-    }
-    if (vel) {
-        if ((st = field_grow(h, &F.vxyz, &F.vxyz_bytes, (size_t)n * 12))) return st;
-        if ((st = field_grow(h, &F.svel, &F.svel_bytes, (size_t)n * 16))) return st;
-        if (h->slab) {
-            if ((st = field_grow(h, &F.vpos, &F.vpos_bytes, (size_t)n * 12))) return st;
-            wsk_field_split(s, pos, F.vpos, F.vxyz, n);
-            pos = F.vpos;
-        } else {
-            wsk_gather_velocities(s, h->cur, F.vxyz, n);
-        }
-    }
-    // counting sort by cell, ascending id inside a cell (the sort view's passes on the sampler's own arrays)
-    wsk_field_keys(s, d, pos, F.keys, n);
-    HIP_TRY(h, hipMemsetAsync(F.count, 0, (size_t)d.ncells * 4, s));
-    wsk_view_count(s, F.keys, F.count, n);
-    wsk_scan(s, F.count, F.start, F.cursor, F.bsum, d.ncells, false, 0);
-    wsk_scatter(s, F.keys, F.cursor, F.tmp, n, nullptr);
-    wsk_view_fix(s, F.tmp, F.keys, F.start, F.perm, n);
-    wsk_field_gather(s, F.perm, pos, F.spos, n);
-    if (vel) wsk_field_gather_vel(s, F.perm, F.vxyz, F.svel, n);
-    HIP_TRY(h, hipGetLastError());
-    if (ap) {
-        if ((st = field_grow(h, &F.cxyz, &F.cxyz_bytes, (size_t)n * 12))) return st;
-        if ((st = field_grow(h, &F.amf, &F.amf_bytes, (size_t)n * 32))) return st;
-        if ((st = field_grow(h, &F.anb, &F.anb_bytes, (size_t)n * 4))) return st;
-        if (!stage_only && (st = field_grow(h, &F.smf, &F.smf_bytes, (size_t)n * 32))) return st;
-        const WsAnisoParams a = {ap->smoothing, ap->max_ratio, ap->lone_scale, ap->min_neighbours};
-        wsk_aniso(s, d, F.start, F.spos, a, F.cxyz, F.amf, F.anb, n);
-        HIP_TRY(h, hipGetLastError());
-        if (stage_only) return WS_OK;
-        // the centres, binned by the same passes (the positions' binning is consumed: the stage ran before, in order)
-        wsk_field_keys(s, d, F.cxyz, F.keys, n);
-        HIP_TRY(h, hipMemsetAsync(F.count, 0, (size_t)d.ncells * 4, s));
-        wsk_view_count(s, F.keys, F.count, n);
-        wsk_scan(s, F.count, F.start, F.cursor, F.bsum, d.ncells, false, 0);
-        wsk_scatter(s, F.keys, F.cursor, F.tmp, n, nullptr);
-        wsk_view_fix(s, F.tmp, F.keys, F.start, F.perm, n);
-        wsk_aniso_gather(s, F.perm, F.cxyz, F.amf, F.spos, F.smf, n);
-        HIP_TRY(h, hipGetLastError());
-    }
-    if (bin_out) {
-        *bin_out = d;
-        return WS_OK;
-    }
-    // queries and results
-    const uint64_t nq = grid6 ? (uint64_t)dims[0] * dims[1] * dims[2] : m;
-    if (!grid6) {
-        st = field_grow(h, &F.q, &F.q_bytes, (size_t)m * 12);
-        if (st) return st;
-        HIP_TRY(h, hipMemcpyAsync(F.q, xyz, (size_t)m * 12, hipMemcpyHostToDevice, s));
-    }
-    if (rho_on && (st = field_grow(h, &F.rho, &F.rho_bytes, (size_t)nq * 4))) return st;
-    if (grad_on && (st = field_grow(h, &F.grad, &F.grad_bytes, (size_t)nq * 12))) return st;
-    // the brick kernel from one node per cell up (spacing <= h on every axis); the points form below
-    const bool bricks = grid6 && grid6[3] <= d.h && grid6[4] <= d.h && grid6[5] <= d.h;
-    wsk_field_sample(s, d, F.start, F.spos, ap ? F.smf : nullptr, h->ieee, grad_on, F.q, (uint32_t)nq, grid6, dims, bricks,
-                     rho_on ? F.rho : nullptr, grad_on ? F.grad : nullptr);
-    HIP_TRY(h, hipGetLastError());
-    return WS_OK;
-}
-
-// The anisotropy parameters of a call (include/wsfluid.h ws_aniso_params).
-ws_status aniso_check(ws_handle *h, const ws_aniso_params *a)
-{
-    if (!a) return fail(h, WS_ERR_INVALID_ARG, "anisotropy: the parameters are required");
-    if (!isfinite(a->smoothing) || !isfinite(a->max_ratio) || !isfinite(a->lone_scale))
-        return fail(h, WS_ERR_INVALID_ARG, "anisotropy: parameters must be finite");
-    if (!(a->smoothing >= 0.0f && a->smoothing <= 1.0f)) return fail(h, WS_ERR_INVALID_ARG, "anisotropy: smoothing must lie in [0, 1]");
-    if (!(a->max_ratio >= 1.0f)) return fail(h, WS_ERR_INVALID_ARG, "anisotropy: max_ratio must be >= 1");
-    if (!(a->lone_scale > 0.0f && a->lone_scale <= 1.0f)) return fail(h, WS_ERR_INVALID_ARG, "anisotropy: lone_scale must lie in (0, 1]");
-    return WS_OK;
-}
-
-// Both sample calls, isotropic (aniso false) or anisotropic (ap): the field into device scratch, then copied out.
-ws_status sample_density(ws_handle *h, const float *xyz, uint32_t m, const float *grid6, const uint32_t *dims,
-                         float *out_rho, float *out_grad, bool aniso = false, const ws_aniso_params *ap = nullptr)
-{
-    if (!h) return WS_ERR_INVALID_ARG;
-    WS_DEAD_CHECK(h);
-    if (h->flags & WS_FLAG_REFERENCE_ORDER) return fail(h, WS_ERR_UNSUPPORTED, "density field: not in the reference-order validation mode");
-    const bool want = out_rho || out_grad;
-    if (!want && !h->slab) return fail(h, WS_ERR_INVALID_ARG, "density field: both outputs are NULL");
-    bool contributed = false;
-    auto check = [&]() -> ws_status {
-        if (aniso) {
-            const ws_status st = aniso_check(h, ap);
-            if (st) return st;
-        }
-        return field_check(h, xyz, m, grid6, dims);
-    };
-    const ws_status st = field_sample_device(h, xyz, m, grid6, dims, want, out_rho != nullptr, out_grad != nullptr, check,
-                                             &contributed, aniso ? ap : nullptr);
-    if (st || contributed) return st;
-    hipStream_t s = h->stream;
-    auto &F = h->field;
-    const uint64_t nq = grid6 ? (uint64_t)dims[0] * dims[1] * dims[2] : m;
-    if (out_rho) HIP_TRY(h, hipMemcpyAsync(out_rho, F.rho, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
-    if (out_grad) HIP_TRY(h, hipMemcpyAsync(out_grad, F.grad, (size_t)nq * 12, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    drain_profile(h);
-    return WS_OK;
-}
-
-// ws_extract_surface: the grid field into device scratch, the node codes and per-workgroup totals, their scans, the
-// counts back to the host and -- when the caller's buffers hold them -- the mesh.  query = origin, spacing and dims were
-// given (grid6 / dims hold placeholders otherwise): a slab rank without them still takes part in the gather, then fails.
-// aniso: ws_extract_aniso_surface (ap checked with the query).
-ws_status extract_surface(ws_handle *h, bool query, const float *grid6, const uint32_t *dims, float iso, uint32_t max_v,
-                          uint32_t max_t, float *out_xyz, float *out_nrm, uint32_t *out_tri, uint32_t *n_v, uint32_t *n_t,
-                          bool aniso = false, const ws_aniso_params *ap = nullptr)
-{
-    WS_DEAD_CHECK(h);
-    if (h->flags & WS_FLAG_REFERENCE_ORDER) return fail(h, WS_ERR_UNSUPPORTED, "surface: not in the reference-order validation mode");
-    const bool want = out_xyz || out_nrm || out_tri || n_v || n_t;
-    // a single handle always wants the counts (field_sample_device validates a single handle's query only if it wants)
-    if (!h->slab && (!n_v || !n_t)) return fail(h, WS_ERR_INVALID_ARG, "surface: the count pointers are required");
-    auto check = [&]() -> ws_status {
-        if (!query) return fail(h, WS_ERR_INVALID_ARG, "surface: origin, spacing and dims are required");
-        if (!n_v || !n_t) return fail(h, WS_ERR_INVALID_ARG, "surface: the count pointers are required");
-        uint64_t nodes = 1;
-        for (int a = 0; a < 3; a++) {
-            if (dims[a] < 2u) return fail(h, WS_ERR_INVALID_ARG, "surface: dims must be >= 2");
-            nodes *= dims[a];
-        }
-        if (nodes > (1ull << 28)) return fail(h, WS_ERR_INVALID_ARG, "surface: more than 2^28 nodes");
-        if (!(iso > 0.0f) || !isfinite(iso)) return fail(h, WS_ERR_INVALID_ARG, "surface: iso must be finite and > 0");
-        if (aniso) {
-            const ws_status st = aniso_check(h, ap);
-            if (st) return st;
-        }
-        return field_check(h, nullptr, 0, grid6, dims);
-    };
-    // the gradient only for a call that asks for normals and passes both mesh buffers (a call whose counts then exceed
-    // its capacities has sampled it for nothing; FluidWorker sizes its first guess from the previous mesh)
-    const bool grad_on = out_nrm && out_xyz && out_tri;
-    bool contributed = false;
-    ws_status st = field_sample_device(h, nullptr, 0, grid6, dims, want, true, grad_on, check, &contributed,
-                                       aniso ? ap : nullptr);
-    if (st || contributed) return st;
-    hipStream_t s = h->stream;
-    auto &F = h->field;
-    const size_t nodes = (size_t)dims[0] * dims[1] * dims[2];
-    const uint32_t nb = wsk_iso_blocks(dims);
-    const size_t half = ((size_t)nb + 4) & ~(size_t)3;  // nb + 1 totals, 16 B aligned for the scan's uint4 accesses
-    const size_t sw = (size_t)wsk_scan_state_words(nb + 1) * 4;
-    if ((st = field_grow(h, &F.code, &F.code_bytes, nodes))) return st;
-    if ((st = field_grow(h, &F.bcnt, &F.bcnt_bytes, 2 * half * 4))) return st;
-    if ((st = field_grow(h, &F.bstart, &F.bstart_bytes, (2 * half + 4) * 4))) return st;  // (+ the two grand totals)
-    if ((st = field_grow(h, &F.bstate, &F.bstate_bytes, sw))) return st;
-    // (the scan's tickets number its launches on a state buffer of a fixed length: fresh state for every call)
-    HIP_TRY(h, hipMemsetAsync(F.bstate, 0, sw, s));
-    wsk_iso_count(s, F.rho, grid6, dims, iso, F.code, F.bcnt, F.bcnt + half);
-    wsk_scan(s, F.bcnt, F.bstart, nullptr, F.bstate, nb + 1, false, 0);
-    wsk_scan(s, F.bcnt + half, F.bstart + half, nullptr, F.bstate, nb + 1, false, 0);
-    wsk_iso_totals(s, F.bstart + nb, F.bstart + half + nb, F.bstart + 2 * half);
-    HIP_TRY(h, hipGetLastError());
-    uint32_t counts[2] = {0u, 0u};
-    HIP_TRY(h, hipMemcpyAsync(counts, F.bstart + 2 * half, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    *n_v = counts[0];
-    *n_t = counts[1];
-    if (out_xyz && out_tri && counts[0] <= max_v && counts[1] <= max_t) {
-        const size_t V = counts[0], T = counts[1];
-        if ((st = field_grow(h, &F.vbase, &F.vbase_bytes, nodes * 4))) return st;
-        if ((st = field_grow(h, &F.mxyz, &F.mxyz_bytes, V * 12))) return st;
-        if (grad_on && (st = field_grow(h, &F.mnrm, &F.mnrm_bytes, V * 12))) return st;
-        if ((st = field_grow(h, &F.tri, &F.tri_bytes, T * 12))) return st;
-        wsk_iso_mesh(s, F.rho, F.grad, grid6, dims, iso, F.code, F.bstart, F.bstart + half, F.vbase, F.mxyz,
-                     grad_on ? F.mnrm : nullptr, F.tri);
-        HIP_TRY(h, hipGetLastError());
-        if (V) HIP_TRY(h, hipMemcpyAsync(out_xyz, F.mxyz, V * 12, hipMemcpyDeviceToHost, s));
-        if (V && grad_on) HIP_TRY(h, hipMemcpyAsync(out_nrm, F.mnrm, V * 12, hipMemcpyDeviceToHost, s));
-        if (T) HIP_TRY(h, hipMemcpyAsync(out_tri, F.tri, T * 12, hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipStreamSynchronize(s));
-    }
-    drain_profile(h);
-    return WS_OK;
-}
-
-// ws_read_anisotropy: the stage alone, copied out by id (the ellipsoids split into M and f on the host).
-ws_status read_anisotropy(ws_handle *h, const ws_aniso_params *ap, float *out_c, float *out_m, float *out_f, uint32_t *out_n)
-{
-    WS_DEAD_CHECK(h);
-    if (h->flags & WS_FLAG_REFERENCE_ORDER) return fail(h, WS_ERR_UNSUPPORTED, "anisotropy: not in the reference-order validation mode");
-    const bool want = out_c || out_m || out_f || out_n;
-    if (!want && !h->slab) return aniso_check(h, ap);
-    bool contributed = false;
-    ws_status st = field_sample_device(h, nullptr, 0, nullptr, nullptr, want, false, false, [&]() { return aniso_check(h, ap); },
-                                       &contributed, ap, true);
-    if (st || contributed) return st;
-    hipStream_t s = h->stream;
-    auto &F = h->field;
-    const size_t n = F.n;
-    if (out_c) HIP_TRY(h, hipMemcpyAsync(out_c, F.cxyz, n * 12, hipMemcpyDeviceToHost, s));
-    if (out_n) HIP_TRY(h, hipMemcpyAsync(out_n, F.anb, n * 4, hipMemcpyDeviceToHost, s));
-    std::vector<float> mf;
-    if (out_m || out_f) {
-        mf.resize(n * 8);
-        HIP_TRY(h, hipMemcpyAsync(mf.data(), F.amf, n * 32, hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(h, hipStreamSynchronize(s));
-    for (size_t i = 0; i < n && (out_m || out_f); i++) {
-        if (out_m)
-            for (int k = 0; k < 6; k++) out_m[6 * i + k] = mf[8 * i + k];
-        if (out_f) out_f[i] = mf[8 * i + 6];
-    }
-    drain_profile(h);
-    return WS_OK;
-}
-
-// The query of a ray call (include/wsfluid.h): the march, then the m rays of origin / dir or the camera and its size.
-ws_status ray_check(ws_handle *h, const ws_ray_params *r, bool camera, const float *origin, const float *dir, uint32_t m,
-                    const ws_camera *cam, const uint32_t *size)
-{
-    const float far = 1e15f;  // keeps every sample point finite: |t| * |v| <= 1e30
-    if (!r) return fail(h, WS_ERR_INVALID_ARG, "rays: the march parameters are required");
-    if (r->steps < 1u || r->steps > 65535u) return fail(h, WS_ERR_INVALID_ARG, "rays: steps must lie in 1 .. 65535");
-    if (r->refine > 24u) return fail(h, WS_ERR_INVALID_ARG, "rays: refine must be <= 24");
-    if (!isfinite(r->dt) || !(r->dt > 0.0f)) return fail(h, WS_ERR_INVALID_ARG, "rays: dt must be finite and > 0");
-    if (!isfinite(r->iso) || !(r->iso > 0.0f)) return fail(h, WS_ERR_INVALID_ARG, "rays: iso must be finite and > 0");
-    if (!isfinite(r->t_start)) return fail(h, WS_ERR_INVALID_ARG, "rays: t_start must be finite");
-    if (fabs((double)r->t_start) + (double)r->steps * (double)r->dt > (double)far)
-        return fail(h, WS_ERR_INVALID_ARG, "rays: |t_start| + steps * dt must be <= 1e15");
-    auto in_range = [&](const float *v, size_t k) {
-        for (size_t t = 0; t < k; t++)
-            if (!isfinite(v[t]) || fabsf(v[t]) > far) return false;
-        return true;
-    };
-    if (camera) {
-        if (!cam || !size) return fail(h, WS_ERR_INVALID_ARG, "rays: the camera and the image size are required");
-        if (size[0] == 0u || size[1] == 0u) return fail(h, WS_ERR_INVALID_ARG, "rays: the image size must be >= 1");
-        if ((uint64_t)size[0] * size[1] > (1ull << 28)) return fail(h, WS_ERR_INVALID_ARG, "rays: more than 2^28 rays");
-        if (!in_range(cam->eye, 3) || !in_range(cam->forward, 3) || !in_range(cam->right, 3) || !in_range(cam->up, 3))
-            return fail(h, WS_ERR_INVALID_ARG, "rays: the camera must be finite and within 1e15");
-        if (cam->forward[0] == 0.0f && cam->forward[1] == 0.0f && cam->forward[2] == 0.0f)
-            return fail(h, WS_ERR_INVALID_ARG, "rays: the camera's forward is (0, 0, 0)");
-        return WS_OK;
-    }
-    if (!origin || !dir || m == 0u) return fail(h, WS_ERR_INVALID_ARG, "rays: no rays");
-    if (m > (1u << 28)) return fail(h, WS_ERR_INVALID_ARG, "rays: more than 2^28 rays");
-    if (!in_range(origin, (size_t)m * 3) || !in_range(dir, (size_t)m * 3))
-        return fail(h, WS_ERR_INVALID_ARG, "rays: origins and directions must be finite and within 1e15");
-    for (size_t t = 0; t < m; t++)
-        if (dir[3 * t] == 0.0f && dir[3 * t + 1] == 0.0f && dir[3 * t + 2] == 0.0f)
-            return fail(h, WS_ERR_INVALID_ARG, "rays: a direction is (0, 0, 0)");
-    return WS_OK;
-}
-
-// ws_cast_rays / ws_cast_camera: the sampler's binning (with ap the stage and the centres' binning), the cast kernel,
-// the results copied out.
-ws_status cast_rays(ws_handle *h, const ws_aniso_params *ap, const ws_ray_params *r, bool camera, const float *origin,
-                    const float *dir, uint32_t m, const ws_camera *cam, const uint32_t *size, float *out_t, float *out_n)
-{
-    WS_DEAD_CHECK(h);
-    if (h->flags & WS_FLAG_REFERENCE_ORDER) return fail(h, WS_ERR_UNSUPPORTED, "rays: not in the reference-order validation mode");
-    const bool want = out_t || out_n;
-    if (!want && !h->slab) return fail(h, WS_ERR_INVALID_ARG, "rays: both outputs are NULL");
-    bool contributed = false;
-    auto check = [&]() -> ws_status {
-        if (ap) {
-            const ws_status st = aniso_check(h, ap);
-            if (st) return st;
-        }
-        return ray_check(h, r, camera, origin, dir, m, cam, size);
-    };
-    WsDev d;
-    ws_status st = field_sample_device(h, nullptr, 0, nullptr, nullptr, want, false, false, check, &contributed, ap, false, &d);
-    if (st || contributed) return st;
-    hipStream_t s = h->stream;
-    auto &F = h->field;
-    const size_t nr = camera ? (size_t)size[0] * size[1] : m;
-    if (out_t && (st = field_grow(h, &F.ray_t, &F.ray_t_bytes, nr * 4))) return st;
-    if (out_n && (st = field_grow(h, &F.ray_n, &F.ray_n_bytes, nr * 12))) return st;
-    if (!camera) {
-        if ((st = field_grow(h, &F.rays, &F.rays_bytes, nr * 24))) return st;
-        HIP_TRY(h, hipMemcpyAsync(F.rays, origin, nr * 12, hipMemcpyHostToDevice, s));
-        HIP_TRY(h, hipMemcpyAsync(F.rays + 3 * nr, dir, nr * 12, hipMemcpyHostToDevice, s));
-    }
-    wsk_ray_cast(s, d, F.start, F.spos, ap ? F.smf : nullptr, h->ieee, *r, F.rays, camera ? nullptr : F.rays + 3 * nr,
-                 (uint32_t)nr, camera ? cam : nullptr, size, out_t ? F.ray_t : nullptr, out_n ? F.ray_n : nullptr);
-    HIP_TRY(h, hipGetLastError());
-    if (out_t) HIP_TRY(h, hipMemcpyAsync(out_t, F.ray_t, nr * 4, hipMemcpyDeviceToHost, s));
-    if (out_n) HIP_TRY(h, hipMemcpyAsync(out_n, F.ray_n, nr * 12, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    drain_profile(h);
-    return WS_OK;
-}
-
-// ws_sample_velocity_grid / _points: the sampler's binning with the velocities beside the positions, the velocity
-// kernel, the results copied out.  The query is the density sampler's, errors included.
-ws_status sample_velocity(ws_handle *h, const float *xyz, uint32_t m, const float *grid6, const uint32_t *dims, float *out_vel,
-                          float *out_rho)
-{
-    WS_DEAD_CHECK(h);
-    if (h->flags & WS_FLAG_REFERENCE_ORDER) return fail(h, WS_ERR_UNSUPPORTED, "velocity field: not in the reference-order validation mode");
-    const bool want = out_vel || out_rho;
-    if (!want && !h->slab) return fail(h, WS_ERR_INVALID_ARG, "velocity field: both outputs are NULL");
-    bool contributed = false;
-    auto check = [&]() -> ws_status { return field_check(h, xyz, m, grid6, dims); };
-    WsDev d;
-    ws_status st = field_sample_device(h, nullptr, 0, nullptr, nullptr, want, false, false, check, &contributed, nullptr, false,
-                                       &d, true);
-    if (st || contributed) return st;
-    hipStream_t s = h->stream;
-    auto &F = h->field;
-    const uint64_t nq = grid6 ? (uint64_t)dims[0] * dims[1] * dims[2] : m;
-    if (!grid6) {
-        if ((st = field_grow(h, &F.q, &F.q_bytes, (size_t)m * 12))) return st;
-        HIP_TRY(h, hipMemcpyAsync(F.q, xyz, (size_t)m * 12, hipMemcpyHostToDevice, s));
-    }
-    if (out_rho && (st = field_grow(h, &F.rho, &F.rho_bytes, (size_t)nq * 4))) return st;
-    if (out_vel && (st = field_grow(h, &F.grad, &F.grad_bytes, (size_t)nq * 12))) return st;
-    // the brick kernel from one node per cell up, as the density sampler; the points form below
-    const bool bricks = grid6 && grid6[3] <= d.h && grid6[4] <= d.h && grid6[5] <= d.h;
-    wsk_velocity_sample(s, d, F.start, F.spos, F.svel, h->ieee, F.q, (uint32_t)nq, grid6, dims, bricks,
-                        out_vel ? F.grad : nullptr, out_rho ? F.rho : nullptr);
-    HIP_TRY(h, hipGetLastError());
-    if (out_rho) HIP_TRY(h, hipMemcpyAsync(out_rho, F.rho, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
-    if (out_vel) HIP_TRY(h, hipMemcpyAsync(out_vel, F.grad, (size_t)nq * 12, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    drain_profile(h);
-    return WS_OK;
-}
-
-// The query of ws_advect_points (include/wsfluid.h).
-ws_status advect_check(ws_handle *h, const ws_advect_params *a, const float *xyz, uint32_t m, const float *out_xyz)
-{
-    if (!a) return fail(h, WS_ERR_INVALID_ARG, "advection: the parameters are required");
-    if (a->substeps < 1u || a->substeps > 4096u) return fail(h, WS_ERR_INVALID_ARG, "advection: substeps must lie in 1 .. 4096");
-    if (!isfinite(a->dt) || fabsf(a->dt) > 1e6f) return fail(h, WS_ERR_INVALID_ARG, "advection: dt must be finite and within 1e6");
-    if (!xyz || m == 0u) return fail(h, WS_ERR_INVALID_ARG, "advection: no points");
-    if (m > (1u << 28)) return fail(h, WS_ERR_INVALID_ARG, "advection: more than 2^28 points");
-    if (!out_xyz) return fail(h, WS_ERR_INVALID_ARG, "advection: out_xyz is required");
-    for (size_t t = 0; t < (size_t)m * 3; t++)
-        if (!isfinite(xyz[t]) || fabsf(xyz[t]) > 1e15f)
-            return fail(h, WS_ERR_INVALID_ARG, "advection: points must be finite and within 1e15");
-    return WS_OK;
-}
-
-// ws_advect_points: the binning with velocities, the march kernel (in place on the uploaded points), the results out.
-ws_status advect_points(ws_handle *h, const ws_advect_params *a, const float *xyz, uint32_t m, float *out_xyz, float *out_vel,
-                        float *out_rho)
-{
-    WS_DEAD_CHECK(h);
-    if (h->flags & WS_FLAG_REFERENCE_ORDER) return fail(h, WS_ERR_UNSUPPORTED, "advection: not in the reference-order validation mode");
-    const bool want = out_xyz || out_vel || out_rho;
-    if (!want && !h->slab) return fail(h, WS_ERR_INVALID_ARG, "advection: every output is NULL");
-    bool contributed = false;
-    auto check = [&]() -> ws_status { return advect_check(h, a, xyz, m, out_xyz); };
-    WsDev d;
-    ws_status st = field_sample_device(h, nullptr, 0, nullptr, nullptr, want, false, false, check, &contributed, nullptr, false,
-                                       &d, true);
-    if (st || contributed) return st;
-    hipStream_t s = h->stream;
-    auto &F = h->field;
-    if ((st = field_grow(h, &F.q, &F.q_bytes, (size_t)m * 12))) return st;
-    if (out_rho && (st = field_grow(h, &F.rho, &F.rho_bytes, (size_t)m * 4))) return st;
-    if (out_vel && (st = field_grow(h, &F.grad, &F.grad_bytes, (size_t)m * 12))) return st;
-    HIP_TRY(h, hipMemcpyAsync(F.q, xyz, (size_t)m * 12, hipMemcpyHostToDevice, s));
-    wsk_advect(s, d, F.start, F.spos, F.svel, h->ieee, F.q, m, a->dt, a->substeps, out_vel ? F.grad : nullptr,
-               out_rho ? F.rho : nullptr);
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(out_xyz, F.q, (size_t)m * 12, hipMemcpyDeviceToHost, s));
-    if (out_rho) HIP_TRY(h, hipMemcpyAsync(out_rho, F.rho, (size_t)m * 4, hipMemcpyDeviceToHost, s));
-    if (out_vel) HIP_TRY(h, hipMemcpyAsync(out_vel, F.grad, (size_t)m * 12, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    drain_profile(h);
-    return WS_OK;
-}
-
-// ---- whitewater (include/wsfluid.h defines the stage, the emission and the step) ----
-// The binning with velocities for a whitewater call (field_sample_device: collective on slabs, check() after the gather).
-template <class Check>
-ws_status whitewater_bin(ws_handle *h, const char *what, bool want, Check check, bool *contributed, WsDev *d)
-{
-    *contributed = false;
-    if (h->flags & WS_FLAG_REFERENCE_ORDER) return fail(h, WS_ERR_UNSUPPORTED, "whitewater: not in the reference-order validation mode");
-    if (!want && !h->slab) return fail(h, WS_ERR_INVALID_ARG, what);
-    return field_sample_device(h, nullptr, 0, nullptr, nullptr, want, false, false, check, contributed, nullptr, false, d, true);
-}
-
-// The per-particle stage into F.wst (T, K, a, E: n floats each, then the normals) and F.wnb, by id.
-ws_status whitewater_stage(ws_handle *h, const WsDev &d)
-{
-    auto &F = h->field;
-    const size_t n = F.n;
-    ws_status st;
-    if ((st = field_grow(h, &F.wnrm, &F.wnrm_bytes, n * 16))) return st;
-    if ((st = field_grow(h, &F.wst, &F.wst_bytes, n * 28))) return st;
-    if ((st = field_grow(h, &F.wnb, &F.wnb_bytes, n * 4))) return st;
-    wsk_whitewater_stage(h->stream, d, F.start, F.spos, F.svel, F.wnrm, F.wst, F.wst + n, F.wst + 2 * n, F.wst + 3 * n,
-                         F.wst + 4 * n, F.wnb, (uint32_t)n);
-    HIP_TRY(h, hipGetLastError());
-    return WS_OK;
-}
-
-ws_status read_whitewater(ws_handle *h, float *out_t, float *out_k, float *out_a, float *out_e, float *out_nrm, uint32_t *out_nb)
-{
-    WS_DEAD_CHECK(h);
-    const bool want = out_t || out_k || out_a || out_e || out_nrm || out_nb;
-    bool contributed = false;
-    WsDev d;
-    ws_status st = whitewater_bin(h, "whitewater: every output is NULL", want, []() { return WS_OK; }, &contributed, &d);
-    if (st || contributed) return st;
-    if ((st = whitewater_stage(h, d))) return st;
-    hipStream_t s = h->stream;
-    auto &F = h->field;
-    const size_t n = F.n;
-    float *const outs[4] = {out_t, out_k, out_a, out_e};
-    for (int k = 0; k < 4; k++)
-        if (outs[k]) HIP_TRY(h, hipMemcpyAsync(outs[k], F.wst + k * n, n * 4, hipMemcpyDeviceToHost, s));
-    if (out_nrm) HIP_TRY(h, hipMemcpyAsync(out_nrm, F.wst + 4 * n, n * 12, hipMemcpyDeviceToHost, s));
-    if (out_nb) HIP_TRY(h, hipMemcpyAsync(out_nb, F.wnb, n * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    drain_profile(h);
-    return WS_OK;
-}
-
-ws_status whitewater_emit_check(ws_handle *h, const ws_whitewater_emit_params *e, const uint32_t *n_emitted)
-{
-    if (!e) return fail(h, WS_ERR_INVALID_ARG, "whitewater: the emission parameters are required");
-    if (!n_emitted) return fail(h, WS_ERR_INVALID_ARG, "whitewater: n_emitted is required");
-    for (const float *tau : {e->tau_trapped, e->tau_crest, e->tau_energy})
-        if (!isfinite(tau[0]) || !isfinite(tau[1]) || !(tau[0] >= 0.0f) || !(tau[0] < tau[1]))
-            return fail(h, WS_ERR_INVALID_ARG, "whitewater: a tau pair must be finite with 0 <= tau[0] < tau[1]");
-    if (!isfinite(e->k_trapped) || !isfinite(e->k_crest) || !(e->k_trapped >= 0.0f) || !(e->k_crest >= 0.0f))
-        return fail(h, WS_ERR_INVALID_ARG, "whitewater: the rates must be finite and >= 0");
-    if (!isfinite(e->crest_align)) return fail(h, WS_ERR_INVALID_ARG, "whitewater: crest_align must be finite");
-    if (!isfinite(e->dt) || !(e->dt > 0.0f)) return fail(h, WS_ERR_INVALID_ARG, "whitewater: dt must be finite and > 0");
-    if (!isfinite(e->radius) || !(e->radius > 0.0f)) return fail(h, WS_ERR_INVALID_ARG, "whitewater: radius must be finite and > 0");
-    if (!isfinite(e->lifetime[0]) || !isfinite(e->lifetime[1]) || !(e->lifetime[0] >= 0.0f) || !(e->lifetime[0] <= e->lifetime[1]))
-        return fail(h, WS_ERR_INVALID_ARG, "whitewater: lifetime must be finite with 0 <= lifetime[0] <= lifetime[1]");
-    if (e->max_per_particle < 1u || e->max_per_particle > 64u)
-        return fail(h, WS_ERR_INVALID_ARG, "whitewater: max_per_particle must lie in 1 .. 64");
-    return WS_OK;
-}
-
-// ws_emit_whitewater: the stage, the counts by id, their scan (n + 1 entries: the last is the total), the total back to
-// the host and -- when the caller's buffers hold them -- the spawns.
-ws_status emit_whitewater(ws_handle *h, const ws_whitewater_emit_params *e, uint32_t max_emitted, float *out_xyz, float *out_vel,
-                          float *out_life, uint32_t *out_src, uint32_t *n_emitted)
-{
-    WS_DEAD_CHECK(h);
-    const bool want = out_xyz || out_vel || out_life || out_src || n_emitted;
-    bool contributed = false;
-    WsDev d;
-    ws_status st = whitewater_bin(h, "whitewater: every output is NULL", want,
-                                  [&]() { return whitewater_emit_check(h, e, n_emitted); }, &contributed, &d);
-    if (st || contributed) return st;
-    if ((st = whitewater_stage(h, d))) return st;
-    hipStream_t s = h->stream;
-    auto &F = h->field;
-    const size_t n = F.n;
-    if (n * e->max_per_particle > 0xFFFFFFFFull) return fail(h, WS_ERR_INVALID_ARG, "whitewater: n * max_per_particle exceeds 2^32 - 1");
-    const size_t words = (n + 1 + 3) & ~(size_t)3;  // whole uint4 for the scan
-    const size_t sw = (size_t)wsk_scan_state_words((uint32_t)n + 1u) * 4;
-    if ((st = field_grow(h, &F.wcnt, &F.wcnt_bytes, words * 4))) return st;
-    if ((st = field_grow(h, &F.woff, &F.woff_bytes, words * 4))) return st;
-    if ((st = field_grow(h, &F.wstate, &F.wstate_bytes, sw))) return st;
-    // (the scan's tickets number its launches on a state buffer of a fixed length: fresh state for every call)
-    HIP_TRY(h, hipMemsetAsync(F.wstate, 0, sw, s));
-    HIP_TRY(h, hipMemsetAsync(F.wcnt, 0, words * 4, s));
-    const WsWhiteEmit we = {e->tau_trapped[0], e->tau_trapped[1], e->tau_crest[0], e->tau_crest[1], e->tau_energy[0],
-                            e->tau_energy[1], e->k_trapped,     e->k_crest,      e->crest_align,  e->dt,
-                            e->radius,         e->lifetime[0],  e->lifetime[1],  e->max_per_particle, e->seed};
-    wsk_whitewater_count(s, we, F.vxyz, F.wst, F.wst + n, F.wst + 2 * n, F.wst + 3 * n, F.wcnt, (uint32_t)n);
-    wsk_scan(s, F.wcnt, F.woff, nullptr, F.wstate, (uint32_t)n + 1u, false, 0);
-    HIP_TRY(h, hipGetLastError());
-    uint32_t total = 0;
-    HIP_TRY(h, hipMemcpyAsync(&total, F.woff + n, 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    *n_emitted = total;
-    if ((out_xyz || out_vel || out_life || out_src) && total != 0u && total <= max_emitted) {
-        const size_t T = total;
-        if ((st = field_grow(h, &F.wout, &F.wout_bytes, T * 32))) return st;
-        float *xyz = F.wout, *vel = F.wout + 3 * T, *life = F.wout + 6 * T;
-        uint32_t *src = reinterpret_cast<uint32_t *>(F.wout + 7 * T);
-        wsk_whitewater_spawn(s, we, h->slab ? F.vpos : F.xyz, F.vxyz, F.wcnt, F.woff, out_xyz ? xyz : nullptr,
-                             out_vel ? vel : nullptr, out_life ? life : nullptr, out_src ? src : nullptr, (uint32_t)n);
-        HIP_TRY(h, hipGetLastError());
-        if (out_xyz) HIP_TRY(h, hipMemcpyAsync(out_xyz, xyz, T * 12, hipMemcpyDeviceToHost, s));
-        if (out_vel) HIP_TRY(h, hipMemcpyAsync(out_vel, vel, T * 12, hipMemcpyDeviceToHost, s));
-        if (out_life) HIP_TRY(h, hipMemcpyAsync(out_life, life, T * 4, hipMemcpyDeviceToHost, s));
-        if (out_src) HIP_TRY(h, hipMemcpyAsync(out_src, src, T * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipStreamSynchronize(s));
-    }
-    drain_profile(h);
-    return WS_OK;
-}
-
-ws_status whitewater_step_check(ws_handle *h, const ws_whitewater_step_params *p, const float *xyz, const float *vel,
-                                const float *life, uint32_t m)
-{
-    if (!p) return fail(h, WS_ERR_INVALID_ARG, "whitewater: the step parameters are required");
-    if (!isfinite(p->dt) || !(p->dt > 0.0f)) return fail(h, WS_ERR_INVALID_ARG, "whitewater: dt must be finite and > 0");
-    if (!isfinite(p->buoyancy)) return fail(h, WS_ERR_INVALID_ARG, "whitewater: buoyancy must be finite");
-    if (!(p->drag >= 0.0f && p->drag <= 1.0f)) return fail(h, WS_ERR_INVALID_ARG, "whitewater: drag must lie in [0, 1]");
-    if (!xyz || !vel || !life || m == 0u) return fail(h, WS_ERR_INVALID_ARG, "whitewater: no diffuse particles");
-    if (m > (1u << 28)) return fail(h, WS_ERR_INVALID_ARG, "whitewater: more than 2^28 diffuse particles");
-    for (size_t t = 0; t < (size_t)m * 3; t++)
-        if (!isfinite(xyz[t]) || fabsf(xyz[t]) > 1e15f || !isfinite(vel[t]) || fabsf(vel[t]) > 1e15f)
-            return fail(h, WS_ERR_INVALID_ARG, "whitewater: positions and velocities must be finite and within 1e15");
-    for (size_t t = 0; t < m; t++)
-        if (!isfinite(life[t])) return fail(h, WS_ERR_INVALID_ARG, "whitewater: lifetimes must be finite");
-    return WS_OK;
-}
-
-// ws_step_whitewater: the binning with velocities, the particles up, one kernel in place, the results out.
-ws_status step_whitewater(ws_handle *h, const ws_whitewater_step_params *p, const float *xyz, const float *vel, const float *life,
-                          uint32_t m, float *out_xyz, float *out_vel, float *out_life, uint8_t *out_class)
-{
-    WS_DEAD_CHECK(h);
-    const bool want = out_xyz || out_vel || out_life || out_class;
-    bool contributed = false;
-    WsDev d;
-    ws_status st = whitewater_bin(h, "whitewater: every output is NULL", want,
-                                  [&]() { return whitewater_step_check(h, p, xyz, vel, life, m); }, &contributed, &d);
-    if (st || contributed) return st;
-    hipStream_t s = h->stream;
-    auto &F = h->field;
-    const size_t M = m;
-    if ((st = field_grow(h, &F.wpt, &F.wpt_bytes, M * 28 + M))) return st;
-    float *dp = F.wpt, *dv = F.wpt + 3 * M, *dl = F.wpt + 6 * M;
-    uint8_t *dc = reinterpret_cast<uint8_t *>(F.wpt + 7 * M);
-    HIP_TRY(h, hipMemcpyAsync(dp, xyz, M * 12, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(dv, vel, M * 12, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(dl, life, M * 4, hipMemcpyHostToDevice, s));
-    const WsWhiteStep sp = {p->dt, p->spray_max, p->bubble_min, p->buoyancy, p->drag};
-    wsk_whitewater_step(s, d, F.start, F.spos, F.svel, h->ieee, sp, dp, dv, dl, dc, m);
-    HIP_TRY(h, hipGetLastError());
-    // (the uploads have left the caller's buffers before the kernel runs: outputs may alias inputs)
-    if (out_xyz) HIP_TRY(h, hipMemcpyAsync(out_xyz, dp, M * 12, hipMemcpyDeviceToHost, s));
-    if (out_vel) HIP_TRY(h, hipMemcpyAsync(out_vel, dv, M * 12, hipMemcpyDeviceToHost, s));
-    if (out_life) HIP_TRY(h, hipMemcpyAsync(out_life, dl, M * 4, hipMemcpyDeviceToHost, s));
-    if (out_class) HIP_TRY(h, hipMemcpyAsync(out_class, dc, M, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    drain_profile(h);
-    return WS_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-ws_status ws_sample_density_grid(ws_handle *h, const float origin[3], const float spacing[3], const uint32_t dims[3],
-                                 float *out_density, float *out_gradient)
-{
-    if (!h) return WS_ERR_INVALID_ARG;
-    if ((out_density || out_gradient || !h->slab) && (!origin || !spacing || !dims))
-        return fail(h, WS_ERR_INVALID_ARG, "density field: origin, spacing and dims are required");
-    float g6[6] = {0.f, 0.f, 0.f, 1.f, 1.f, 1.f};
-    const uint32_t one[3] = {1u, 1u, 1u};
-    if (origin && spacing && dims) {
-        for (int a = 0; a < 3; a++) {
-            g6[a] = origin[a];
-            g6[3 + a] = spacing[a];
-        }
-    }
-    return sample_density(h, nullptr, 0, g6, dims ? dims : one, out_density, out_gradient);
-}
-
-ws_status ws_sample_density_points(ws_handle *h, const float *xyz, uint32_t m, float *out_density, float *out_gradient)
-{
-    if (!h) return WS_ERR_INVALID_ARG;
-    return sample_density(h, xyz, m, nullptr, nullptr, out_density, out_gradient);
-}
-
-ws_status ws_extract_surface(ws_handle *h, const float origin[3], const float spacing[3], const uint32_t dims[3], float iso,
-                             uint32_t max_vertices, uint32_t max_triangles, float *out_xyz, float *out_normal,
-                             uint32_t *out_tri, uint32_t *n_vertices, uint32_t *n_triangles)
-{
-    if (!h) return WS_ERR_INVALID_ARG;
-    const bool query = origin && spacing && dims;
-    // (a slab rank without a query fails after the collective gather: extract_surface's check)
-    if (!query && !h->slab) return fail(h, WS_ERR_INVALID_ARG, "surface: origin, spacing and dims are required");
-    float g6[6] = {0.f, 0.f, 0.f, 1.f, 1.f, 1.f};
-    const uint32_t two[3] = {2u, 2u, 2u};
-    if (query) {
-        for (int a = 0; a < 3; a++) {
-            g6[a] = origin[a];
-            g6[3 + a] = spacing[a];
-        }
-    }
-    return extract_surface(h, query, g6, query ? dims : two, iso, max_vertices, max_triangles, out_xyz, out_normal,
-                           out_tri, n_vertices, n_triangles);
-}
-
-// ======================================================================================
-// anisotropic kernels (Yu & Turk 2013; include/wsfluid.h defines the stage, the field and the mesh)
-// ======================================================================================
-ws_status ws_default_aniso_params(ws_aniso_params *out)
-{
-    if (!out) return WS_ERR_INVALID_ARG;
-    out->smoothing = 0.9f;
-    out->max_ratio = 4.0f;
-    out->lone_scale = 0.5f;
-    out->min_neighbours = 12u;
-    return WS_OK;
-}
-
-ws_status ws_read_anisotropy(ws_handle *h, const ws_aniso_params *a, float *out_centre, float *out_matrix, float *out_scale,
-                             uint32_t *out_neighbours)
-{
-    if (!h) return WS_ERR_INVALID_ARG;
-    return read_anisotropy(h, a, out_centre, out_matrix, out_scale, out_neighbours);
-}
-
-ws_status ws_sample_aniso_grid(ws_handle *h, const ws_aniso_params *a, const float origin[3], const float spacing[3],
-                               const uint32_t dims[3], float *out_field, float *out_gradient)
-{
-    if (!h) return WS_ERR_INVALID_ARG;
-    if ((out_field || out_gradient || !h->slab) && (!origin || !spacing || !dims))
-        return fail(h, WS_ERR_INVALID_ARG, "density field: origin, spacing and dims are required");
-    float g6[6] = {0.f, 0.f, 0.f, 1.f, 1.f, 1.f};
-    const uint32_t one[3] = {1u, 1u, 1u};
-    if (origin && spacing && dims) {
-        for (int k = 0; k < 3; k++) {
-            g6[k] = origin[k];
-            g6[3 + k] = spacing[k];
-        }
-    }
-    return sample_density(h, nullptr, 0, g6, dims ? dims : one, out_field, out_gradient, true, a);
-}
-
-ws_status ws_sample_aniso_points(ws_handle *h, const ws_aniso_params *a, const float *xyz, uint32_t m, float *out_field,
-                                 float *out_gradient)
-{
-    if (!h) return WS_ERR_INVALID_ARG;
-    return sample_density(h, xyz, m, nullptr, nullptr, out_field, out_gradient, true, a);
-}
-
-ws_status ws_extract_aniso_surface(ws_handle *h, const ws_aniso_params *a, const float origin[3], const float spacing[3],
-                                   const uint32_t dims[3], float iso, uint32_t max_vertices, uint32_t max_triangles,
-                                   float *out_xyz, float *out_normal, uint32_t *out_tri, uint32_t *n_vertices,
-                                   uint32_t *n_triangles)
-{
-    if (!h) return WS_ERR_INVALID_ARG;
-    const bool query = origin && spacing && dims;
-    if (!query && !h->slab) return fail(h, WS_ERR_INVALID_ARG, "surface: origin, spacing and dims are required");
-    float g6[6] = {0.f, 0.f, 0.f, 1.f, 1.f, 1.f};
-    const uint32_t two[3] = {2u, 2u, 2u};
-    if (query) {
-        for (int k = 0; k < 3; k++) {
-            g6[k] = origin[k];
-            g6[3 + k] = spacing[k];
-        }
-    }
-    return extract_surface(h, query, g6, query ? dims : two, iso, max_vertices, max_triangles, out_xyz, out_normal,
-                           out_tri, n_vertices, n_triangles, true, a);
-}
-
-// ======================================================================================
-// rays at the fluid surface (include/wsfluid.h defines the march, the hit and the normal)
-// ======================================================================================
-ws_status ws_cast_rays(ws_handle *h, const ws_aniso_params *a, const ws_ray_params *r, const float *origin_xyz,
-                       const float *dir_xyz, uint32_t m, float *out_t, float *out_normal)
-{
-    if (!h) return WS_ERR_INVALID_ARG;
-    return cast_rays(h, a, r, false, origin_xyz, dir_xyz, m, nullptr, nullptr, out_t, out_normal);
-}
-
-ws_status ws_cast_camera(ws_handle *h, const ws_aniso_params *a, const ws_ray_params *r, const ws_camera *cam,
-                         const uint32_t size[2], float *out_t, float *out_normal)
-{
-    if (!h) return WS_ERR_INVALID_ARG;
-    return cast_rays(h, a, r, true, nullptr, nullptr, 0, cam, size, out_t, out_normal);
-}
-
-// ======================================================================================
-// velocity field and tracer advection (include/wsfluid.h defines the field and the march)
-// ======================================================================================
-ws_status ws_sample_velocity_grid(ws_handle *h, const float origin[3], const float spacing[3], const uint32_t dims[3],
-                                  float *out_velocity, float *out_density)
-{
-    if (!h) return WS_ERR_INVALID_ARG;
-    if ((out_velocity || out_density || !h->slab) && (!origin || !spacing || !dims))
-        return fail(h, WS_ERR_INVALID_ARG, "velocity field: origin, spacing and dims are required");
-    float g6[6] = {0.f, 0.f, 0.f, 1.f, 1.f, 1.f};
-    const uint32_t one[3] = {1u, 1u, 1u};
-    if (origin && spacing && dims) {
-        for (int k = 0; k < 3; k++) {
-            g6[k] = origin[k];
-            g6[3 + k] = spacing[k];
-        }
-    }
-    return sample_velocity(h, nullptr, 0, g6, dims ? dims : one, out_velocity, out_density);
-}
-
-ws_status ws_sample_velocity_points(ws_handle *h, const float *xyz, uint32_t m, float *out_velocity, float *out_density)
-{
-    if (!h) return WS_ERR_INVALID_ARG;
-    return sample_velocity(h, xyz, m, nullptr, nullptr, out_velocity, out_density);
-}
-
-ws_status ws_advect_points(ws_handle *h, const ws_advect_params *a, const float *xyz, uint32_t m, float *out_xyz,
-                           float *out_velocity, float *out_density)
-{
-    if (!h) return WS_ERR_INVALID_ARG;
-    return advect_points(h, a, xyz, m, out_xyz, out_velocity, out_density);
-}
-
-// ======================================================================================
-// whitewater: foam, spray and bubbles (include/wsfluid.h defines the stage, the emission and the step)
-// ======================================================================================
-ws_status ws_default_whitewater_emit_params(ws_whitewater_emit_params *out)
-{
-    if (!out) return WS_ERR_INVALID_ARG;
-    out->tau_trapped[0] = 5.0f;  out->tau_trapped[1] = 50.0f;
-    out->tau_crest[0] = 0.5f;    out->tau_crest[1] = 4.0f;
-    out->tau_energy[0] = 1.0f;   out->tau_energy[1] = 25.0f;
-    out->k_trapped = 400.0f;
-    out->k_crest = 400.0f;
-    out->crest_align = 0.6f;
-    out->dt = 1.0f / 60.0f;
-    out->radius = 0.1f;
-    out->lifetime[0] = 2.0f;     out->lifetime[1] = 5.0f;
-    out->max_per_particle = 8u;
-    out->seed = 0u;
-    return WS_OK;
-}
-
-ws_status ws_default_whitewater_step_params(ws_whitewater_step_params *out)
-{
-    if (!out) return WS_ERR_INVALID_ARG;
-    out->dt = 1.0f / 60.0f;
-    out->spray_max = 6u;
-    out->bubble_min = 20u;
-    out->buoyancy = 2.0f;
-    out->drag = 0.5f;
-    return WS_OK;
-}
-
-ws_status ws_read_whitewater(ws_handle *h, float *out_trapped, float *out_crest, float *out_align, float *out_energy,
-                             float *out_normal, uint32_t *out_neighbours)
-{
-    if (!h) return WS_ERR_INVALID_ARG;
-    return read_whitewater(h, out_trapped, out_crest, out_align, out_energy, out_normal, out_neighbours);
-}
-
-ws_status ws_emit_whitewater(ws_handle *h, const ws_whitewater_emit_params *e, uint32_t max_emitted, float *out_xyz,
-                             float *out_velocity, float *out_life, uint32_t *out_source, uint32_t *n_emitted)
-{
-    if (!h) return WS_ERR_INVALID_ARG;
-    return emit_whitewater(h, e, max_emitted, out_xyz, out_velocity, out_life, out_source, n_emitted);
-}
-
-ws_status ws_step_whitewater(ws_handle *h, const ws_whitewater_step_params *p, const float *xyz, const float *velocity,
-                             const float *life, uint32_t m, float *out_xyz, float *out_velocity, float *out_life,
-                             uint8_t *out_class)
-{
-    if (!h) return WS_ERR_INVALID_ARG;
-    return step_whitewater(h, p, xyz, velocity, life, m, out_xyz, out_velocity, out_life, out_class);
-}
-
-// ======================================================================================
 // introspection
 // ======================================================================================
 ws_status ws_profile_read(ws_handle *h, uint32_t k, double *total_ms, uint64_t *launches)
@@ -2323,4 +1391,5 @@ ws_status ws_grid_dims(ws_handle *h, uint32_t dims[3])
 
 }  // extern "C"
 
+#include "ws_field.inc"
 #include "ws_slab.inc"

@@ -177,6 +177,68 @@ struct WsEventPair {
     bool counts = true;  // false: the second launch of a kernel id within one step (time is added, the launch count is per step)
 };
 
+// Device scratch of the derived-field layer (csrc/ws_field.inc defines alloc and grow).  A failed allocation is
+// WS_ERR_OUT_OF_MEMORY with the sticky HIP error cleared, p == nullptr and bytes == 0: the handle stays usable.
+template <class T>
+struct WsScratch {
+    T *p = nullptr;
+    size_t bytes = 0;
+    ws_status alloc(ws_handle *h, size_t need);  // release(), then `need` bytes
+    ws_status grow(ws_handle *h, size_t need);   // nothing when it holds `need` bytes already, else alloc()
+    void release()
+    {
+        hipFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
+};
+
+// ws_handle::field: the scratch of the derived-field calls -- their own counting sort of the CURRENT positions, allocated
+// on the first call, freed by ws_destroy.  Nothing ws_step reads is written.  Per particle: 12 B positions by id
+// (single-GPU handles), 3 x 4 B keys / tentative slots / sorted ids, 16 B sorted {position, id} = 40 B; per cell: count,
+// cursor and start (4 B each) and the scan state; plus the queries and results of the largest call so far.  
+struct WsField {
+    // per particle, exact size, keyed by n: a call with another particle count releases EVERYTHING below and starts over
+    uint32_t n = 0;                   // particles the arrays hold
+    WsScratch<float> xyz;             // positions by id (single-GPU handles; a slab samples the gathered S->g_out); the
+                                      // by-id positions the whitewater spawn kernel reads on a single handle
+    WsScratch<uint32_t> keys, tmp, perm;  // cell id by id, tentative slots, sorted ids
+    WsScratch<float4> spos;           // {position, id} in cell order, id inside a cell; ALIASED: an anisotropic call
+                                      // overwrites it with the centres in THEIR cell order (field_aniso_bin)
+    // per cell, exact size, keyed by cells: rebuilt after a re-grid (bsum zeroed once at allocation, start[cells] = n
+    // written when the tables are made)
+    uint32_t cells = 0;               // cells the tables describe
+    WsScratch<uint32_t> count, cursor, start, bsum;  // cells (+ 1) words each, and the scan state
+    // everything below is grow-only: allocated by the first call that needs it, kept at the largest size seen
+    WsScratch<float> q, rho;          // query points and densities on the device
+    WsScratch<float> grad;            // gradients; ALIASED: the velocity and advect calls put their velocities here
+    // surface extraction (ws_extract_surface): node codes and vertex bases, per-workgroup totals and their scans
+    // (2 x blocks + 1 words each, 16 B aligned halves; bstart also the two grand totals) and scan state, the mesh
+    WsScratch<uint8_t> code;
+    WsScratch<uint32_t> vbase, bcnt, bstart, bstate, tri;
+    WsScratch<float> mxyz, mnrm;
+    // velocity field (ws_sample_velocity_*, ws_advect_points, whitewater): the velocities by id and in cell order beside
+    // spos, and on slab handles the gathered positions by id (the gather brings {position, velocity} records, split into
+    // vpos / vxyz); vpos is also the by-id positions the whitewater spawn kernel reads on a slab
+    WsScratch<float> vxyz, vpos;
+    WsScratch<float4> svel;
+    // whitewater (ws_read_whitewater, ws_emit_whitewater, ws_step_whitewater): the normals in spos' order, the stage by id
+    // (trapped, crest, align, energy, normal x 3 as one array of 7 n floats; the neighbour counts), the emission counts,
+    // their scan and its state, the spawns (xyz, velocity: 3 floats, life, source: 1 word each, as one array), a step's
+    // particles (7 floats + 1 byte each)
+    WsScratch<float4> wnrm;
+    WsScratch<float> wst, wout, wpt;
+    WsScratch<uint32_t> wnb, wcnt, woff, wstate;
+    // anisotropic kernels (ws_read_anisotropy, ws_sample_aniso_*, ws_extract_aniso_surface): centres, ellipsoids and
+    // neighbour counts by id, the centres' ellipsoids in their cell order (their {c, id} reuse spos)
+    WsScratch<float> cxyz;
+    WsScratch<float4> amf, smf;
+    WsScratch<uint32_t> anb;
+    // rays (ws_cast_rays / ws_cast_camera): the rays of a list call (origins, then directions: 24 B per ray) and the
+    // results (4 B + 12 B per ray)
+    WsScratch<float> rays, ray_t, ray_n;
+};
+
 struct ws_handle {
     int device = 0;
     uint32_t flags = 0;
@@ -229,51 +291,7 @@ struct ws_handle {
     uint32_t *v_keys = nullptr, *v_perm = nullptr, *v_tmp = nullptr, *v_count = nullptr,
              *v_cursor = nullptr, *v_start = nullptr, *v_bsum = nullptr, *v_off = nullptr;
 
-    // density field sampler (ws_sample_density_grid / _points): its own counting sort of the CURRENT positions, allocated
-    // on the first sample call, rebuilt when the grid changes, freed by ws_destroy.  Nothing ws_step reads is written.
-    struct {
-        float *xyz = nullptr;      // positions by id (single-GPU handles; a slab samples the gathered S->g_out)
-        uint32_t *keys = nullptr, *tmp = nullptr, *perm = nullptr;  // cell id by id, tentative slots, sorted ids
-        float4 *spos = nullptr;    // {position, id} in cell order, id inside a cell
-        uint32_t n = 0;            // particles the arrays hold
-        uint32_t *count = nullptr, *cursor = nullptr, *start = nullptr, *bsum = nullptr;  // ncells (+ 1) per-cell words
-        uint32_t cells = 0;        // cells the tables describe
-        float *q = nullptr, *rho = nullptr, *grad = nullptr;  // query points and results on the device
-        size_t q_bytes = 0, rho_bytes = 0, grad_bytes = 0;
-        // surface extraction (ws_extract_surface): node codes and vertex bases, per-workgroup totals and their scans
-        // (2 x blocks + 1 words each, 16 B aligned halves; bstart also the two grand totals) and scan state, the mesh --
-        // all grow-only
-        uint8_t *code = nullptr;
-        uint32_t *vbase = nullptr, *bcnt = nullptr, *bstart = nullptr, *bstate = nullptr, *tri = nullptr;
-        float *mxyz = nullptr, *mnrm = nullptr;
-        size_t code_bytes = 0, vbase_bytes = 0, bcnt_bytes = 0, bstart_bytes = 0, bstate_bytes = 0, tri_bytes = 0,
-               mxyz_bytes = 0, mnrm_bytes = 0;
-        // velocity field (ws_sample_velocity_*, ws_advect_points), grow-only, allocated on the first velocity call: the
-        // velocities by id and in cell order beside spos, and on slab handles the gathered positions by id (the
-        // gather brings {position, velocity} records, split into vpos / vxyz)
-        float *vxyz = nullptr, *vpos = nullptr;
-        float4 *svel = nullptr;
-        size_t vxyz_bytes = 0, vpos_bytes = 0, svel_bytes = 0;
-        // whitewater (ws_read_whitewater, ws_emit_whitewater, ws_step_whitewater), grow-only, allocated on the first
-        // whitewater call: the normals in spos' order, the stage by id (trapped, crest, align, energy, normal x 3 as one
-        // array of 7 n floats; the neighbour counts), the emission counts, their scan and its state, the spawns
-        // (xyz, velocity: 3 floats, life, source: 1 word each, as one array), a step's particles (7 floats + 1 byte each)
-        float4 *wnrm = nullptr;
-        float *wst = nullptr, *wout = nullptr, *wpt = nullptr;
-        uint32_t *wnb = nullptr, *wcnt = nullptr, *woff = nullptr, *wstate = nullptr;
-        size_t wnrm_bytes = 0, wst_bytes = 0, wout_bytes = 0, wpt_bytes = 0, wnb_bytes = 0, wcnt_bytes = 0, woff_bytes = 0,
-               wstate_bytes = 0;
-        // anisotropic kernels (ws_read_anisotropy, ws_sample_aniso_*, ws_extract_aniso_surface), grow-only: centres,
-        // ellipsoids and neighbour counts by id, the centres' ellipsoids in their cell order (their {c, id} reuse spos)
-        float *cxyz = nullptr;
-        float4 *amf = nullptr, *smf = nullptr;
-        uint32_t *anb = nullptr;
-        size_t cxyz_bytes = 0, amf_bytes = 0, smf_bytes = 0, anb_bytes = 0;
-        // rays (ws_cast_rays / ws_cast_camera), grow-only: the rays of a list call (origins, then directions: 24 B per
-        // ray) and the results (4 B + 12 B per ray)
-        float *rays = nullptr, *ray_t = nullptr, *ray_n = nullptr;
-        size_t rays_bytes = 0, ray_t_bytes = 0, ray_n_bytes = 0;
-    } field;
+    WsField field;  // derived-field calls (csrc/ws_field.inc)
 
     // profiling
     std::vector<WsEventPair> pending;
