@@ -745,6 +745,61 @@ ws_status ws_step_whitewater(ws_handle *h, const ws_whitewater_step_params *p, c
                              const float *life, uint32_t m, float *out_xyz, float *out_velocity, float *out_life,
                              uint8_t *out_class);
 
+/* ---- acting on the fluid: push, pull, blow on and stir it (the "interaction force" of the simulation the
+ *      reference descends from, which the reference dropped) ----------------------------------------------------------
+ * Every call above this block reads the fluid.  ws_apply_forces changes the VELOCITIES of the state the enqueued steps
+ * leave, by one explicit Euler step of the acceleration of k emitters, stream-ordered after the steps enqueued so far and
+ * before the next ws_step -- where the step itself applies gravity (v += a * dt, then the predicted position, then the
+ * cell).  A host calls it once per frame while the mouse button is held, with the hit point of ws_cast_camera as centre.
+ * Positions do not change.  The predicted position of EVERY particle becomes the library's own rule on the new velocity,
+ * pred_a = fl(x_a + fl(v'_a * 0.02f)), and the next step starts from it exactly as if gravity had produced that velocity.
+ * Below fl() is a rounding to float; arithmetic is IEEE whatever the handle's flags: every operation is rounded once, sqrt
+ * and division are correctly rounded, nothing is contracted; dot(a, b) = fl(fl(fl(a.x*b.x) + fl(a.y*b.y)) + fl(a.z*b.z))
+ * (the whitewater block's).  x, v are what ws_read_positions / ws_read_velocities return.
+ * Per particle, with A = (+0, +0, +0), for the emitters e = 0 .. k-1 in the order given (c = centre, R = radius):
+ *   1. q_a = x_a - c_a; d = sqrt(dot(q, q)).  If !(d < R) the emitter does not see the particle: on to the next one.
+ *      Otherwise the particle is AFFECTED and n_e += 1.
+ *   2. w = 1 - d / R; s = strength * w.
+ *   3. WS_FORCE_RADIAL: if d > 0: A_a = A_a - (q_a / d) * s (a particle exactly at the centre gets no radial term);
+ *      WS_FORCE_JET:    A_a = A_a + axis_a * s;
+ *      WS_FORCE_VORTEX: t = axis x q, t_x = axis_y*q_z - axis_z*q_y and cyclically (each product rounded, then the
+ *                       difference); A_a = A_a + t_a * s.
+ *   4. every kind: g = damping * w; A_a = A_a - v_a * g, with v the velocity BEFORE the call, not a running value.
+ * After the loop an affected particle gets v'_a = v_a + dt * A_a; a particle no emitter sees keeps its velocity bit for
+ * bit (a -0 stays -0).  out_affected, if not NULL, receives the k counts n_e.
+ * Afterwards, on a single handle: ws_steps_done is unchanged; ws_read_particles reports the old position, the new velocity
+ * and predicted position and the LAST STEP's density, pressure and acceleration; every read-only call sees the new
+ * velocities; a WS_FLAG_GRAPH handle keeps replaying its captured step (the emitters travel in the kernel's arguments, the
+ * kernel is launched outside the graph, no array moves).  The call may be made between ws_read_positions_begin and _end.
+ * With out_affected == NULL a single handle only enqueues and returns without waiting; with it the call waits for the
+ * counts.
+ * Slab handles: COLLECTIVE, the same bits as a single handle: every rank makes the same call with the same arguments at the
+ * same point of its frame.  The state is gathered, every rank applies the definition to the global set and reloads the
+ * particles it owns on the unchanged geometry -- so, as after any load of a slab handle, the 80-byte view reports zero
+ * density / pressure / acceleration until the next ws_step, cumulative counters carry over and captured steps are
+ * re-captured.  out_affected is the GLOBAL count on every rank that passes it.  The verdict is common: a rank validates its
+ * arguments after the gather, and if any rank refuses, or the ranks' arguments differ, ALL return WS_ERR_INVALID_ARG and
+ * nothing is changed.
+ * Errors: WS_ERR_INVALID_ARG (NULL handle or f; k outside 1 .. WS_MAX_FORCES; dt not finite or not > 0; a kind > 2; a
+ * non-zero reserved word; a non-finite centre, axis, strength or damping; damping < 0; radius not finite or not > 0; any
+ * magnitude above 1e15): nothing is touched and the handle steps on.  WS_ERR_UNSUPPORTED (WS_FLAG_REFERENCE_ORDER
+ * handles); WS_ERR_HIP on an unusable handle.  Whether a huge strength drives a velocity to infinity is the host's
+ * business, as it is with gravity. */
+#define WS_FORCE_RADIAL 0u   /* toward the centre (strength > 0) or away from it (< 0) */
+#define WS_FORCE_JET    1u   /* along `axis` */
+#define WS_FORCE_VORTEX 2u   /* around `axis` through the centre */
+#define WS_MAX_FORCES   16u
+typedef struct ws_force {      /* 48 bytes */
+    uint32_t kind;             /* offset 0 */
+    float centre[3];           /* 4  */
+    float axis[3];             /* 16: used as given, never normalised; ignored by RADIAL */
+    float radius;              /* 28: R > 0; a particle is in reach iff d < R */
+    float strength;            /* 32 */
+    float damping;             /* 36: >= 0; velocity removed per second at the centre (a brake, a spoon) */
+    uint32_t reserved[2];      /* 40: must be 0 */
+} ws_force;
+ws_status ws_apply_forces(ws_handle *h, const ws_force *f, uint32_t k, float dt, uint32_t *out_affected);
+
 /* ---- introspection ------------------------------------------------------------- */
 const char *ws_last_error(ws_handle *h);
 uint32_t ws_num_particles(ws_handle *h);

@@ -30,6 +30,7 @@ ws_status slab_reset(ws_handle *h, const float *pos_xyz);
 ws_status slab_write_particles(ws_handle *h, const ws_particle80 *in);
 ws_status slab_regrid(ws_handle *h, const ws_params *params, bool rebalance);
 ws_status slab_field_positions(ws_handle *h, const float **xyz, WsDev *global, bool with_vel);
+ws_status slab_apply_forces(ws_handle *h, const ws_force *f, uint32_t k, float dt, uint32_t *out_affected);
 // ws_field.inc
 void free_field(ws_handle *h);
 
@@ -649,7 +650,7 @@ void free_all(ws_handle *h)
     for (auto e : h->pool) hipEventDestroy(e);
     free_grid(h);
     free_particle_arrays(h);
-    hipFree(h->stats); hipFree(h->mult); hipFree(h->stage);
+    hipFree(h->stats); hipFree(h->mult); hipFree(h->stage); hipFree(h->force_cnt);
     hipFree(h->v_keys); hipFree(h->v_perm); hipFree(h->v_tmp); hipFree(h->v_count);
     hipFree(h->v_cursor); hipFree(h->v_start); hipFree(h->v_bsum); hipFree(h->v_off);
     free_field(h);
@@ -1256,6 +1257,70 @@ ws_status ws_write_particles(ws_handle *h, const ws_particle80 *in)
     if (st) return st;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->steps = 0;
+    return WS_OK;
+}
+
+// ======================================================================================
+// acting on the fluid
+// ======================================================================================
+}  // extern "C"
+
+namespace {
+
+// the argument errors of ws_apply_forces (nullptr = acceptable); nothing is touched before this has passed
+const char *forces_refusal(const ws_force *f, uint32_t k, float dt)
+{
+    const auto bad = [](float x) { return !isfinite(x) || fabsf(x) > 1e15f; };
+    if (!f) return "forces: f is NULL";
+    if (k < 1u || k > WS_MAX_FORCES) return "forces: k outside 1 .. WS_MAX_FORCES";
+    if (bad(dt) || !(dt > 0.f)) return "forces: dt must be finite, > 0 and at most 1e15";
+    for (uint32_t e = 0; e < k; e++) {
+        if (f[e].kind > WS_FORCE_VORTEX) return "forces: unknown kind";
+        if (f[e].reserved[0] || f[e].reserved[1]) return "forces: reserved words must be 0";
+        for (int c = 0; c < 3; c++)
+            if (bad(f[e].centre[c]) || bad(f[e].axis[c])) return "forces: centre and axis must be finite and at most 1e15 in magnitude";
+        if (bad(f[e].strength) || bad(f[e].damping)) return "forces: strength and damping must be finite and at most 1e15 in magnitude";
+        if (f[e].damping < 0.f) return "forces: damping must be >= 0";
+        if (bad(f[e].radius) || !(f[e].radius > 0.f)) return "forces: radius must be finite, > 0 and at most 1e15";
+    }
+    return nullptr;
+}
+
+// the k per-emitter counters on the device, zeroed on the handle's stream
+ws_status forces_counters(ws_handle *h)
+{
+    if (!h->force_cnt) HIP_TRY(h, hipMalloc(&h->force_cnt, WS_MAX_FORCES * 4));
+    HIP_TRY(h, hipMemsetAsync(h->force_cnt, 0, WS_MAX_FORCES * 4, h->stream));
+    return WS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// One streaming pass over `cur` behind the steps enqueued so far: new velocities, and the binned state every ws_step
+// starts from (bin_current's pair: the counts zeroed, then the kernel that draws cell ids, counts and ranks).  srt, the
+// accept masks and accel[] are not touched -- the 80-byte view keeps the last step's density, pressure and
+// acceleration -- and no array moves, so a captured step is replayed as it is.
+ws_status ws_apply_forces(ws_handle *h, const ws_force *f, uint32_t k, float dt, uint32_t *out_affected)
+{
+    if (!h) return WS_ERR_INVALID_ARG;
+    WS_DEAD_CHECK(h);
+    if (h->flags & WS_FLAG_REFERENCE_ORDER) return fail(h, WS_ERR_UNSUPPORTED, "forces: not in the reference-order validation mode");
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (h->slab) return slab_apply_forces(h, f, k, dt, out_affected);  // collective: validated after the gather
+    if (const char *why = forces_refusal(f, k, dt)) return fail(h, WS_ERR_INVALID_ARG, why);
+    WsForceSet fs{};
+    memcpy(fs.e, f, (size_t)k * sizeof(ws_force));
+    if (out_affected) {
+        const ws_status st = forces_counters(h);
+        if (st) return st;
+    }
+    HIP_TRY(h, hipMemsetAsync(h->count, 0, (size_t)h->dev.ncells * 4, h->stream));
+    wsk_apply_forces(h->stream, h->dev, h->cur, h->cid_cur, h->count, fs, k, dt, out_affected ? h->force_cnt : nullptr);
+    HIP_TRY(h, hipGetLastError());
+    h->pred_stale = true;  // cur.pred is behind the new velocities: k_reorder<true> / refresh_pred recompute it
+    if (out_affected) HIP_TRY(h, copy_now(h, out_affected, h->force_cnt, (size_t)k * 4, hipMemcpyDeviceToHost));
     return WS_OK;
 }
 

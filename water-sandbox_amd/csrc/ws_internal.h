@@ -269,6 +269,7 @@ struct ws_handle {
     bool ieee = false;            // WS_FLAG_IEEE_DIVISION: correctly rounded sqrt / division in the pair terms
     uint32_t *stats = nullptr;    // device counters: [0] particle-steps with more candidates than the mask holds
     uint8_t *mult = nullptr;      // 27 stencil multiplicities (hash aliasing), device
+    uint32_t *force_cnt = nullptr;  // ws_apply_forces: WS_MAX_FORCES per-emitter counts (allocated by the first call that asks)
     bool alias = false;
     size_t grid_alloc_cells = 0;
 
@@ -429,6 +430,16 @@ void wsk_scatter(hipStream_t s, const uint32_t *keys, uint32_t *cursor, uint32_t
 void wsk_reorder(hipStream_t s, const WsDev &d, const uint32_t *slot_tmp, const uint32_t *cid_cur, const uint32_t *start, WsSoA cur,
                  WsSorted srt, uint32_t *cid_srt, WsXYZ sxyz, bool recompute_pred);
 void wsk_refresh_pred(hipStream_t s, const WsDev &d, WsSoA cur);
+// ws_apply_forces: the emitters as ONE by-value kernel argument (scalar loads, wave-uniform loop); affected = k device
+// words the kernel adds the per-emitter counts to, or nullptr.  The first form edits `cur` in place and re-bins it (what
+// bin_current leaves: cid, the record's cell id, count, rank); the second edits gathered {id, pos, vel, pred} records.
+struct WsForceSet {
+    ws_force e[WS_MAX_FORCES];
+};
+void wsk_apply_forces(hipStream_t s, const WsDev &d, WsSoA cur, uint32_t *cid, uint32_t *count, const WsForceSet &fs, uint32_t k,
+                      float dt, uint32_t *affected);
+void wsk_apply_forces_records(hipStream_t s, uint32_t *all, const uint32_t *cnt, uint32_t world, uint32_t max_n,
+                              size_t stride_words, const WsForceSet &fs, uint32_t k, float dt, uint32_t *affected);
 void wsk_density(hipStream_t s, const WsDev &d, const uint32_t *start, const uint32_t *cid_srt, WsSorted srt,
                  const uint8_t *mult, bool alias, int variant, bool ieee, uint32_t *stats, WsMask mask, WsXYZ sxyz,
                  const WsEventPair *ev = nullptr, WsSched sched = WsSched{});

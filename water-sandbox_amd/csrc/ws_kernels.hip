@@ -581,6 +581,134 @@ void wsk_refresh_pred(hipStream_t s, const WsDev &d, WsSoA cur)
 }
 
 // ---------------------------------------------------------------------------------
+// ws_apply_forces: the emitters' acceleration as one explicit Euler step on the velocities (never inside ws_step)
+//
+// include/wsfluid.h pins every operation; IEEE arithmetic whatever the handle's flags.  The emitters are a by-value kernel
+// argument (768 B): the loop over them is wave-uniform and reads them through scalar loads -- no LDS, no device buffer.
+// Returns whether any emitter saw the particle (v is replaced only then: an unseen particle keeps its bits).  COUNTS: one
+// ballot per emitter and wave, one atomic per wave that saw anything.  Every lane of the wave must call.
+// ---------------------------------------------------------------------------------
+template <bool COUNTS>
+__device__ __forceinline__ bool forces_eval(const WsForceSet &fs, uint32_t k, float dt, bool active, const float4 &p, float4 &v,
+                                            uint32_t *__restrict__ affected)
+{
+    float ax = 0.f, ay = 0.f, az = 0.f;
+    bool hit = false;
+    for (uint32_t e = 0; e < k; e++) {
+        const ws_force &f = fs.e[e];
+        const float qx = p.x - f.centre[0], qy = p.y - f.centre[1], qz = p.z - f.centre[2];
+        const float dst = sqrtf(qx * qx + qy * qy + qz * qz);
+        const bool in = active && dst < f.radius;
+        if constexpr (COUNTS) {
+            const uint32_t c = (uint32_t)__popcll(__ballot(in));
+            if (c && (threadIdx.x & 63u) == 0u) atomicAdd(&affected[e], c);
+        }
+        if (!in) continue;
+        hit = true;
+        const float w = 1.f - dst / f.radius, s = f.strength * w;
+        if (f.kind == WS_FORCE_RADIAL) {
+            if (dst > 0.f) {
+                ax = ax - (qx / dst) * s;
+                ay = ay - (qy / dst) * s;
+                az = az - (qz / dst) * s;
+            }
+        } else if (f.kind == WS_FORCE_JET) {
+            ax = ax + f.axis[0] * s;
+            ay = ay + f.axis[1] * s;
+            az = az + f.axis[2] * s;
+        } else {
+            const float tx = f.axis[1] * qz - f.axis[2] * qy;
+            const float ty = f.axis[2] * qx - f.axis[0] * qz;
+            const float tz = f.axis[0] * qy - f.axis[1] * qx;
+            ax = ax + tx * s;
+            ay = ay + ty * s;
+            az = az + tz * s;
+        }
+        const float g = f.damping * w;
+        ax = ax - v.x * g;
+        ay = ay - v.y * g;
+        az = az - v.z * g;
+    }
+    if (hit) {
+        v.x = v.x + dt * ax;
+        v.y = v.y + dt * ay;
+        v.z = v.z + dt * az;
+    }
+    return hit;
+}
+
+// Single-GPU handles: one lane per slot of `cur` in the order the last step left it (two 16-byte loads of consecutive
+// records), then what k_refresh_pred and k_bin would do in two more passes: the predicted position in registers, its
+// cell, cid[i] and the velocity record's w lane, the per-cell count and the particle's rank in it -- one atomic per run
+// of lanes that share a cell, as the force kernel's epilogue draws them.  The velocity record goes out as one 16-byte
+// store; cur.pred is not stored (k_reorder<true> and k_refresh_pred recompute it from the record).
+template <bool COUNTS>
+__global__ void __launch_bounds__(WS_BLOCK) k_apply_forces(WsDev d, WsSoA cur, uint32_t *__restrict__ cid,
+                                                           uint32_t *__restrict__ count, WsForceSet fs, uint32_t k, float dt,
+                                                           uint32_t *__restrict__ affected)
+{
+    const uint32_t i = blockIdx.x * WS_BLOCK + threadIdx.x;
+    const bool active = i < d.n;
+    float4 p = make_float4(0.f, 0.f, 0.f, 0.f), v = p;
+    if (active) {
+        p = cur.pos(i);
+        v = cur.vel(i);
+    }
+    forces_eval<COUNTS>(fs, k, dt, active, p, v, affected);
+    uint32_t c = 0;
+    if (active) {
+        c = grid_cell(d, p.x + v.x * WS_LOOKAHEAD, p.y + v.y * WS_LOOKAHEAD, p.z + v.z * WS_LOOKAHEAD);
+        cid[i] = c;
+        cur.vel(i) = make_float4(v.x, v.y, v.z, __uint_as_float(c));
+    }
+    const uint32_t r = wave_run_atomic_inc(count, c, active);
+    if (active && cur.rank) cur.rank[i] = r;
+}
+
+void wsk_apply_forces(hipStream_t s, const WsDev &d, WsSoA cur, uint32_t *cid, uint32_t *count, const WsForceSet &fs, uint32_t k,
+                      float dt, uint32_t *affected)
+{
+    if (!d.n) return;
+    const dim3 grid(cdiv(d.n, WS_BLOCK)), block(WS_BLOCK);
+    if (affected)
+        hipLaunchKernelGGL(k_apply_forces<true>, grid, block, 0, s, d, cur, cid, count, fs, k, dt, affected);
+    else
+        hipLaunchKernelGGL(k_apply_forces<false>, grid, block, 0, s, d, cur, cid, count, fs, k, dt, affected);
+}
+
+// Slab handles: the same definition on the gathered {id, pos, vel, pred} records of every rank (blockIdx.y = source rank,
+// the layout k_slab_select<2> reads), edited in place: velocity, and the predicted position by the library's own rule.
+template <bool COUNTS>
+__global__ void __launch_bounds__(WS_BLOCK) k_apply_forces_records(uint32_t *__restrict__ all, const uint32_t *__restrict__ cnt,
+                                                                   uint32_t max_n, size_t stride_words, WsForceSet fs, uint32_t k,
+                                                                   float dt, uint32_t *__restrict__ affected)
+{
+    const uint32_t t = blockIdx.x * WS_BLOCK + threadIdx.x, r = blockIdx.y;
+    const bool active = t < min(cnt[4 * r], max_n);
+    float *f = reinterpret_cast<float *>(all + (size_t)r * stride_words + (size_t)t * 10u + 1u);
+    float4 p = make_float4(0.f, 0.f, 0.f, 0.f), v = p;
+    if (active) {
+        p = make_float4(f[0], f[1], f[2], 0.f);
+        v = make_float4(f[3], f[4], f[5], 0.f);
+    }
+    forces_eval<COUNTS>(fs, k, dt, active, p, v, affected);
+    if (!active) return;
+    f[3] = v.x; f[4] = v.y; f[5] = v.z;
+    f[6] = p.x + v.x * WS_LOOKAHEAD; f[7] = p.y + v.y * WS_LOOKAHEAD; f[8] = p.z + v.z * WS_LOOKAHEAD;
+}
+
+void wsk_apply_forces_records(hipStream_t s, uint32_t *all, const uint32_t *cnt, uint32_t world, uint32_t max_n,
+                              size_t stride_words, const WsForceSet &fs, uint32_t k, float dt, uint32_t *affected)
+{
+    if (!max_n) return;
+    const dim3 grid(cdiv(max_n, WS_BLOCK), world), block(WS_BLOCK);
+    if (affected)
+        hipLaunchKernelGGL(k_apply_forces_records<true>, grid, block, 0, s, all, cnt, max_n, stride_words, fs, k, dt, affected);
+    else
+        hipLaunchKernelGGL(k_apply_forces_records<false>, grid, block, 0, s, all, cnt, max_n, stride_words, fs, k, dt, affected);
+}
+
+// ---------------------------------------------------------------------------------
 // smoothing kernels, assets/simulation.wgsl:93-117 (evaluation order as written)
 // ---------------------------------------------------------------------------------
 __device__ __forceinline__ float sk_density(const WsDev &d, float dst)

@@ -1139,6 +1139,108 @@ ws_status slab_regrid(ws_handle *h, const ws_params *params, bool rebalance)
     return WS_OK;
 }
 
+// ws_apply_forces on slab handles (COLLECTIVE).  The re-grid's route on the UNCHANGED geometry: gather the state, run the
+// definition on the gathered global set on every rank (a pure per-particle function: the same records and the same
+// global counts everywhere), and reload the owned set from the edited records -- ownership follows the new predicted
+// position, exactly as a host edit through ws_write_particles would have it.  No array is freed or allocated.  (A kernel
+// applied in place to the steady-state arrays would have to undo migration decisions the force epilogue has already
+// packed; the form that moves only the particles in reach is the scale-out follow-up: DESIGN.md 9.6.)
+// The call mutates state, so its verdict is made common before anything is touched: bit 0 of the agreed word = this rank
+// refuses, the rest = a hash of k, dt and the emitters' bytes.
+ws_status slab_apply_forces(ws_handle *h, const ws_force *f, uint32_t k, float dt, uint32_t *out_affected)
+{
+    WsSlab *S = h->slab;
+    const uint32_t W = S->world;
+    size_t stride = 0;
+    uint32_t max_n = 0;
+    ws_status st = slab_gather(h, WS_PACK_STATE_H, &stride, &max_n);  // (also brings every rank's capacity: S->caps)
+    if (st) return st;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    const char *why = forces_refusal(f, k, dt);
+    const ws_status st_cnt = !why && out_affected ? forces_counters(h) : WS_OK;  // (this rank's alone: it refuses for all)
+    uint32_t word = 2166136261u;  // FNV-1a
+    const auto mix = [&word](const void *p, size_t bytes) {
+        for (size_t b = 0; b < bytes; b++) word = (word ^ static_cast<const uint8_t *>(p)[b]) * 16777619u;
+    };
+    mix(&k, 4);
+    mix(&dt, 4);
+    if (!why) mix(f, (size_t)k * sizeof(ws_force));
+    word = (word << 1) | ((why || st_cnt) ? 1u : 0u);
+    bool anybody = false, differ = false;
+    if (W > 1) {
+        std::vector<uint32_t> tab;
+        st = slab_agree_words(h, word, &tab);
+        if (st) return st;
+        for (uint32_t r = 0; r < W; r++) {
+            anybody = anybody || (tab[4 * r] & 1u);
+            differ = differ || (tab[4 * r] >> 1) != (word >> 1);
+        }
+    }
+    if (why) return fail(h, WS_ERR_INVALID_ARG, why);
+    if (st_cnt) return st_cnt;
+    if (anybody) return fail(h, WS_ERR_INVALID_ARG, "forces: another slab refused its arguments; nothing was changed");
+    if (differ) return fail(h, WS_ERR_INVALID_ARG, "forces: the slabs were given different emitters; nothing was changed");
+    WsForceSet fs{};
+    memcpy(fs.e, f, (size_t)k * sizeof(ws_force));
+    uint32_t *recs = const_cast<uint32_t *>(slab_gathered(S));  // (scratch of the gather: nothing the step reads)
+    // the edit, and the x-layer histogram of the edited set: every slab's owned count under the cuts against every slab's
+    // capacity, all alike, before the old state is given up (slab_regrid).  A failure in here is this rank's alone and is
+    // made common before anybody goes on.
+    const uint32_t nx = (uint32_t)h->dev.gdim_x;
+    std::vector<uint32_t> hist(nx);
+    {
+        hipError_t e = hipSuccess;
+        wsk_apply_forces_records(h->stream, recs, S->cnt_all, W, max_n, stride, fs, k, dt, out_affected ? h->force_cnt : nullptr);
+        if (S->hist_cap < nx) {
+            if (S->hist_dev) S->retired.push_back(S->hist_dev);  // (no hipFree between collectives: slab_grow)
+            S->hist_dev = nullptr;
+            const uint32_t want = std::max(nx, 2u * S->hist_cap);
+            e = hipMalloc(&S->hist_dev, (size_t)want * 4);
+            S->hist_cap = e == hipSuccess ? want : 0u;
+        }
+        if (e == hipSuccess) e = hipMemsetAsync(S->hist_dev, 0, (size_t)nx * 4, h->stream);
+        if (e == hipSuccess) {
+            wsk_slab_layer_hist(h->stream, h->dev, recs, S->cnt_all, W, max_n, stride, S->hist_dev);
+            e = copy_now(h, hist.data(), S->hist_dev, (size_t)nx * 4, hipMemcpyDeviceToHost);
+        }
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e == hipSuccess && out_affected) e = copy_now(h, out_affected, h->force_cnt, (size_t)k * 4, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) (void)hipGetLastError();
+        uint32_t failed = 0;
+        const ws_status st_agree = slab_agree(h, e != hipSuccess ? 1u : 0u, &failed);
+        if (st_agree) return st_agree;
+        if (e != hipSuccess) return fail(h, e == hipErrorOutOfMemory ? WS_ERR_OUT_OF_MEMORY : WS_ERR_HIP, "forces: edit of the gathered state; nothing was changed", e);
+        if (failed) return fail(h, WS_ERR_OUT_OF_MEMORY, "forces: another slab could not edit the gathered state; nothing was changed");
+    }
+    for (uint32_t r = 0; r < W; r++) {
+        uint64_t cnt = 0;
+        for (uint32_t l = S->cuts[r]; l < S->cuts[r + 1] && l < nx; l++) cnt += hist[l];
+        if (cnt > S->caps[r]) {
+            char buf[200];
+            snprintf(buf, sizeof buf, "forces: slab %u would own %llu particles, its capacity is %u (ws_device_cfg.capacity); nothing was changed",
+                     r, (unsigned long long)cnt, S->caps[r]);
+            return fail(h, WS_ERR_OUT_OF_MEMORY, buf);
+        }
+    }
+    // ---- mutation: the re-grid's tail on the unchanged geometry
+    st = slab_load_begin(h);
+    if (!st) {
+        wsk_slab_select(h->stream, h->dev, 2, S->cuts_dev, W, S->rank, recs, 0, max_n, S->cnt_all, stride, h->cur, S->cap, S->dyn);
+        if (hipGetLastError() != hipSuccess) st = fail(h, WS_ERR_HIP, "k_slab_select");
+    }
+    if (!st) st = slab_load_end(h);
+    const std::string reason = h->err;
+    uint32_t failed = 0;
+    const ws_status st_agree = slab_agree(h, st ? 1u : 0u, &failed);
+    if (st || st_agree || failed) {
+        h->dead = true;
+        h->err = st ? "forces: the reload failed after the old state was given up (" + reason + "); the handle is unusable"
+                    : "another slab failed its reload; the handle is unusable";
+        return st ? st : (st_agree ? st_agree : WS_ERR_OUT_OF_MEMORY);
+    }
+    return WS_OK;
+}
+
 // ws_sample_density_* on a slab handle (COLLECTIVE): every rank's current positions all-gathered by id into S->g_out
 // (what ws_read_positions does) and the GLOBAL single-GPU grid, so that the single-GPU binning and sampler run on the
 // whole particle set -- bit-identical to a single handle by construction.  (A ghost-layer sampler that avoids the

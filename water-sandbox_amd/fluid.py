@@ -54,7 +54,7 @@ ABI_SYMBOLS = [
     "ws_extract_aniso_surface", "ws_cast_rays", "ws_cast_camera",
     "ws_read_velocities", "ws_sample_velocity_grid", "ws_sample_velocity_points", "ws_advect_points",
     "ws_default_whitewater_emit_params", "ws_default_whitewater_step_params", "ws_read_whitewater", "ws_emit_whitewater",
-    "ws_step_whitewater",
+    "ws_step_whitewater", "ws_apply_forces",
 ]
 
 
@@ -132,6 +132,24 @@ class WsWhitewaterStepParams(C.Structure):
         ("bubble_min", C.c_uint32),
         ("buoyancy", C.c_float),
         ("drag", C.c_float),
+    ]
+
+
+WS_FORCE_RADIAL, WS_FORCE_JET, WS_FORCE_VORTEX = 0, 1, 2
+WS_MAX_FORCES = 16
+
+
+class WsForce(C.Structure):
+    """ws_force: one emitter of ws_apply_forces -- a puller / pusher, a jet or a vortex with a brake (include/wsfluid.h)."""
+
+    _fields_ = [
+        ("kind", C.c_uint32),
+        ("centre", C.c_float * 3),
+        ("axis", C.c_float * 3),
+        ("radius", C.c_float),
+        ("strength", C.c_float),
+        ("damping", C.c_float),
+        ("reserved", C.c_uint32 * 2),
     ]
 
 
@@ -253,6 +271,7 @@ def bind_library(path):
     L.ws_read_whitewater.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.ws_emit_whitewater.argtypes = [vp, vp, u32, vp, vp, vp, vp, vp]
     L.ws_step_whitewater.argtypes = [vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]
+    L.ws_apply_forces.argtypes = [vp, vp, u32, C.c_float, vp]
     return L
 
 
@@ -505,6 +524,23 @@ def step_whitewater(L, h, check, step, xyz, velocity, life, in_place=False, want
     check(L.ws_step_whitewater(h, C.byref(step), p.ctypes.data, v.ctypes.data, l.ctypes.data, m, op.ctypes.data,
                                ov.ctypes.data, ol.ctypes.data, cls.ctypes.data))
     return op, ov, ol, cls
+
+
+def force(kind, centre, radius, strength, axis=(0.0, 0.0, 0.0), damping=0.0):
+    """One ws_force: kind = WS_FORCE_RADIAL / _JET / _VORTEX (or "radial" / "jet" / "vortex")."""
+    kind = {"radial": WS_FORCE_RADIAL, "jet": WS_FORCE_JET, "vortex": WS_FORCE_VORTEX}.get(kind, kind)
+    return WsForce(kind, (C.c_float * 3)(*centre), (C.c_float * 3)(*axis), radius, strength, damping, (C.c_uint32 * 2)(0, 0))
+
+
+def apply_forces(L, h, check, forces, dt, counts=True):
+    """ws_apply_forces: one Euler step of the emitters' acceleration on the velocities (include/wsfluid.h has the
+    definition).  forces: a WsForce or a sequence of them.  Returns the per-emitter counts of affected particles (k,)
+    uint32, or None with counts=False (a single handle then only enqueues)."""
+    forces = [forces] if isinstance(forces, WsForce) else list(forces)
+    arr = (WsForce * max(len(forces), 1))(*forces)
+    out = np.zeros(max(len(forces), 1), np.uint32) if counts else None
+    check(L.ws_apply_forces(h, C.byref(arr), len(forces), dt, out.ctypes.data if counts else None))
+    return out[:len(forces)] if counts else None
 
 
 def extract_surface(L, h, check, origin, spacing, dims, iso, normals=True, want=True, collective=False, cap=None,
@@ -824,6 +860,12 @@ class FluidWorker:
         """Classify the host's diffuse particles against the current fluid (spray / foam / bubble / dead) and move them by
         step.dt: step = whitewater_step_params(...).  (xyz, velocity, life, class)."""
         return step_whitewater(self._L, self._h, self._check, step, xyz, velocity, life, in_place)
+
+    def apply_forces(self, forces, dt, counts=True):
+        """Push, pull, blow on or stir the fluid between two steps: forces = force(...) or a list of up to 16, applied
+        to the velocities as one Euler step of dt.  The per-emitter counts of affected particles, or None with
+        counts=False (the call then only enqueues)."""
+        return apply_forces(self._L, self._h, self._check, forces, dt, counts)
 
     def steps_done(self):
         return int(self._L.ws_steps_done(self._h))

@@ -445,6 +445,11 @@ class SlabWorker:
         """FluidWorker.step_whitewater over the GLOBAL particle set (COLLECTIVE); want=False: only contribute (None)."""
         return fluid.step_whitewater(self._L, self._h, self._check, step, xyz, velocity, life, in_place, want)
 
+    def apply_forces(self, forces, dt, counts=True):
+        """FluidWorker.apply_forces on the GLOBAL particle set (COLLECTIVE: every rank makes the same call with the same
+        emitters); the counts are global.  counts=False: this rank applies without asking for them (None)."""
+        return fluid.apply_forces(self._L, self._h, self._check, forces, dt, counts)
+
     def read_positions_begin(self, buf):
         assert buf.dtype == np.float32 and buf.shape == (self.n_global, 3) and buf.flags.c_contiguous
         self._check(self._L.ws_read_positions_begin(self._h, buf.ctypes.data))
