@@ -262,6 +262,18 @@ def _near(grid, bins, cen, q):
     return (j, _take(near, keep)) + offsets(j)
 
 
+def accepted_counts(params, x, q, merged=(1, 1, 1)):
+    """How many candidates the restatement accepts at each query of q: the terms iso_field32 sums there."""
+    x = np.ascontiguousarray(x, F32)
+    q = np.ascontiguousarray(q, F32).reshape(-1, 3)
+    grid, bins = _candidates(params, x, q, merged)
+    count = np.zeros(len(q), np.int64)
+    for s0 in range(0, len(q), grid.chunk()):
+        sl = slice(s0, min(len(q), s0 + grid.chunk()))
+        count[sl] = _near(grid, bins, x, q[sl])[1].sum(1)
+    return count
+
+
 def _mul(M, e):
     """u_a = (M_a0 e_x + M_a1 e_y) + M_a2 e_z in float32, M (..., 6) = xx yy zz xy xz yz."""
     xx, yy, zz, xy, xz, yz = (M[..., k] for k in range(6))

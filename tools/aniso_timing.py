@@ -17,6 +17,7 @@ import ctypes as C
 import glob
 import json
 import os
+import re
 import subprocess
 import sys
 import tempfile
@@ -102,7 +103,8 @@ def kernel_medians(trace_dir):
         name = r["Kernel_Name"]
         key = name.split("(")[0].split("<")[0].replace("void ", "").strip()
         if key in ("k_field_bricks", "k_field_points"):
-            key += "_aniso" if "FieldAniso" in name else "_iso"
+            key += {"FieldAniso": "_aniso", "FieldIso": "_iso", "FieldVel": "_vel"}[  # (the candidate source, a whole word)
+                re.search(r"\b(FieldAniso|FieldIso|FieldVel)\b", name.split("(")[0]).group(1)]
         by.setdefault(key, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) * 1e-3)
     return {k: float(np.median(v)) for k, v in by.items()}, {k: len(v) for k, v in by.items()}
 

@@ -14,6 +14,7 @@ import csv
 import glob
 import json
 import os
+import re
 import subprocess
 import sys
 import tempfile
@@ -129,7 +130,7 @@ def main():
     kt = glob.glob(os.path.join(out, "trace", "**", "*_kernel_trace.csv"), recursive=True)[0]
     rows = sorted(csv.DictReader(open(kt)), key=lambda r: int(r["Start_Timestamp"]))
     disp = [(r["Kernel_Name"], (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) * 1e-3) for r in rows
-            if "k_field_bricks" in r["Kernel_Name"] or "k_field_points" in r["Kernel_Name"]]
+            if re.search(r"\bk_field_(bricks|points)<.*\bFieldIso\b", r["Kernel_Name"].split("(")[0])]  # (the density field's)
     cases = json.load(open(cases_path))
     result = []
     k = 0

@@ -18,6 +18,7 @@ import ctypes as C
 import glob
 import json
 import os
+import re
 import subprocess
 import sys
 import tempfile
@@ -73,7 +74,7 @@ def groups(rows):
         body = rows[i:end]
         if not any("k_iso_triangles" in n for n, _ in body):
             continue  # a counts-only call
-        brick = [t for n, t in rows[:i] if "k_field_bricks" in n][-1]
+        brick = [t for n, t in rows[:i] if "k_field_bricks" in n and re.search(r"\bFieldIso\b", n.split("(")[0])][-1]
         scans = [t for n, t in body if "k_scan" in n]
         pick = {"k_field_bricks": brick, "k_iso_count": body[0][1], "scan_v": scans[0], "scan_t": scans[1],
                 "k_iso_totals": [t for n, t in body if "k_iso_totals" in n][0],

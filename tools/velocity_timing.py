@@ -15,6 +15,7 @@ import csv
 import glob
 import json
 import os
+import re
 import subprocess
 import sys
 import tempfile
@@ -24,7 +25,17 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-KERNELS = ("k_velocity_bricks", "k_velocity_points", "k_advect", "k_field_bricks", "k_field_points")
+# The two field kernels serve both fields: an instantiation is told by the kernel's name together with the candidate
+# source among its template arguments (whole word: FieldVel is a prefix of FieldVelCount).
+KERNELS = {"velocity bricks": ("k_field_bricks", "FieldVel"), "velocity points": ("k_field_points", "FieldVel"),
+           "k_advect": ("k_advect", None), "density bricks": ("k_field_bricks", "FieldIso"),
+           "density points": ("k_field_points", "FieldIso")}
+
+
+def is_kernel(name, key):
+    kernel, source = KERNELS[key]
+    head = name.split("(")[0]
+    return re.search(r"\b%s\b" % kernel, head) is not None and (source is None or re.search(r"\b%s\b" % source, head) is not None)
 
 
 def child(out_path, repeats):
@@ -51,17 +62,17 @@ def child(out_path, repeats):
         for name, dims, spacing in (("256x144x144 @ h", (256, 144, 144), h), ("512x288x288 @ h/2", (512, 288, 288), h / np.float32(2))):
             sp = np.full(3, spacing, np.float32)
             nodes = dims[0] * dims[1] * dims[2]
-            case(step, "velocity grid " + name, "k_velocity_bricks", nodes, lambda: w.sample_velocity_grid(origin, sp, dims, density=True))
-            case(step, "density grid " + name, "k_field_bricks", nodes, lambda: w.sample_density_grid(origin, sp, dims))
+            case(step, "velocity grid " + name, "velocity bricks", nodes, lambda: w.sample_velocity_grid(origin, sp, dims, density=True))
+            case(step, "density grid " + name, "density bricks", nodes, lambda: w.sample_density_grid(origin, sp, dims))
             ax = [origin[a] + np.arange(dims[a], dtype=np.float32) * sp[a] for a in range(3)]
             z, y, x = np.meshgrid(ax[2], ax[1], ax[0], indexing="ij")
             q = np.stack([x.ravel(), y.ravel(), z.ravel()], 1).astype(np.float32)
             del x, y, z
-            case(step, "velocity points " + name, "k_velocity_points", nodes, lambda: w.sample_velocity_points(q, density=True))
-            case(step, "density points " + name, "k_field_points", nodes, lambda: w.sample_density_points(q))
+            case(step, "velocity points " + name, "velocity points", nodes, lambda: w.sample_velocity_points(q, density=True))
+            case(step, "density points " + name, "density points", nodes, lambda: w.sample_density_points(q))
             del q
-        case(step, "velocity points 1 M uniform", "k_velocity_points", len(pts), lambda: w.sample_velocity_points(pts, density=True))
-        case(step, "density points 1 M uniform", "k_field_points", len(pts), lambda: w.sample_density_points(pts))
+        case(step, "velocity points 1 M uniform", "velocity points", len(pts), lambda: w.sample_velocity_points(pts, density=True))
+        case(step, "density points 1 M uniform", "density points", len(pts), lambda: w.sample_density_points(pts))
         case(step, "advect 1 M tracers x 1 substep", "k_advect", len(pts), lambda: w.advect_points(march, pts))
     w.close()
     json.dump(cases, open(out_path, "w"))
@@ -78,14 +89,14 @@ def main():
     kt = glob.glob(os.path.join(out, "trace", "**", "*_kernel_trace.csv"), recursive=True)[0]
     rows = sorted(csv.DictReader(open(kt)), key=lambda r: int(r["Start_Timestamp"]))
     disp = [(r["Kernel_Name"], (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) * 1e-3) for r in rows
-            if any(k in r["Kernel_Name"] for k in KERNELS)]
+            if any(is_kernel(r["Kernel_Name"], k) for k in KERNELS)]
     cases = json.load(open(cases_path))
     result = []
     k = 0
     for c in cases:
         ds = disp[k:k + c["repeats"]]
         k += c["repeats"]
-        assert len(ds) == c["repeats"] and all(c["kernel"] in n for n, _ in ds), (c, [n for n, _ in ds])
+        assert len(ds) == c["repeats"] and all(is_kernel(n, c["kernel"]) for n, _ in ds), (c, [n for n, _ in ds])
         us = float(np.median([t for _, t in ds]))
         result.append({"step": c["step"], "what": c["what"], "kernel": c["kernel"], "us": us, "items_per_s": c["items"] / (us * 1e-6)})
     assert k == len(disp), (k, len(disp))

@@ -15,6 +15,7 @@ import csv
 import glob
 import json
 import os
+import re
 import subprocess
 import sys
 import tempfile
@@ -81,7 +82,7 @@ def main():
     kt = glob.glob(os.path.join(out, "trace", "**", "*_kernel_trace.csv"), recursive=True)[0]
     rows = sorted(csv.DictReader(open(kt)), key=lambda r: int(r["Start_Timestamp"]))
     disp = [(r["Kernel_Name"], (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) * 1e-3) for r in rows
-            if any(k in r["Kernel_Name"] for k in KERNELS)]
+            if any(k in r["Kernel_Name"] for k in KERNELS) and not re.search(r"\bk_field_\w+<.*\bFieldVel\b", r["Kernel_Name"].split("(")[0])]
     cases = json.load(open(cases_path))
     result = []
     k = 0

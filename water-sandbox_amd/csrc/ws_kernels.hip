@@ -2880,16 +2880,30 @@ __device__ __forceinline__ void field_pair(const WsDev &d, float ex, float ey, f
     }
 }
 
-// The candidate source of a field kernel: FieldIso (the density sampler: sorted positions, K4's pair term) or FieldAniso
-// (ws_sample_aniso_*: sorted centres and their ellipsoids; points form only).  at(j) = {position, id bits} of sorted
-// candidate j; pair() adds candidate j, which passed the isotropic distance test.
+// The candidate source of a field kernel: FieldIso (the density sampler: sorted positions, K4's pair term), FieldVel (the
+// velocity field, below) or FieldAniso (ws_sample_aniso_*: sorted centres and their ellipsoids).  at(j) = {position, id
+// bits} of sorted candidate j; pair() adds candidate j, which passed the isotropic distance test.
+//
+// A source the brick kernel can stage says so with three more members: chunk, the candidates staged at a time; payload(j),
+// what it stages of candidate j beside position and cell code (staged<GRAD> = whether it stages one at all); and term(),
+// pair() with that payload in place of j.  FieldAniso has none of them: k_field_bricks does not compile over it.
+struct FieldNone {};
 struct FieldIso {
     const float4 *__restrict__ spos;
+    static constexpr uint32_t chunk = 512;  // 8 KiB of LDS per wave
+    using Payload = FieldNone;
+    template <bool GRAD>
+    static constexpr bool staged = false;
     __device__ __forceinline__ float4 at(uint32_t j) const { return spos[j]; }
+    template <bool IEEE, bool GRAD>
+    __device__ __forceinline__ void term(const WsDev &d, float ex, float ey, float ez, float d2, FieldNone, FieldAcc &a) const
+    {
+        field_pair<IEEE, GRAD>(d, ex, ey, ez, d2, a);
+    }
     template <bool IEEE, bool GRAD>
     __device__ __forceinline__ void pair(const WsDev &d, uint32_t, float ex, float ey, float ez, float d2, FieldAcc &a) const
     {
-        field_pair<IEEE, GRAD>(d, ex, ey, ez, d2, a);
+        term<IEEE, GRAD>(d, ex, ey, ez, d2, FieldNone{}, a);
     }
 };
 
@@ -2959,164 +2973,6 @@ __device__ __forceinline__ Acc field_sweep(const WsDev &d, const uint32_t *__res
     return a;
 }
 
-__device__ __forceinline__ void field_store(const FieldAcc &a, size_t at, float *__restrict__ rho, float *__restrict__ grad)
-{
-    if (rho) rho[at] = a.rho;
-    if (grad) {
-        grad[3 * at] = a.gx;
-        grad[3 * at + 1] = a.gy;
-        grad[3 * at + 2] = a.gz;
-    }
-}
-
-// Points form: one lane per query.  GRID = the queries are the nodes of g (node index = lane index, x fastest) -- the
-// grid call's form below one node per cell; otherwise the m points of xyz.
-template <bool IEEE, bool GRAD, bool GRID, class Src>
-__global__ void __launch_bounds__(WS_BLOCK) k_field_points(WsDev d, const uint32_t *__restrict__ start, Src src,
-                                                           const float *__restrict__ xyz, WsFieldGrid g, uint32_t m,
-                                                           float *__restrict__ rho, float *__restrict__ grad)
-{
-    const uint32_t t = blockIdx.x * WS_BLOCK + threadIdx.x;
-    if (t >= m) return;
-    float4 o;
-    if constexpr (GRID) {
-        const uint32_t i = t % g.nx, r = t / g.nx;
-        o = field_node(g, i, r % g.ny, r / g.ny);
-    } else {
-        o = make_float4(xyz[3 * (size_t)t], xyz[3 * (size_t)t + 1], xyz[3 * (size_t)t + 2], 0.f);
-    }
-    field_store(field_sweep<IEEE, GRAD>(d, start, src, o), t, rho, grad);
-}
-
-// Grid form (the hot path): one wave per brick of 4 x 4 x 4 nodes, lane l = node (l & 3, (l >> 2) & 3, l >> 4) of the
-// brick.  The brick's support is the box of cells [first node's cell - 1, last node's cell + 1] per axis (clamped to
-// the grid; cell coordinates are monotone in the node index), i.e. at most 64 z-runs (one per (x, y) column, x
-// slower) when the node spacing is at most h.  The wave stages the runs' candidates into LDS in that order -- which
-// is increasing cell id, then particle id -- a chunk at a time, and every lane tests every staged candidate against
-// its node.  A candidate counts for a node iff it passes the distance test AND lies in the node's own 27 cells (the
-// points form never sees the others; the cell test is made on accepted candidates only), so each node sums the same
-// terms in the same order as the points form: bit-identical.  A brick whose support holds no particle (air) writes
-// zeros without a candidate loop.
-#define FB_CHUNK 512  // staged candidates (8 KiB of LDS per wave)
-#define FB_COLS 64    // z-runs a brick may span (6 x 6 = 36 at spacing h; more only through rounding at exactly h)
-
-// staged candidate: xyz and the cell relative to the brick's first cell, one byte per axis + 1 (w lane)
-__device__ __forceinline__ uint32_t field_pack_cell(int x, int y, int z) { return (uint32_t)((x + 1) << 16 | (y + 1) << 8 | (z + 1)); }
-
-template <bool IEEE, bool GRAD, class Src>
-__global__ void __launch_bounds__(64) k_field_bricks(WsDev d, const uint32_t *__restrict__ start, Src src, WsFieldGrid g,
-                                                     uint32_t bx_n, uint32_t by_n, float *__restrict__ rho,
-                                                     float *__restrict__ grad)
-{
-    __shared__ float4 s_q[FB_CHUNK];
-    __shared__ uint32_t s_pre[FB_COLS + 1], s_b[FB_COLS];
-    const uint32_t lane = threadIdx.x;
-    const uint32_t bid = blockIdx.x;
-    const uint32_t bi = bid % bx_n, bj = (bid / bx_n) % by_n, bk = bid / (bx_n * by_n);
-    const uint32_t i0 = bi * 4u, j0 = bj * 4u, k0 = bk * 4u;
-    const uint32_t i = i0 + (lane & 3u), j = j0 + ((lane >> 2) & 3u), k = k0 + (lane >> 4);
-    const bool valid = i < g.nx && j < g.ny && k < g.nz;
-    const float4 o = field_node(g, i, j, k);
-    // the brick's cell box from its first and last VALID node (wave-uniform)
-    const uint32_t il = min(i0 + 3u, g.nx - 1u), jl = min(j0 + 3u, g.ny - 1u), kl = min(k0 + 3u, g.nz - 1u);
-    const float4 lo = field_node(g, i0, j0, k0), hi = field_node(g, il, jl, kl);
-    const int x0 = max(field_axis_cell(d, 0, lo.x) - 1, 0), x1 = min(field_axis_cell(d, 0, hi.x) + 1, d.dim[0] - 1);
-    const int y0 = max(field_axis_cell(d, 1, lo.y) - 1, 0), y1 = min(field_axis_cell(d, 1, hi.y) + 1, d.dim[1] - 1);
-    const int z0 = max(field_axis_cell(d, 2, lo.z) - 1, 0), z1 = min(field_axis_cell(d, 2, hi.z) + 1, d.dim[2] - 1);
-    const int ny_c = y1 - y0 + 1;
-    const int ncol = (x1 - x0 + 1) * ny_c;
-    const size_t at = ((size_t)k * g.ny + j) * g.nx + i;
-    if (ncol > FB_COLS) {  // (a spacing the host would not send here: take the points form, lane by lane)
-        if (valid) field_store(field_sweep<IEEE, GRAD>(d, start, src, o), at, rho, grad);
-        return;
-    }
-    // the runs: lane c = column c (x slower), then an exclusive scan of their lengths
-    uint32_t len = 0, b = 0;
-    if ((int)lane < ncol) {
-        const int x = x0 + (int)lane / ny_c, y = y0 + (int)lane % ny_c;
-        const uint32_t col = (uint32_t)(x * d.dim[1] + y) * (uint32_t)d.dim[2];
-        b = start[col + z0];
-        len = start[col + z1 + 1] - b;
-    }
-    const uint32_t incl = wave_incl_scan(len);
-    const uint32_t total = __shfl(incl, 63, 64);
-    FieldAcc a = {0.f, 0.f, 0.f, 0.f};
-    if (total != 0u) {
-        s_pre[lane] = incl - len;
-        s_b[lane] = b;
-        if (lane == 0) s_pre[FB_COLS] = total;
-        // this lane's node: its 27 cells, relative to the brick's box (fields >= 0; see field_pack_cell)
-        const uint32_t own = (uint32_t)((field_axis_cell(d, 0, o.x) - x0) << 16 | (field_axis_cell(d, 1, o.y) - y0) << 8 |
-                                        (field_axis_cell(d, 2, o.z) - z0));
-        for (uint32_t base = 0; base < total; base += FB_CHUNK) {
-            const uint32_t cnt = min((uint32_t)FB_CHUNK, total - base);
-            __syncthreads();  // (the previous chunk has been consumed; s_pre / s_b are written)
-            for (uint32_t t = lane; t < cnt; t += 64u) {
-                const uint32_t v = base + t;
-                int lo_c = 0, hi_c = ncol - 1;  // last column whose prefix is <= v (empty columns share a prefix)
-                while (lo_c < hi_c) {
-                    const int mid = (lo_c + hi_c + 1) >> 1;
-                    if (s_pre[mid] <= v) lo_c = mid;
-                    else hi_c = mid - 1;
-                }
-                const float4 q = src.at(s_b[lo_c] + (v - s_pre[lo_c]));
-                const uint32_t code = field_pack_cell(lo_c / ny_c, lo_c % ny_c, field_axis_cell(d, 2, q.z) - z0);
-                s_q[t] = make_float4(q.x, q.y, q.z, __uint_as_float(code));
-            }
-            __syncthreads();
-            for (uint32_t t = 0; t < cnt; t++) {
-                const float4 q = s_q[t];
-                const float ex = q.x - o.x, ey = q.y - o.y, ez = q.z - o.z;
-                const float d2 = ex * ex + ey * ey + ez * ez;
-                if (d2 > d.d2_accept) continue;
-                // in the node's 27 cells: every byte of code - own lies in [0, 2] (guard bit 7 keeps the bytes apart)
-                if ((((__float_as_uint(q.w) | 0x808080u) - own) & 0xFCFCFCu) != 0x808080u) continue;
-                src.template pair<IEEE, GRAD>(d, 0u, ex, ey, ez, d2, a);  // (FieldIso only: see wsk_field_sample)
-            }
-        }
-    }
-    if (valid) field_store(a, at, rho, grad);
-}
-
-template <class Src>
-void field_sample_launch(hipStream_t s, const WsDev &d, const uint32_t *start, Src src, bool ieee, bool grad_on,
-                         const float *xyz, uint32_t m, const float *grid6, const uint32_t *dims, bool bricks, float *rho,
-                         float *grad)
-{
-    WsFieldGrid g = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0u, 0u, 0u};
-    if (grid6) g = {grid6[0], grid6[1], grid6[2], grid6[3], grid6[4], grid6[5], dims[0], dims[1], dims[2]};
-    if (grid6 && bricks) {
-        const uint32_t bx = cdiv(dims[0], 4u), by = cdiv(dims[1], 4u), bz = cdiv(dims[2], 4u);
-        const dim3 grid(bx * by * bz);
-#define FB_LAUNCH(I, G) hipLaunchKernelGGL((k_field_bricks<I, G, Src>), grid, dim3(64), 0, s, d, start, src, g, bx, by, rho, grad)
-        if (ieee) { if (grad_on) FB_LAUNCH(true, true); else FB_LAUNCH(true, false); }
-        else { if (grad_on) FB_LAUNCH(false, true); else FB_LAUNCH(false, false); }
-#undef FB_LAUNCH
-        return;
-    }
-    const dim3 grid(cdiv(m, WS_BLOCK));
-#define FP_LAUNCH(I, G, R) \
-    hipLaunchKernelGGL((k_field_points<I, G, R, Src>), grid, dim3(WS_BLOCK), 0, s, d, start, src, xyz, g, m, rho, grad)
-    if (grid6) {
-        if (ieee) { if (grad_on) FP_LAUNCH(true, true, true); else FP_LAUNCH(true, false, true); }
-        else { if (grad_on) FP_LAUNCH(false, true, true); else FP_LAUNCH(false, false, true); }
-    } else {
-        if (ieee) { if (grad_on) FP_LAUNCH(true, true, false); else FP_LAUNCH(true, false, false); }
-        else { if (grad_on) FP_LAUNCH(false, true, false); else FP_LAUNCH(false, false, false); }
-    }
-#undef FP_LAUNCH
-}
-
-void wsk_field_sample(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, const float4 *smf, bool ieee,
-                      bool grad_on, const float *xyz, uint32_t m, const float *grid6, const uint32_t *dims, bool bricks,
-                      float *rho, float *grad)
-{
-    // The anisotropic field takes the points form on grids too: a brick form of it (the staged candidates' sorted indices
-    // in LDS, M and f loaded for accepted pairs) lost to the points form on sparse C3 at spacing h.
-    if (smf) field_sample_launch(s, d, start, FieldAniso{spos, smf}, ieee, grad_on, xyz, m, grid6, dims, false, rho, grad);
-    else field_sample_launch(s, d, start, FieldIso{spos}, ieee, grad_on, xyz, m, grid6, dims, bricks, rho, grad);
-}
-
 // ---------------------------------------------------------------------------------
 // velocity field and tracer advection (ws_sample_velocity_grid / _points, ws_advect_points; never inside ws_step)
 //
@@ -3163,22 +3019,34 @@ void wsk_field_gather_vel(hipStream_t s, const uint32_t *perm, const float *vxyz
 }
 
 // The candidate source of the velocity field: FieldIso's positions and the velocities in the same order.  GRAD = the
-// momentum sums are wanted; they take the accumulator's gradient lanes.
+// momentum sums are wanted; they take the accumulator's gradient lanes.  A staged candidate is then 32 B (position + cell
+// code, and the velocity), so the chunk is 256 candidates: 8 KiB of LDS per wave, what the density brick stages, and with
+// the run tables 18 one-wave workgroups per CU of 160 KiB -- the residency the density brick runs at.  Without GRAD the
+// chunk stays 256 and no velocity is staged.
 struct FieldVel {
     const float4 *__restrict__ spos;
     const float4 *__restrict__ svel;
+    static constexpr uint32_t chunk = 256;
+    using Payload = float4;
+    template <bool GRAD>
+    static constexpr bool staged = GRAD;
     __device__ __forceinline__ float4 at(uint32_t j) const { return spos[j]; }
+    __device__ __forceinline__ float4 payload(uint32_t j) const { return svel[j]; }
     template <bool IEEE, bool GRAD>
-    __device__ __forceinline__ void pair(const WsDev &d, uint32_t j, float, float, float, float d2, FieldAcc &a) const
+    __device__ __forceinline__ void term(const WsDev &d, float, float, float, float d2, const float4 &v, FieldAcc &a) const
     {
         const float w = sk_density(d, ws_sqrt<IEEE>(d2));
         a.rho += w;
         if constexpr (GRAD) {
-            const float4 v = svel[j];
             a.gx += w * v.x;
             a.gy += w * v.y;
             a.gz += w * v.z;
         }
+    }
+    template <bool IEEE, bool GRAD>
+    __device__ __forceinline__ void pair(const WsDev &d, uint32_t j, float ex, float ey, float ez, float d2, FieldAcc &a) const
+    {
+        term<IEEE, GRAD>(d, ex, ey, ez, d2, GRAD ? svel[j] : float4{}, a);
     }
 };
 
@@ -3196,41 +3064,103 @@ __device__ __forceinline__ void field_store3(float *__restrict__ out, size_t at,
     out[3 * at + 2] = v.z;
 }
 
-// Points form (the definition), one lane per query: the m points of xyz or (GRID) the nodes of g, x fastest.  VEL: the
-// velocity is wanted (vel != nullptr); rho may be nullptr.
-template <bool IEEE, bool VEL, bool GRID>
-__global__ void __launch_bounds__(WS_BLOCK) k_velocity_points(WsDev d, const uint32_t *__restrict__ start, FieldVel src,
-                                                              const float *__restrict__ xyz, WsFieldGrid g, uint32_t m,
-                                                              float *__restrict__ vel, float *__restrict__ rho)
+// the unit normal -g / sqrtf(g . g) of a gradient g (correctly rounded), (0, 0, 0) where g . g == 0
+__device__ __forceinline__ float4 field_unit_normal(float gx, float gy, float gz)
 {
-    const uint32_t t = blockIdx.x * WS_BLOCK + threadIdx.x;
-    if (t >= m) return;
-    float4 o;
-    if constexpr (GRID) {
-        const uint32_t i = t % g.nx, r = t / g.nx;
-        o = field_node(g, i, r % g.ny, r / g.ny);
-    } else {
-        o = make_float4(xyz[3 * (size_t)t], xyz[3 * (size_t)t + 1], xyz[3 * (size_t)t + 2], 0.f);
+    const float gg = gx * gx + gy * gy + gz * gz;
+    float nx = 0.f, ny = 0.f, nz = 0.f;
+    if (gg != 0.f) {
+        const float len = sqrtf(gg);
+        nx = -gx / len;
+        ny = -gy / len;
+        nz = -gz / len;
     }
-    const FieldAcc a = field_sweep<IEEE, VEL>(d, start, src, o);
-    if (rho) rho[t] = a.rho;
-    if constexpr (VEL) field_store3(vel, t, field_velocity(a));
+    return make_float4(nx, ny, nz, 0.f);
 }
 
-// Grid form: k_field_bricks with the velocities staged beside the positions -- one wave per 4 x 4 x 4 brick of nodes, the
-// brick's support runs staged into LDS in canonical order a chunk at a time, every lane testing every staged candidate,
-// a candidate counting for a node iff it passes the distance test and lies in the node's own 27 cells: each node sums
-// the points form's terms in its order, bit-identically.  A staged candidate is 32 B here (position + cell code, and
-// the velocity), so the chunk is 256 candidates: 8 KiB of LDS per wave, what the density brick stages, and with the run
-// tables 18 one-wave workgroups per CU of 160 KiB -- the residency the density brick runs at.
-#define FBV_CHUNK 256
+// ---------------------------------------------------------------------------------
+// the two field kernels, over a candidate source, the queries and what is stored of a query's sums
+// ---------------------------------------------------------------------------------
+// The queries of the points form: the m points of xyz, or the nodes of g (node index = lane index, x fastest) -- the grid
+// call's form below one node per cell.
+struct QueryPoints {
+    const float *__restrict__ xyz;
+    uint32_t m;
+    __device__ __forceinline__ uint32_t count() const { return m; }
+    __device__ __forceinline__ float4 at(uint32_t t) const
+    {
+        return make_float4(xyz[3 * (size_t)t], xyz[3 * (size_t)t + 1], xyz[3 * (size_t)t + 2], 0.f);
+    }
+};
+struct QueryNodes {
+    WsFieldGrid g;
+    __device__ __forceinline__ uint32_t count() const { return g.nx * g.ny * g.nz; }
+    __device__ __forceinline__ float4 at(uint32_t t) const
+    {
+        const uint32_t i = t % g.nx, r = t / g.nx;
+        return field_node(g, i, r % g.ny, r / g.ny);
+    }
+};
 
-template <bool IEEE, bool VEL>
-__global__ void __launch_bounds__(64) k_velocity_bricks(WsDev d, const uint32_t *__restrict__ start, FieldVel src, WsFieldGrid g,
-                                                        uint32_t bx_n, uint32_t by_n, float *__restrict__ vel,
-                                                        float *__restrict__ rho)
+// What a query keeps of its sums, at slot `at`: the density and its gradient (either may be nullptr), or the velocity
+// field's u = M / rho (GRAD: it is wanted, vel != nullptr) and density (may be nullptr).  plain: put() is stores alone, so
+// the brick kernel's fallback makes its own and returns; a store that divides is not duplicated into the fallback but made
+// once, at the kernel's end ("Grid kernel", has the measurement behind the two shapes).
+struct StoreDensity {
+    float *__restrict__ rho;
+    float *__restrict__ grad;
+    static constexpr bool plain = true;
+    template <bool GRAD>
+    __device__ __forceinline__ void put(const FieldAcc &a, size_t at) const
+    {
+        if (rho) rho[at] = a.rho;
+        if (grad) field_store3(grad, at, make_float4(a.gx, a.gy, a.gz, 0.f));
+    }
+};
+struct StoreVelocity {
+    float *__restrict__ vel;
+    float *__restrict__ rho;
+    static constexpr bool plain = false;
+    template <bool GRAD>
+    __device__ __forceinline__ void put(const FieldAcc &a, size_t at) const
+    {
+        if (rho) rho[at] = a.rho;
+        if constexpr (GRAD) field_store3(vel, at, field_velocity(a));
+    }
+};
+
+// Points form (the definition): one lane per query, one field_sweep.
+template <bool IEEE, bool GRAD, class Src, class Query, class Store>
+__global__ void __launch_bounds__(WS_BLOCK) k_field_points(WsDev d, const uint32_t *__restrict__ start, Src src, Query query,
+                                                           Store store)
 {
-    __shared__ float4 s_q[FBV_CHUNK], s_v[VEL ? FBV_CHUNK : 1];
+    const uint32_t t = blockIdx.x * WS_BLOCK + threadIdx.x;
+    if (t >= query.count()) return;
+    store.template put<GRAD>(field_sweep<IEEE, GRAD>(d, start, src, query.at(t)), t);
+}
+
+// Grid form (the hot path): one wave per brick of 4 x 4 x 4 nodes, lane l = node (l & 3, (l >> 2) & 3, l >> 4) of the
+// brick.  The brick's support is the box of cells [first node's cell - 1, last node's cell + 1] per axis (clamped to
+// the grid; cell coordinates are monotone in the node index), i.e. at most 64 z-runs (one per (x, y) column, x
+// slower) when the node spacing is at most h.  The wave stages the runs' candidates into LDS in that order -- which
+// is increasing cell id, then particle id -- Src::chunk at a time, the source's payload beside them, and every lane tests
+// every staged candidate against its node.  A candidate counts for a node iff it passes the distance test AND lies in
+// the node's own 27 cells (the points form never sees the others; the cell test is made on accepted candidates only),
+// so each node sums the same terms in the same order as the points form: bit-identical.  A brick whose support holds no
+// particle (air) writes zeros without a candidate loop.
+#define FB_COLS 64  // z-runs a brick may span (6 x 6 = 36 at spacing h; more only through rounding at exactly h)
+
+// staged candidate: xyz and the cell relative to the brick's first cell, one byte per axis + 1 (w lane)
+__device__ __forceinline__ uint32_t field_pack_cell(int x, int y, int z) { return (uint32_t)((x + 1) << 16 | (y + 1) << 8 | (z + 1)); }
+
+template <bool IEEE, bool GRAD, class Src, class Store>
+__global__ void __launch_bounds__(64) k_field_bricks(WsDev d, const uint32_t *__restrict__ start, Src src, WsFieldGrid g,
+                                                     uint32_t bx_n, uint32_t by_n, Store store)
+{
+    constexpr uint32_t CHUNK = Src::chunk;
+    constexpr bool STAGED = Src::template staged<GRAD>;
+    __shared__ float4 s_q[CHUNK];
+    __shared__ typename Src::Payload s_v[STAGED ? CHUNK : 1];
     __shared__ uint32_t s_pre[FB_COLS + 1], s_b[FB_COLS];
     const uint32_t lane = threadIdx.x;
     const uint32_t bid = blockIdx.x;
@@ -3250,7 +3180,11 @@ __global__ void __launch_bounds__(64) k_velocity_bricks(WsDev d, const uint32_t 
     const size_t at = ((size_t)k * g.ny + j) * g.nx + i;
     FieldAcc a = {0.f, 0.f, 0.f, 0.f};
     if (ncol > FB_COLS) {  // (a spacing the host would not send here: take the points form, lane by lane)
-        if (valid) a = field_sweep<IEEE, VEL>(d, start, src, o);
+        if (valid) a = field_sweep<IEEE, GRAD>(d, start, src, o);
+        if constexpr (Store::plain) {
+            if (valid) store.template put<GRAD>(a, at);
+            return;
+        }
     } else {
         // the runs: lane c = column c (x slower), then an exclusive scan of their lengths
         uint32_t len = 0, b = 0;
@@ -3266,10 +3200,11 @@ __global__ void __launch_bounds__(64) k_velocity_bricks(WsDev d, const uint32_t 
             s_pre[lane] = incl - len;
             s_b[lane] = b;
             if (lane == 0) s_pre[FB_COLS] = total;
+            // this lane's node: its 27 cells, relative to the brick's box (fields >= 0; see field_pack_cell)
             const uint32_t own = (uint32_t)((field_axis_cell(d, 0, o.x) - x0) << 16 | (field_axis_cell(d, 1, o.y) - y0) << 8 |
                                             (field_axis_cell(d, 2, o.z) - z0));
-            for (uint32_t base = 0; base < total; base += FBV_CHUNK) {
-                const uint32_t cnt = min((uint32_t)FBV_CHUNK, total - base);
+            for (uint32_t base = 0; base < total; base += CHUNK) {
+                const uint32_t cnt = min(CHUNK, total - base);
                 __syncthreads();  // (the previous chunk has been consumed; s_pre / s_b are written)
                 for (uint32_t t = lane; t < cnt; t += 64u) {
                     const uint32_t v = base + t;
@@ -3280,10 +3215,10 @@ __global__ void __launch_bounds__(64) k_velocity_bricks(WsDev d, const uint32_t 
                         else hi_c = mid - 1;
                     }
                     const uint32_t idx = s_b[lo_c] + (v - s_pre[lo_c]);
-                    const float4 q = src.spos[idx];
+                    const float4 q = src.at(idx);
                     const uint32_t code = field_pack_cell(lo_c / ny_c, lo_c % ny_c, field_axis_cell(d, 2, q.z) - z0);
                     s_q[t] = make_float4(q.x, q.y, q.z, __uint_as_float(code));
-                    if constexpr (VEL) s_v[t] = src.svel[idx];
+                    if constexpr (STAGED) s_v[t] = src.payload(idx);
                 }
                 __syncthreads();
                 for (uint32_t t = 0; t < cnt; t++) {
@@ -3291,53 +3226,80 @@ __global__ void __launch_bounds__(64) k_velocity_bricks(WsDev d, const uint32_t 
                     const float ex = q.x - o.x, ey = q.y - o.y, ez = q.z - o.z;
                     const float d2 = ex * ex + ey * ey + ez * ez;
                     if (d2 > d.d2_accept) continue;
-                    // in the node's 27 cells: every byte of code - own lies in [0, 2] (k_field_bricks)
+                    // in the node's 27 cells: every byte of code - own lies in [0, 2] (guard bit 7 keeps the bytes apart)
                     if ((((__float_as_uint(q.w) | 0x808080u) - own) & 0xFCFCFCu) != 0x808080u) continue;
-                    const float w = sk_density(d, ws_sqrt<IEEE>(d2));
-                    a.rho += w;
-                    if constexpr (VEL) {
-                        const float4 pv = s_v[t];
-                        a.gx += w * pv.x;
-                        a.gy += w * pv.y;
-                        a.gz += w * pv.z;
-                    }
+                    src.template term<IEEE, GRAD>(d, ex, ey, ez, d2, s_v[STAGED ? t : 0u], a);
                 }
             }
         }
     }
-    if (!valid) return;
-    if (rho) rho[at] = a.rho;
-    if constexpr (VEL) field_store3(vel, at, field_velocity(a));
+    if (valid) store.template put<GRAD>(a, at);
 }
 
-// bricks: the brick kernel (grid only; the host sends grids of spacing <= h on every axis there)
+// Run-time bools as template bools: f is called once, with a std::true_type or std::false_type for every bool given.
+template <class F>
+void ws_dispatch(F &&f)
+{
+    f();
+}
+template <class F, class... Bools>
+void ws_dispatch(F &&f, bool first, Bools... rest)
+{
+    if (first) ws_dispatch([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else ws_dispatch([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+
+// Whether the brick kernel can stage a source: the source declares its chunk.
+template <class Src, class = void>
+constexpr bool field_stageable = false;
+template <class Src>
+constexpr bool field_stageable<Src, std::void_t<decltype(Src::chunk)>> = true;
+
+// One field call: the m points of xyz (grid6 == nullptr), or the grid of grid6 = origin xyz, spacing xyz and dims (m its
+// nodes) -- with the brick kernel where `bricks` (the host sends grids of spacing <= h on every axis there, DESIGN.md
+// 9.4) and the source can be staged, else node by node in the points form.
+template <class Src, class Store>
+void field_launch(hipStream_t s, const WsDev &d, const uint32_t *start, Src src, Store store, bool ieee, bool grad_on,
+                  const float *xyz, uint32_t m, const float *grid6, const uint32_t *dims, bool bricks)
+{
+    const auto points = [&](auto query) {
+        ws_dispatch([&](auto I, auto G) {
+            hipLaunchKernelGGL((k_field_points<I(), G(), Src, decltype(query), Store>), dim3(cdiv(m, WS_BLOCK)),
+                               dim3(WS_BLOCK), 0, s, d, start, src, query, store);
+        }, ieee, grad_on);
+    };
+    if (!grid6) return points(QueryPoints{xyz, m});
+    const WsFieldGrid g = {grid6[0], grid6[1], grid6[2], grid6[3], grid6[4], grid6[5], dims[0], dims[1], dims[2]};
+    if constexpr (field_stageable<Src>) {
+        if (bricks) {
+            const uint32_t bx = cdiv(dims[0], 4u), by = cdiv(dims[1], 4u), bz = cdiv(dims[2], 4u);
+            ws_dispatch([&](auto I, auto G) {
+                hipLaunchKernelGGL((k_field_bricks<I(), G(), Src, Store>), dim3(bx * by * bz), dim3(64), 0, s, d, start,
+                                   src, g, bx, by, store);
+            }, ieee, grad_on);
+            return;
+        }
+    }
+    points(QueryNodes{g});
+}
+
+void wsk_field_sample(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, const float4 *smf, bool ieee,
+                      bool grad_on, const float *xyz, uint32_t m, const float *grid6, const uint32_t *dims, bool bricks,
+                      float *rho, float *grad)
+{
+    // The anisotropic field takes the points form on grids too (FieldAniso declares no chunk): a brick form of it (the
+    // staged candidates' sorted indices in LDS, M and f loaded for accepted pairs) lost to the points form on sparse C3 at
+    // spacing h.
+    const StoreDensity store = {rho, grad};
+    if (smf) field_launch(s, d, start, FieldAniso{spos, smf}, store, ieee, grad_on, xyz, m, grid6, dims, bricks);
+    else field_launch(s, d, start, FieldIso{spos}, store, ieee, grad_on, xyz, m, grid6, dims, bricks);
+}
+
 void wsk_velocity_sample(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, const float4 *svel, bool ieee,
                          const float *xyz, uint32_t m, const float *grid6, const uint32_t *dims, bool bricks, float *vel,
                          float *rho)
 {
-    WsFieldGrid g = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0u, 0u, 0u};
-    if (grid6) g = {grid6[0], grid6[1], grid6[2], grid6[3], grid6[4], grid6[5], dims[0], dims[1], dims[2]};
-    const FieldVel src = {spos, svel};
-    if (grid6 && bricks) {
-        const uint32_t bx = cdiv(dims[0], 4u), by = cdiv(dims[1], 4u), bz = cdiv(dims[2], 4u);
-        const dim3 bgrid(bx * by * bz);
-#define VB_LAUNCH(I, V) hipLaunchKernelGGL((k_velocity_bricks<I, V>), bgrid, dim3(64), 0, s, d, start, src, g, bx, by, vel, rho)
-        if (ieee) { if (vel) VB_LAUNCH(true, true); else VB_LAUNCH(true, false); }
-        else { if (vel) VB_LAUNCH(false, true); else VB_LAUNCH(false, false); }
-#undef VB_LAUNCH
-        return;
-    }
-    const dim3 grid(cdiv(m, WS_BLOCK));
-#define VP_LAUNCH(I, V, R) \
-    hipLaunchKernelGGL((k_velocity_points<I, V, R>), grid, dim3(WS_BLOCK), 0, s, d, start, src, xyz, g, m, vel, rho)
-    if (grid6) {
-        if (ieee) { if (vel) VP_LAUNCH(true, true, true); else VP_LAUNCH(true, false, true); }
-        else { if (vel) VP_LAUNCH(false, true, true); else VP_LAUNCH(false, false, true); }
-    } else {
-        if (ieee) { if (vel) VP_LAUNCH(true, true, false); else VP_LAUNCH(true, false, false); }
-        else { if (vel) VP_LAUNCH(false, true, false); else VP_LAUNCH(false, false, false); }
-    }
-#undef VP_LAUNCH
+    field_launch(s, d, start, FieldVel{spos, svel}, StoreVelocity{vel, rho}, ieee, vel != nullptr, xyz, m, grid6, dims, bricks);
 }
 
 // k_advect, one lane per tracer: a plain loop of midpoint steps through the frozen field, each sample one field_sweep --
@@ -3375,13 +3337,10 @@ void wsk_advect(hipStream_t s, const WsDev &d, const uint32_t *start, const floa
 {
     const FieldVel src = {spos, svel};
     const float hdt = 0.5f * dt;
-    const dim3 grid(cdiv(m, WS_BLOCK));
-#define AD_LAUNCH(I, F) \
-    hipLaunchKernelGGL((k_advect<I, F>), grid, dim3(WS_BLOCK), 0, s, d, start, src, pts, m, dt, hdt, substeps, vel, rho)
-    const bool field = vel || rho;
-    if (ieee) { if (field) AD_LAUNCH(true, true); else AD_LAUNCH(true, false); }
-    else { if (field) AD_LAUNCH(false, true); else AD_LAUNCH(false, false); }
-#undef AD_LAUNCH
+    ws_dispatch([&](auto I, auto F) {
+        hipLaunchKernelGGL((k_advect<I(), F()>), dim3(cdiv(m, WS_BLOCK)), dim3(WS_BLOCK), 0, s, d, start, src, pts, m, dt,
+                           hdt, substeps, vel, rho);
+    }, ieee, vel || rho);
 }
 
 // ---------------------------------------------------------------------------------
@@ -3407,15 +3366,7 @@ __global__ void __launch_bounds__(WS_BLOCK) k_whitewater_normals(WsDev d, const 
     const uint32_t i = blockIdx.x * WS_BLOCK + threadIdx.x;
     if (i >= n) return;
     const FieldAcc g = field_sweep<true, true>(d, start, FieldIso{spos}, spos[i]);
-    const float gg = g.gx * g.gx + g.gy * g.gy + g.gz * g.gz;
-    float nx = 0.f, ny = 0.f, nz = 0.f;
-    if (gg != 0.f) {
-        const float len = sqrtf(gg);
-        nx = -g.gx / len;
-        ny = -g.gy / len;
-        nz = -g.gz / len;
-    }
-    snrm[i] = make_float4(nx, ny, nz, 0.f);
+    snrm[i] = field_unit_normal(g.gx, g.gy, g.gz);
 }
 
 // Pass B's accumulator and candidate source: positions, velocities and normals in cell order, and the query particle's
@@ -3591,23 +3542,19 @@ void wsk_whitewater_spawn(hipStream_t s, const WsWhiteEmit &e, const float *pxyz
 }
 
 // The velocity field's source with a count lane: FieldVel's terms, the same bits, and the number of accepted candidates.
-struct WhiteVelAcc {
-    float rho, gx, gy, gz;
+// It holds a FieldVel rather than being one: it declares no chunk, so the brick kernel, whose sums have no count lane,
+// does not compile over it.
+struct FieldCountAcc : FieldAcc {
     uint32_t c;
 };
 struct FieldVelCount {
-    const float4 *__restrict__ spos;
-    const float4 *__restrict__ svel;
-    __device__ __forceinline__ float4 at(uint32_t j) const { return spos[j]; }
+    FieldVel vel;
+    __device__ __forceinline__ float4 at(uint32_t j) const { return vel.at(j); }
     template <bool IEEE, bool GRAD>
-    __device__ __forceinline__ void pair(const WsDev &d, uint32_t j, float, float, float, float d2, WhiteVelAcc &a) const
+    __device__ __forceinline__ void pair(const WsDev &d, uint32_t j, float ex, float ey, float ez, float d2,
+                                         FieldCountAcc &a) const
     {
-        const float w = sk_density(d, ws_sqrt<IEEE>(d2));
-        const float4 v = svel[j];
-        a.rho += w;
-        a.gx += w * v.x;
-        a.gy += w * v.y;
-        a.gz += w * v.z;
+        vel.pair<IEEE, GRAD>(d, j, ex, ey, ez, d2, a);
         a.c++;
     }
 };
@@ -3624,8 +3571,9 @@ __global__ void __launch_bounds__(WS_BLOCK) k_whitewater_step(WsDev d, const uin
     float p[3] = {pts[3 * (size_t)t], pts[3 * (size_t)t + 1], pts[3 * (size_t)t + 2]};
     float v[3] = {vel[3 * (size_t)t], vel[3 * (size_t)t + 1], vel[3 * (size_t)t + 2]};
     float l = life[t];
-    const WhiteVelAcc a = field_sweep<IEEE, true, FieldVelCount, WhiteVelAcc>(d, start, src, make_float4(p[0], p[1], p[2], 0.f));
-    const float4 u4 = field_velocity(FieldAcc{a.rho, a.gx, a.gy, a.gz});
+    const FieldCountAcc a =
+        field_sweep<IEEE, true, FieldVelCount, FieldCountAcc>(d, start, src, make_float4(p[0], p[1], p[2], 0.f));
+    const float4 u4 = field_velocity(a);
     const float u[3] = {u4.x, u4.y, u4.z};
     uint32_t kind;
     if (a.c < sp.spray_max) {
@@ -3667,10 +3615,11 @@ __global__ void __launch_bounds__(WS_BLOCK) k_whitewater_step(WsDev d, const uin
 void wsk_whitewater_step(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, const float4 *svel, bool ieee,
                          const WsWhiteStep &sp, float *pts, float *vel, float *life, uint8_t *cls, uint32_t m)
 {
-    const FieldVelCount src = {spos, svel};
-    const dim3 grid(cdiv(m, WS_BLOCK)), block(WS_BLOCK);
-    if (ieee) hipLaunchKernelGGL(k_whitewater_step<true>, grid, block, 0, s, d, start, src, sp, pts, vel, life, cls, m);
-    else hipLaunchKernelGGL(k_whitewater_step<false>, grid, block, 0, s, d, start, src, sp, pts, vel, life, cls, m);
+    const FieldVelCount src = {{spos, svel}};
+    ws_dispatch([&](auto I) {
+        hipLaunchKernelGGL(k_whitewater_step<I()>, dim3(cdiv(m, WS_BLOCK)), dim3(WS_BLOCK), 0, s, d, start, src, sp, pts, vel,
+                           life, cls, m);
+    }, ieee);
 }
 
 // ---------------------------------------------------------------------------------
@@ -3779,22 +3728,12 @@ __global__ void __launch_bounds__(WS_BLOCK) k_ray_cast(WsDev d, const uint32_t *
     }
     const bool hit = valid && st.t != INFINITY;
     if constexpr (NORMALS) {
-        float nx = 0.f, ny = 0.f, nz = 0.f;
+        float4 n = make_float4(0.f, 0.f, 0.f, 0.f);
         if (hit) {
             const FieldAcc g = field_sweep<IEEE, true>(d, start, src, ray_point(o, v, st.t));
-            const float gg = g.gx * g.gx + g.gy * g.gy + g.gz * g.gz;
-            if (gg != 0.f) {
-                const float len = sqrtf(gg);
-                nx = -g.gx / len;
-                ny = -g.gy / len;
-                nz = -g.gz / len;
-            }
+            n = field_unit_normal(g.gx, g.gy, g.gz);
         }
-        if (valid) {
-            out_n[3 * at] = nx;
-            out_n[3 * at + 1] = ny;
-            out_n[3 * at + 2] = nz;
-        }
+        if (valid) field_store3(out_n, at, n);
     }
     if (valid && out_t) out_t[at] = st.t;
 }
@@ -3803,12 +3742,10 @@ template <class Src, class Rays>
 void ray_cast_launch(hipStream_t s, const WsDev &d, const uint32_t *start, Src src, Rays rays,
                      uint32_t lanes, const ws_ray_params &r, bool ieee, float *out_t, float *out_n)
 {
-    const dim3 grid(cdiv(lanes, WS_BLOCK));
-#define RC_LAUNCH(I, N) \
-    hipLaunchKernelGGL((k_ray_cast<I, N, Src, Rays>), grid, dim3(WS_BLOCK), 0, s, d, start, src, rays, r, out_t, out_n)
-    if (ieee) { if (out_n) RC_LAUNCH(true, true); else RC_LAUNCH(true, false); }
-    else { if (out_n) RC_LAUNCH(false, true); else RC_LAUNCH(false, false); }
-#undef RC_LAUNCH
+    ws_dispatch([&](auto I, auto N) {
+        hipLaunchKernelGGL((k_ray_cast<I(), N(), Src, Rays>), dim3(cdiv(lanes, WS_BLOCK)), dim3(WS_BLOCK), 0, s, d, start, src,
+                           rays, r, out_t, out_n);
+    }, ieee, out_n != nullptr);
 }
 
 void wsk_ray_cast(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, const float4 *smf,
@@ -4134,17 +4071,10 @@ __global__ void __launch_bounds__(WS_BLOCK) k_iso_vertices(const float *__restri
             const float gx = grad[3 * (size_t)n] + t * (grad[3 * (size_t)m] - grad[3 * (size_t)n]);
             const float gy = grad[3 * (size_t)n + 1] + t * (grad[3 * (size_t)m + 1] - grad[3 * (size_t)n + 1]);
             const float gz = grad[3 * (size_t)n + 2] + t * (grad[3 * (size_t)m + 2] - grad[3 * (size_t)n + 2]);
-            const float gg = gx * gx + gy * gy + gz * gz;
-            float nx = 0.f, ny = 0.f, nz = 0.f;
-            if (gg != 0.f) {
-                const float len = sqrtf(gg);
-                nx = -gx / len;
-                ny = -gy / len;
-                nz = -gz / len;
-            }
-            nrm[at] = nx;
-            nrm[at + 1] = ny;
-            nrm[at + 2] = nz;
+            const float4 nh = field_unit_normal(gx, gy, gz);
+            nrm[at] = nh.x;
+            nrm[at + 1] = nh.y;
+            nrm[at + 2] = nh.z;
         }
         v++;
     }
