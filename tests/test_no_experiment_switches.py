@@ -76,6 +76,15 @@ def test_product_build_defines_nothing():
     assert re.findall(r'"-D(\w+)', src) == ["WS_WITH_REFCHECK", "WS_DEV_HOOKS"]  # the two test-only libraries alone
 
 
+def test_host_code_allocates_and_frees_through_the_two_owner_forms_only():
+    """Every device and page-locked allocation of a handle has one owner, a WsScratch or a WsGroup (csrc/ws_internal.h,
+    DESIGN.md 2), and those two are the only host code that allocates or frees: no hand-kept free list can miss an array."""
+    for f in ("ws_api.cpp", "ws_slab.inc", "ws_field.inc"):
+        text = open(os.path.join(CSRC, f)).read()
+        for call in ("hipMalloc(", "hipFree(", "hipHostMalloc(", "hipHostFree("):
+            assert call not in text, "%s calls %s...)" % (f, call)
+
+
 @pytest.mark.skipif(shutil.which("patch") is None, reason="no patch(1)")
 @pytest.mark.parametrize("name", PATCHES)
 def test_experiment_patches_still_apply(name):

@@ -55,6 +55,19 @@ ws_status fail(ws_handle *h, ws_status st, const char *what, hipError_t e = hipS
             return fail(h, e_ == hipErrorOutOfMemory ? WS_ERR_OUT_OF_MEMORY : WS_ERR_HIP, #expr, e_); \
     } while (0)
 
+// The same inside ws_create / ws_slab_create, where a failure gives the half-built handle up through the function's `bail`.
+#define CREATE_TRY(expr)                  \
+    do {                                  \
+        ws_status s_ = (expr);            \
+        if (s_) return bail(s_);          \
+    } while (0)
+#define CREATE_HIP(expr)                                                                   \
+    do {                                                                                   \
+        hipError_t e_ = (expr);                                                            \
+        if (e_ != hipSuccess)                                                              \
+            return bail(fail(h, e_ == hipErrorOutOfMemory ? WS_ERR_OUT_OF_MEMORY : WS_ERR_HIP, #expr, e_)); \
+    } while (0)
+
 // A host <-> device copy on the HANDLE'S OWN stream, complete on return.  Never the legacy (null) stream: it
 // synchronises implicitly with streams that are none of this handle's business, and it fails outright
 // (hipErrorStreamCaptureImplicit) while any other thread of the host is capturing a hipGraph -- another handle with
@@ -92,6 +105,17 @@ float accept_threshold(float h)
     }
     return t;
 }
+
+}  // namespace
+
+// what the two owner forms of ws_internal.h (WsScratch, WsGroup) report when HIP refuses them memory
+ws_status ws_alloc_failed(ws_handle *h, const char *what, hipError_t e)
+{
+    (void)hipGetLastError();
+    return fail(h, e == hipErrorOutOfMemory ? WS_ERR_OUT_OF_MEMORY : WS_ERR_HIP, what, e);
+}
+
+namespace {
 
 bool is_pow2(uint32_t n) { return n && !(n & (n - 1)); }
 
@@ -193,11 +217,9 @@ ws_status derive_dev(ws_handle *h, const ws_params &p, uint32_t n, WsDev *out)
 
 void free_grid(ws_handle *h)
 {
-    hipFree(h->count);
-    hipFree(h->cursor);
-    hipFree(h->start_alloc);
-    hipFree(h->bsum);
-    h->count = h->cursor = h->start = h->start_alloc = h->bsum = nullptr;
+    h->cells.release();
+    h->starts.release();
+    h->start = nullptr;  // (the shifted alias of start_alloc)
     h->grid_alloc_cells = 0;
 }
 
@@ -206,22 +228,22 @@ ws_status alloc_grid(ws_handle *h)
     const WsDev &d = h->dev;
     // (developer builds: WS_FAIL_REGRID=1 makes a RE-grid's allocation fail -- the tests' way to a dead handle)
     if (h->steps > 0 && WS_DEV_ENV("WS_FAIL_REGRID")) return fail(h, WS_ERR_OUT_OF_MEMORY, "cell tables: allocation failure forced by WS_FAIL_REGRID");
+    ws_status st = WS_OK;
     if (h->grid_alloc_cells < d.ncells) {
         free_grid(h);
-        HIP_TRY(h, hipMalloc(&h->count, (size_t)d.ncells * 4));
-        HIP_TRY(h, hipMalloc(&h->cursor, (size_t)d.ncells * 4));
+        if ((st = h->cells.alloc(h, &h->count, (size_t)d.ncells * 4, "cell counts"))) return st;
+        if ((st = h->cells.alloc(h, &h->cursor, (size_t)d.ncells * 4, "cell cursors"))) return st;
         h->grid_alloc_cells = d.ncells;
     }
     // start is sized by the guard too, which depends on the dims: always (re)build it
-    hipFree(h->start_alloc);
-    hipFree(h->bsum);
-    h->start = h->start_alloc = h->bsum = nullptr;
+    h->starts.release();
+    h->start = nullptr;
     const size_t nstart = (size_t)d.ncells + 2 * (size_t)d.guard + 2;
     // the scan writes start's body (from entry `guard`) 16 B at a time: shift the array so that entry is aligned
-    HIP_TRY(h, hipMalloc(&h->start_alloc, (nstart + 4) * 4));
+    if ((st = h->starts.alloc(h, &h->start_alloc, (nstart + 4) * 4, "cell starts"))) return st;
     h->start = h->start_alloc + (4u - (uint32_t)d.guard % 4u) % 4u;
-    HIP_TRY(h, hipMalloc(&h->bsum, (size_t)wsk_scan_state_words(d.ncells) * 4));
-    HIP_TRY(h, hipMemsetAsync(h->bsum, 0, (size_t)wsk_scan_state_words(d.ncells) * 4, h->stream));  // same stream as its users
+    // (zeroed on the same stream as its users)
+    if ((st = h->starts.alloc(h, &h->bsum, (size_t)wsk_scan_state_words(d.ncells) * 4, "cell scan state", true))) return st;
     // constant parts of cell_start: front guard = 0, [ncells] and the back guard = n
     HIP_TRY(h, hipMemsetAsync(h->start, 0, (size_t)d.guard * 4, h->stream));
     std::vector<uint32_t> tail((size_t)d.guard + 2, d.n);
@@ -267,7 +289,10 @@ ws_status upload_mult(ws_handle *h)
                 m[(dx + 1) * 9 + (dy + 1) * 3 + (dz + 1)] = (uint8_t)(cnt ? cnt : 1);
             }
     h->alias = alias;
-    if (!h->mult) HIP_TRY(h, hipMalloc(&h->mult, 32));
+    if (!h->mult) {
+        const ws_status st = h->fixed.alloc(h, &h->mult, 32, "stencil multiplicities");
+        if (st) return st;
+    }
     HIP_TRY(h, copy_now(h, h->mult, m, 27, hipMemcpyHostToDevice));
     return WS_OK;
 }
@@ -279,15 +304,13 @@ void configure_kernels(ws_handle *h)
     h->ieee = (h->flags & WS_FLAG_IEEE_DIVISION) != 0;
 }
 
+// The staging buffer of uploads and readbacks, at least `bytes` large.  ws_handle::stage is what the calls read and write:
+// the alias of stage_mem.p, refreshed here, the one place that grows it.
 ws_status ensure_stage(ws_handle *h, size_t bytes)
 {
-    if (h->stage_bytes >= bytes) return WS_OK;
-    hipFree(h->stage);
-    h->stage = nullptr;
-    h->stage_bytes = 0;
-    HIP_TRY(h, hipMalloc(&h->stage, bytes));
-    h->stage_bytes = bytes;
-    return WS_OK;
+    const ws_status st = h->stage_mem.grow(h, bytes, "staging buffer");
+    h->stage = h->stage_mem.p;
+    return st;
 }
 
 // A handle whose re-grid failed after the old tables were given up (h->dead; ws_set_params, slab_regrid): its cell
@@ -438,12 +461,8 @@ void free_schedule(ws_handle *h)
     }
     if (h->ev_sched_in) hipEventDestroy(h->ev_sched_in);
     if (h->ev_sched_out) hipEventDestroy(h->ev_sched_out);
-    hipFree(h->sched4[0].cost);  // (shared by both of K4's sets)
-    for (int k = 0; k < 2; k++) {
-        hipFree(h->sched4[k].split); hipFree(h->sched4[k].perm);
-        hipFree(h->sched5[k].split); hipFree(h->sched5[k].perm); hipFree(h->sched5[k].cost);
-        h->sched4[k] = h->sched5[k] = WsSched{};
-    }
+    h->sched.release();
+    h->sched4[1].cost = nullptr;  // (the alias of sched4[0].cost)
     h->sched_stream = nullptr;
     h->ev_sched_in = h->ev_sched_out = nullptr;
     h->sched_on = false;
@@ -462,18 +481,19 @@ ws_status alloc_schedule(ws_handle *h)
     if (const char *v = WS_DEV_ENV("WS_SCHED_GROUP")) h->sched_group = (uint32_t)atoi(v);
     h->sched_tiles4 = (h->n + wsk_density_tile() - 1u) / wsk_density_tile();
     h->sched_tiles5 = (h->n + wsk_force_tile(h->n) - 1u) / wsk_force_tile(h->n);
-    uint32_t *cost4 = nullptr;
-    HIP_TRY(h, hipMalloc(&cost4, (size_t)h->sched_tiles4 * 4));
-    HIP_TRY(h, hipMemsetAsync(cost4, 0, (size_t)h->sched_tiles4 * 4, h->stream));
-    for (int k = 0; k < 2; k++) {
-        h->sched4[k].cost = cost4;
-        HIP_TRY(h, hipMalloc(&h->sched4[k].split, 16 * 4));
-        HIP_TRY(h, hipMalloc(&h->sched4[k].perm, (size_t)h->sched_tiles4 * 4));
-        HIP_TRY(h, hipMalloc(&h->sched5[k].split, 16 * 4));
-        HIP_TRY(h, hipMalloc(&h->sched5[k].perm, (size_t)h->sched_tiles5 * 4));
-        HIP_TRY(h, hipMalloc(&h->sched5[k].cost, (size_t)h->sched_tiles5 * 4));
-        HIP_TRY(h, hipMemsetAsync(h->sched5[k].cost, 0, (size_t)h->sched_tiles5 * 4, h->stream));
+    const size_t t4 = (size_t)h->sched_tiles4 * 4, t5 = (size_t)h->sched_tiles5 * 4;
+    WsGroup &G = h->sched;
+    // K4's two sets share one cost array, owned once (through set 0); the costs start at zero
+    ws_status st = G.alloc(h, &h->sched4[0].cost, t4, "tile costs", true);
+    h->sched4[1].cost = h->sched4[0].cost;
+    for (int k = 0; k < 2 && !st; k++) {
+        st = G.alloc(h, &h->sched4[k].split, 16 * 4, "tile schedule");
+        if (!st) st = G.alloc(h, &h->sched4[k].perm, t4, "tile schedule");
+        if (!st) st = G.alloc(h, &h->sched5[k].split, 16 * 4, "tile schedule");
+        if (!st) st = G.alloc(h, &h->sched5[k].perm, t5, "tile schedule");
+        if (!st) st = G.alloc(h, &h->sched5[k].cost, t5, "tile costs", true);
     }
+    if (st) return st;
     HIP_TRY(h, hipStreamCreateWithFlags(&h->sched_stream, hipStreamNonBlocking));
     HIP_TRY(h, hipEventCreateWithFlags(&h->ev_sched_in, hipEventDisableTiming));
     HIP_TRY(h, hipEventCreateWithFlags(&h->ev_sched_out, hipEventDisableTiming));
@@ -617,20 +637,36 @@ void drop_graphs(ws_handle *h)
     if (h->slab) slab_drop_graphs(h->slab);
 }
 
+// The particle arrays of a handle: `slots` particle slots (n on a single handle; ghosts | capacity | ghosts on a slab), and
+// accept masks of `mask_particles` particles per row (n; on a slab the owned capacity: ghosts have no masks).
+ws_status alloc_particle_arrays(ws_handle *h, size_t slots, uint32_t mask_particles)
+{
+    // +16 entries: phase 1 trips read up to U-1 slots past a run's end (masked, but must be mapped)
+    const size_t n16 = (slots + 16) * 16, n4 = slots * 4;
+    WsGroup &G = h->particles;
+    ws_status st = G.alloc(h, &h->cur.pv, 2 * n16, "particle records");
+    if (!st) st = G.alloc(h, &h->cur.pred, n16, "predicted positions");
+    if (!st) st = G.alloc(h, &h->cur.rank, n4, "cell ranks");
+    if (!st) st = G.alloc(h, &h->srt.pos, n16, "sorted positions");
+    if (!st) st = G.alloc(h, &h->srt.pv, 2 * n16, "sorted records");
+    for (float **plane : {&h->sxyz.x, &h->sxyz.y, &h->sxyz.z})
+        if (!st) st = G.alloc(h, plane, n16 / 4, "sorted position planes", true);
+    if (!st) st = G.alloc(h, &h->cid_cur, n4, "cell ids");
+    if (!st) st = G.alloc(h, &h->cid_srt, n4, "sorted cell ids");
+    if (!st) st = G.alloc(h, &h->accel, n16, "accelerations");
+    if (!st) st = G.alloc(h, &h->slot_tmp, n4, "sort slots");
+    if (!st && h->variant == WS_VARIANT_LISTED) {
+        h->mask.stride = mask_particles;
+        st = G.alloc(h, &h->mask.words, (size_t)wsk_mask_words() * mask_particles * 4, "accept masks");
+    }
+    return st;
+}
+
 void free_particle_arrays(ws_handle *h)
 {
     drop_graphs(h);
-    hipFree(h->cur.pv); hipFree(h->cur.pred); hipFree(h->cur.rank);
-    hipFree(h->srt.pos); hipFree(h->srt.pv);
-    hipFree(h->sxyz.x); hipFree(h->sxyz.y); hipFree(h->sxyz.z);
-    hipFree(h->cid_cur); hipFree(h->cid_srt); hipFree(h->accel);
-    hipFree(h->slot_tmp); hipFree(h->mask.words);
-    h->cur = WsSoA{};
-    h->srt = WsSorted{};
-    h->sxyz = WsXYZ{};
-    h->cid_cur = h->cid_srt = h->slot_tmp = nullptr;
-    h->accel = nullptr;
-    h->mask = WsMask{nullptr, 0};
+    h->particles.release();
+    h->mask.stride = 0;
 }
 
 void free_all(ws_handle *h)
@@ -643,16 +679,13 @@ void free_all(ws_handle *h)
     free_schedule(h);
     if (h->rb_gathered) hipEventDestroy(h->rb_gathered);
     if (h->rb_done) hipEventDestroy(h->rb_done);
-    hipFree(h->rb_stage);
-    for (float *b : h->rb_host)
-        if (b) hipHostFree(b);
+    release_all(h->rb_stage, h->rb_host[0], h->rb_host[1]);
     drain_profile(h);
     for (auto e : h->pool) hipEventDestroy(e);
     free_grid(h);
     free_particle_arrays(h);
-    hipFree(h->stats); hipFree(h->mult); hipFree(h->stage); hipFree(h->force_cnt);
-    hipFree(h->v_keys); hipFree(h->v_perm); hipFree(h->v_tmp); hipFree(h->v_count);
-    hipFree(h->v_cursor); hipFree(h->v_start); hipFree(h->v_bsum); hipFree(h->v_off);
+    release_all(h->fixed, h->stage_mem, h->force_cnt, h->v_keys, h->v_perm, h->v_tmp, h->v_count, h->v_cursor, h->v_start, h->v_bsum,
+                h->v_off);
     free_field(h);
 #ifdef WS_WITH_REFCHECK
     ref_free(h);
@@ -810,17 +843,6 @@ ws_status ws_create(const ws_params *params, const float *pos_xyz, uint32_t n, c
         delete h;
         return s;
     };
-#define CREATE_TRY(expr)                  \
-    do {                                  \
-        ws_status s_ = (expr);            \
-        if (s_) return bail(s_);          \
-    } while (0)
-#define CREATE_HIP(expr)                                                                   \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return bail(fail(h, e_ == hipErrorOutOfMemory ? WS_ERR_OUT_OF_MEMORY : WS_ERR_HIP, #expr, e_)); \
-    } while (0)
 
     CREATE_HIP(hipSetDevice(device));
     CREATE_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
@@ -834,31 +856,12 @@ ws_status ws_create(const ws_params *params, const float *pos_xyz, uint32_t n, c
         return WS_OK;
     }
 #endif
-    // +16 entries: phase 1 trips read up to U-1 slots past a run's end (masked, but must be mapped)
-    const size_t n16 = ((size_t)n + 16) * 16;
-    CREATE_HIP(hipMalloc(&h->cur.pv, 2 * n16));
-    CREATE_HIP(hipMalloc(&h->cur.pred, n16));
-    CREATE_HIP(hipMalloc(&h->cur.rank, (size_t)n * 4));
-    CREATE_HIP(hipMalloc(&h->srt.pos, n16));
-    CREATE_HIP(hipMalloc(&h->srt.pv, 2 * n16));
-    CREATE_HIP(hipMalloc(&h->sxyz.x, n16 / 4)); CREATE_HIP(hipMalloc(&h->sxyz.y, n16 / 4)); CREATE_HIP(hipMalloc(&h->sxyz.z, n16 / 4));
-    CREATE_HIP(hipMemsetAsync(h->sxyz.x, 0, n16 / 4, h->stream)); CREATE_HIP(hipMemsetAsync(h->sxyz.y, 0, n16 / 4, h->stream)); CREATE_HIP(hipMemsetAsync(h->sxyz.z, 0, n16 / 4, h->stream));
-    CREATE_HIP(hipMalloc(&h->cid_cur, (size_t)n * 4));
-    CREATE_HIP(hipMalloc(&h->cid_srt, (size_t)n * 4));
-    CREATE_HIP(hipMalloc(&h->accel, n16));
-    CREATE_HIP(hipMalloc(&h->slot_tmp, (size_t)n * 4));
-    if (h->variant == WS_VARIANT_LISTED) {
-        h->mask.stride = n;
-        CREATE_HIP(hipMalloc(&h->mask.words, (size_t)wsk_mask_words() * n * 4));
-    }
-    CREATE_HIP(hipMalloc(&h->stats, 64));
-    CREATE_HIP(hipMemsetAsync(h->stats, 0, 64, h->stream));
+    CREATE_TRY(alloc_particle_arrays(h, n, n));
+    CREATE_TRY(h->fixed.alloc(h, &h->stats, 64, "device counters", true));
     CREATE_TRY(alloc_grid(h));
     CREATE_TRY(upload_mult(h));
     CREATE_TRY(upload_positions(h, pos_xyz));
     CREATE_TRY(alloc_schedule(h));
-#undef CREATE_TRY
-#undef CREATE_HIP
     *out = h;
     return WS_OK;
 }
@@ -1072,18 +1075,16 @@ ws_status ws_read_positions_begin(ws_handle *h, float *out_xyz)
     }
     const bool owned = out_xyz == nullptr;
     if (owned) {
-        if (h->rb_host_bytes < bytes) {
-            for (float *&b : h->rb_host) {
-                if (b) hipHostFree(b);
-                b = nullptr;
-            }
-            h->rb_host_bytes = 0;
+        if (h->rb_host[1].bytes < bytes) {  // (the pair has one size: [1] is allocated last)
+            release_all(h->rb_host[0], h->rb_host[1]);
             h->rb_last = -1;
-            for (float *&b : h->rb_host) HIP_TRY(h, hipHostMalloc((void **)&b, bytes, hipHostMallocDefault));
-            h->rb_host_bytes = bytes;
+            for (auto &b : h->rb_host) {
+                const ws_status st = b.alloc(h, bytes, "page-locked readback buffer");
+                if (st) return st;
+            }
         }
         h->rb_fill = h->rb_last == 0 ? 1 : 0;  // never the buffer the host may still be reading
-        out_xyz = h->rb_host[h->rb_fill];
+        out_xyz = h->rb_host[h->rb_fill].p;
     }
     const float *src;
     if (h->slab) {
@@ -1091,18 +1092,13 @@ ws_status ws_read_positions_begin(ws_handle *h, float *out_xyz)
         // the id-ordered result overlaps with the steps enqueued after this call, as on a single handle
         const ws_status st = slab_gather_by_id(h, WS_PACK_POS_H);
         if (st) return st;
-        src = reinterpret_cast<const float *>(h->slab->g_out);
+        src = reinterpret_cast<const float *>(h->slab->g_out.p);
     } else {
-        if (h->rb_bytes < bytes) {
-            hipFree(h->rb_stage);
-            h->rb_stage = nullptr;
-            h->rb_bytes = 0;
-            HIP_TRY(h, hipMalloc(&h->rb_stage, bytes));
-            h->rb_bytes = bytes;
-        }
-        wsk_gather_positions(h->stream, h->cur, h->rb_stage, h->n);
+        const ws_status st = h->rb_stage.grow(h, bytes, "readback staging buffer");
+        if (st) return st;
+        wsk_gather_positions(h->stream, h->cur, h->rb_stage.p, h->n);
         HIP_TRY(h, hipGetLastError());
-        src = h->rb_stage;
+        src = h->rb_stage.p;
     }
     HIP_TRY(h, hipEventRecord(h->rb_gathered, h->stream));
     HIP_TRY(h, hipStreamWaitEvent(h->copy_stream, h->rb_gathered, 0));
@@ -1133,7 +1129,7 @@ ws_status ws_read_positions_view(ws_handle *h, const float **out_xyz)
     if (!h || !out_xyz) return WS_ERR_INVALID_ARG;
     *out_xyz = nullptr;
     if (h->rb_last < 0) return fail(h, WS_ERR_INVALID_ARG, "no finished readback into the library's buffers (ws_read_positions_begin(h, NULL) / _end)");
-    *out_xyz = h->rb_host[h->rb_last];
+    *out_xyz = h->rb_host[h->rb_last].p;
     return WS_OK;
 }
 
@@ -1170,7 +1166,7 @@ ws_status ws_read_velocities(ws_handle *h, float *out_xyz)
         if (st) return st;
         if (out_xyz) {
             if ((st = ensure_stage(h, bytes))) return st;
-            wsk_field_split(h->stream, reinterpret_cast<const float *>(h->slab->g_out), nullptr, (float *)h->stage, n);
+            wsk_field_split(h->stream, reinterpret_cast<const float *>(h->slab->g_out.p), nullptr, (float *)h->stage, n);
             HIP_TRY(h, hipGetLastError());
             HIP_TRY(h, hipMemcpyAsync(out_xyz, h->stage, bytes, hipMemcpyDeviceToHost, h->stream));
         }
@@ -1289,8 +1285,9 @@ const char *forces_refusal(const ws_force *f, uint32_t k, float dt)
 // the k per-emitter counters on the device, zeroed on the handle's stream
 ws_status forces_counters(ws_handle *h)
 {
-    if (!h->force_cnt) HIP_TRY(h, hipMalloc(&h->force_cnt, WS_MAX_FORCES * 4));
-    HIP_TRY(h, hipMemsetAsync(h->force_cnt, 0, WS_MAX_FORCES * 4, h->stream));
+    const ws_status st = h->force_cnt.grow(h, WS_MAX_FORCES * 4, "force counters");
+    if (st) return st;
+    HIP_TRY(h, hipMemsetAsync(h->force_cnt.p, 0, WS_MAX_FORCES * 4, h->stream));
     return WS_OK;
 }
 
@@ -1317,10 +1314,10 @@ ws_status ws_apply_forces(ws_handle *h, const ws_force *f, uint32_t k, float dt,
         if (st) return st;
     }
     HIP_TRY(h, hipMemsetAsync(h->count, 0, (size_t)h->dev.ncells * 4, h->stream));
-    wsk_apply_forces(h->stream, h->dev, h->cur, h->cid_cur, h->count, fs, k, dt, out_affected ? h->force_cnt : nullptr);
+    wsk_apply_forces(h->stream, h->dev, h->cur, h->cid_cur, h->count, fs, k, dt, out_affected ? h->force_cnt.p : nullptr);
     HIP_TRY(h, hipGetLastError());
     h->pred_stale = true;  // cur.pred is behind the new velocities: k_reorder<true> / refresh_pred recompute it
-    if (out_affected) HIP_TRY(h, copy_now(h, out_affected, h->force_cnt, (size_t)k * 4, hipMemcpyDeviceToHost));
+    if (out_affected) HIP_TRY(h, copy_now(h, out_affected, h->force_cnt.p, (size_t)k * 4, hipMemcpyDeviceToHost));
     return WS_OK;
 }
 
@@ -1337,48 +1334,45 @@ ws_status ws_read_sort_view(ws_handle *h, uint32_t *keys_by_id, uint32_t *perm, 
     const bool stepped = h->slab ? h->steps > h->slab->t0 : h->steps > 0;
     hipStream_t s = h->stream;
     WS_REF_DISPATCH(h, ref_read_sort_view(h, keys_by_id, perm, cell_offsets));
-    if (!h->v_keys) {
-        HIP_TRY(h, hipMalloc(&h->v_keys, (size_t)n * 4));
-        HIP_TRY(h, hipMalloc(&h->v_perm, (size_t)n * 4));
-        HIP_TRY(h, hipMalloc(&h->v_tmp, (size_t)n * 4));
-        HIP_TRY(h, hipMalloc(&h->v_count, (size_t)n * 4));
-        HIP_TRY(h, hipMalloc(&h->v_cursor, (size_t)n * 4));
-        HIP_TRY(h, hipMalloc(&h->v_start, ((size_t)n + 1) * 4));
-        HIP_TRY(h, hipMalloc(&h->v_off, (size_t)n * 4));
-        HIP_TRY(h, hipMalloc(&h->v_bsum, (size_t)wsk_scan_state_words(n) * 4));
-        HIP_TRY(h, hipMemsetAsync(h->v_bsum, 0, (size_t)wsk_scan_state_words(n) * 4, h->stream));
-        HIP_TRY(h, copy_now(h, h->v_start + n, &n, 4, hipMemcpyHostToDevice));
+    if (!h->v_bsum.p) {  // (allocated last: it is there only if all eight are)
+        ws_status st = WS_OK;
+        for (auto *v : {&h->v_keys, &h->v_perm, &h->v_tmp, &h->v_count, &h->v_cursor, &h->v_off})
+            if ((st = v->alloc(h, (size_t)n * 4, "sort view"))) return st;
+        if ((st = h->v_start.alloc(h, ((size_t)n + 1) * 4, "sort view"))) return st;
+        if ((st = h->v_bsum.alloc(h, (size_t)wsk_scan_state_words(n) * 4, "sort view"))) return st;
+        HIP_TRY(h, hipMemsetAsync(h->v_bsum.p, 0, (size_t)wsk_scan_state_words(n) * 4, h->stream));
+        HIP_TRY(h, copy_now(h, h->v_start.p + n, &n, 4, hipMemcpyHostToDevice));
     }
     if (!stepped) {
         // src/fluid_compute.rs:306-308: all three buffers start as the identity
         if (h->slab) HIP_TRY(h, hipStreamSynchronize(s));
-        wsk_iota(s, h->v_keys, n);
+        wsk_iota(s, h->v_keys.p, n);
         HIP_TRY(h, hipGetLastError());
         HIP_TRY(h, hipStreamSynchronize(s));
         for (uint32_t *dst : {keys_by_id, perm, cell_offsets})
-            if (dst) HIP_TRY(h, copy_now(h, dst, h->v_keys, (size_t)n * 4, hipMemcpyDeviceToHost));
+            if (dst) HIP_TRY(h, copy_now(h, dst, h->v_keys.p, (size_t)n * 4, hipMemcpyDeviceToHost));
         return WS_OK;
     }
-    HIP_TRY(h, hipMemsetAsync(h->v_count, 0, (size_t)n * 4, s));
-    const uint32_t *keys = h->v_keys;
+    HIP_TRY(h, hipMemsetAsync(h->v_count.p, 0, (size_t)n * 4, s));
+    const uint32_t *keys = h->v_keys.p;
     if (h->slab) {
         const ws_status st = slab_gather_by_id(h, WS_PACK_KEY_H);
         if (st) return st;
-        keys = h->slab->g_out;
-        wsk_view_count(s, keys, h->v_count, n);
+        keys = h->slab->g_out.p;
+        wsk_view_count(s, keys, h->v_count.p, n);
     } else {
         // the predicted positions the last step started from live in the sorted copy
-        wsk_view_keys(s, h->dev, h->srt, h->v_keys, h->v_count);
+        wsk_view_keys(s, h->dev, h->srt, h->v_keys.p, h->v_count.p);
     }
-    wsk_scan(s, h->v_count, h->v_start, h->v_cursor, h->v_bsum, n, false, 0);
-    wsk_scatter(s, keys, h->v_cursor, h->v_tmp, n, nullptr);
-    wsk_view_fix(s, h->v_tmp, keys, h->v_start, h->v_perm, n);
-    wsk_view_offsets(s, h->v_start, h->v_off, n);
+    wsk_scan(s, h->v_count.p, h->v_start.p, h->v_cursor.p, h->v_bsum.p, n, false, 0);
+    wsk_scatter(s, keys, h->v_cursor.p, h->v_tmp.p, n, nullptr);
+    wsk_view_fix(s, h->v_tmp.p, keys, h->v_start.p, h->v_perm.p, n);
+    wsk_view_offsets(s, h->v_start.p, h->v_off.p, n);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipStreamSynchronize(s));
     if (keys_by_id) HIP_TRY(h, copy_now(h, keys_by_id, keys, (size_t)n * 4, hipMemcpyDeviceToHost));
-    if (perm) HIP_TRY(h, copy_now(h, perm, h->v_perm, (size_t)n * 4, hipMemcpyDeviceToHost));
-    if (cell_offsets) HIP_TRY(h, copy_now(h, cell_offsets, h->v_off, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (perm) HIP_TRY(h, copy_now(h, perm, h->v_perm.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (cell_offsets) HIP_TRY(h, copy_now(h, cell_offsets, h->v_off.p, (size_t)n * 4, hipMemcpyDeviceToHost));
     return WS_OK;
 }
 

@@ -10,35 +10,11 @@
 // (SURVEY 8(f) row 2: readback / render coupling.)
 
 // ---- scratch ---------------------------------------------------------------------------------------------------------
-// An allocation of the layer: a failure is WS_ERR_OUT_OF_MEMORY and leaves no sticky HIP error behind (the next ws_step
-// checks hipGetLastError), so the handle stays usable.
-template <class T>
-ws_status WsScratch<T>::alloc(ws_handle *h, size_t need)
-{
-    release();
-    const hipError_t e = hipMalloc(reinterpret_cast<void **>(&p), std::max<size_t>(need, 4));
-    if (e == hipSuccess) {
-        bytes = need;
-        return WS_OK;
-    }
-    (void)hipGetLastError();
-    p = nullptr;
-    return fail(h, WS_ERR_OUT_OF_MEMORY, "density field scratch", e);
-}
-
-template <class T>
-ws_status WsScratch<T>::grow(ws_handle *h, size_t need)
-{
-    return bytes >= need ? WS_OK : alloc(h, need);
-}
-
+// Every allocation of the layer is a WsScratch of ws_handle::field (ws_internal.h): a failure leaves no sticky HIP error
+// behind (the next ws_step checks hipGetLastError), so the handle stays usable.
 namespace {
 
-template <class... S>
-void release_all(S &...s)
-{
-    (s.release(), ...);
-}
+constexpr const char *kFieldScratch = "density field scratch";
 
 void free_field_cells(ws_handle *h)
 {
@@ -64,11 +40,11 @@ ws_status field_alloc(ws_handle *h, uint32_t n, uint32_t ncells)
     ws_status st = WS_OK;
     if (F.n != n) {
         free_field(h);
-        if (!h->slab) st = F.xyz.alloc(h, (size_t)n * 12);
-        if (!st) st = F.keys.alloc(h, (size_t)n * 4);
-        if (!st) st = F.tmp.alloc(h, (size_t)n * 4);
-        if (!st) st = F.perm.alloc(h, (size_t)n * 4);
-        if (!st) st = F.spos.alloc(h, (size_t)n * 16);
+        if (!h->slab) st = F.xyz.alloc(h, (size_t)n * 12, kFieldScratch);
+        if (!st) st = F.keys.alloc(h, (size_t)n * 4, kFieldScratch);
+        if (!st) st = F.tmp.alloc(h, (size_t)n * 4, kFieldScratch);
+        if (!st) st = F.perm.alloc(h, (size_t)n * 4, kFieldScratch);
+        if (!st) st = F.spos.alloc(h, (size_t)n * 16, kFieldScratch);
         if (st) {
             free_field(h);
             return st;
@@ -78,10 +54,10 @@ ws_status field_alloc(ws_handle *h, uint32_t n, uint32_t ncells)
     if (F.cells != ncells) {  // (new handle, or a re-grid since the last call)
         free_field_cells(h);
         const size_t sw = (size_t)wsk_scan_state_words(ncells) * 4;
-        st = F.count.alloc(h, (size_t)ncells * 4);
-        if (!st) st = F.cursor.alloc(h, (size_t)ncells * 4);
-        if (!st) st = F.start.alloc(h, ((size_t)ncells + 1) * 4);
-        if (!st) st = F.bsum.alloc(h, sw);
+        st = F.count.alloc(h, (size_t)ncells * 4, kFieldScratch);
+        if (!st) st = F.cursor.alloc(h, (size_t)ncells * 4, kFieldScratch);
+        if (!st) st = F.start.alloc(h, ((size_t)ncells + 1) * 4, kFieldScratch);
+        if (!st) st = F.bsum.alloc(h, sw, kFieldScratch);
         if (!st && hipMemsetAsync(F.bsum.p, 0, sw, h->stream) != hipSuccess) st = fail(h, WS_ERR_HIP, "density field scan state");
         if (!st && hipMemcpyAsync(F.start.p + ncells, &n, 4, hipMemcpyHostToDevice, h->stream) != hipSuccess)
             st = fail(h, WS_ERR_HIP, "density field cell starts");
@@ -159,7 +135,7 @@ ws_status field_check(ws_handle *h, const FieldQuery &q)
 ws_status field_upload(ws_handle *h, const FieldQuery &q)
 {
     auto &F = h->field;
-    const ws_status st = F.q.grow(h, (size_t)q.m * 12);
+    const ws_status st = F.q.grow(h, (size_t)q.m * 12, kFieldScratch);
     if (st) return st;
     HIP_TRY(h, hipMemcpyAsync(F.q.p, q.xyz, (size_t)q.m * 12, hipMemcpyHostToDevice, h->stream));
     return WS_OK;
@@ -246,10 +222,10 @@ ws_status field_source(ws_handle *h, FieldCtx *c, FieldInputs inputs, Check chec
         c->pos = F.xyz.p;
     }
     if (vel) {
-        if ((st = F.vxyz.grow(h, n * 12))) return st;
-        if ((st = F.svel.grow(h, n * 16))) return st;
+        if ((st = F.vxyz.grow(h, n * 12, kFieldScratch))) return st;
+        if ((st = F.svel.grow(h, n * 16, kFieldScratch))) return st;
         if (h->slab) {
-            if ((st = F.vpos.grow(h, n * 12))) return st;
+            if ((st = F.vpos.grow(h, n * 12, kFieldScratch))) return st;
             wsk_field_split(s, c->pos, F.vpos.p, F.vxyz.p, c->n);
             c->pos = F.vpos.p;
         } else {
@@ -292,9 +268,9 @@ ws_status field_aniso_stage(ws_handle *h, const FieldCtx &c, const ws_aniso_para
     auto &F = h->field;
     const size_t n = c.n;
     ws_status st;
-    if ((st = F.cxyz.grow(h, n * 12))) return st;
-    if ((st = F.amf.grow(h, n * 32))) return st;
-    if ((st = F.anb.grow(h, n * 4))) return st;
+    if ((st = F.cxyz.grow(h, n * 12, kFieldScratch))) return st;
+    if ((st = F.amf.grow(h, n * 32, kFieldScratch))) return st;
+    if ((st = F.anb.grow(h, n * 4, kFieldScratch))) return st;
     const WsAnisoParams a = {ap->smoothing, ap->max_ratio, ap->lone_scale, ap->min_neighbours};
     wsk_aniso(h->stream, c.d, F.start.p, F.spos.p, a, F.cxyz.p, F.amf.p, F.anb.p, c.n);
     HIP_TRY(h, hipGetLastError());
@@ -307,7 +283,7 @@ ws_status field_aniso_bin(ws_handle *h, const FieldCtx &c)
 {
     auto &F = h->field;
     ws_status st;
-    if ((st = F.smf.grow(h, (size_t)c.n * 32))) return st;
+    if ((st = F.smf.grow(h, (size_t)c.n * 32, kFieldScratch))) return st;
     if ((st = field_bin(h, c, F.cxyz.p))) return st;
     wsk_aniso_gather(h->stream, F.perm.p, F.cxyz.p, F.amf.p, F.spos.p, F.smf.p, c.n);
     HIP_TRY(h, hipGetLastError());
@@ -331,8 +307,8 @@ ws_status field_sample(ws_handle *h, const FieldCtx &c, const FieldQuery &q, Fie
     const uint64_t nq = q.count();
     ws_status st;
     if (!q.grid && (st = field_upload(h, q))) return st;
-    if (rho && (st = rho->grow(h, (size_t)nq * 4))) return st;
-    if (grad && (st = grad->grow(h, (size_t)nq * 12))) return st;
+    if (rho && (st = rho->grow(h, (size_t)nq * 4, kFieldScratch))) return st;
+    if (grad && (st = grad->grow(h, (size_t)nq * 12, kFieldScratch))) return st;
     wsk_field_sample(h->stream, c.d, F.start.p, F.spos.p, kind == FIELD_ANISOTROPIC ? F.smf.p : nullptr, h->ieee, grad != nullptr,
                      F.q.p, (uint32_t)nq, q.grid6(), q.dims3(), q.bricks(c.d), rho ? rho->p : nullptr, grad ? grad->p : nullptr);
     HIP_TRY(h, hipGetLastError());
@@ -426,10 +402,10 @@ ws_status extract_surface(ws_handle *h, const FieldQuery &q, FieldKind kind, con
     const uint32_t nb = wsk_iso_blocks(dims);
     const size_t half = ((size_t)nb + 4) & ~(size_t)3;  // nb + 1 totals, 16 B aligned for the scan's uint4 accesses
     const size_t sw = (size_t)wsk_scan_state_words(nb + 1) * 4;
-    if ((st = F.code.grow(h, nodes))) return st;
-    if ((st = F.bcnt.grow(h, 2 * half * 4))) return st;
-    if ((st = F.bstart.grow(h, (2 * half + 4) * 4))) return st;  // (+ the two grand totals)
-    if ((st = F.bstate.grow(h, sw))) return st;
+    if ((st = F.code.grow(h, nodes, kFieldScratch))) return st;
+    if ((st = F.bcnt.grow(h, 2 * half * 4, kFieldScratch))) return st;
+    if ((st = F.bstart.grow(h, (2 * half + 4) * 4, kFieldScratch))) return st;  // (+ the two grand totals)
+    if ((st = F.bstate.grow(h, sw, kFieldScratch))) return st;
     // (the scan's tickets number its launches on a state buffer of a fixed length: fresh state for every call)
     HIP_TRY(h, hipMemsetAsync(F.bstate.p, 0, sw, s));
     wsk_iso_count(s, F.rho.p, grid6, dims, iso, F.code.p, F.bcnt.p, F.bcnt.p + half);
@@ -447,10 +423,10 @@ ws_status extract_surface(ws_handle *h, const FieldQuery &q, FieldKind kind, con
         return WS_OK;
     }
     const size_t V = counts[0], T = counts[1];
-    if ((st = F.vbase.grow(h, nodes * 4))) return st;
-    if ((st = F.mxyz.grow(h, V * 12))) return st;
-    if (grad_on && (st = F.mnrm.grow(h, V * 12))) return st;
-    if ((st = F.tri.grow(h, T * 12))) return st;
+    if ((st = F.vbase.grow(h, nodes * 4, kFieldScratch))) return st;
+    if ((st = F.mxyz.grow(h, V * 12, kFieldScratch))) return st;
+    if (grad_on && (st = F.mnrm.grow(h, V * 12, kFieldScratch))) return st;
+    if ((st = F.tri.grow(h, T * 12, kFieldScratch))) return st;
     wsk_iso_mesh(s, F.rho.p, F.grad.p, grid6, dims, iso, F.code.p, F.bstart.p, F.bstart.p + half, F.vbase.p, F.mxyz.p,
                  grad_on ? F.mnrm.p : nullptr, F.tri.p);
     HIP_TRY(h, hipGetLastError());
@@ -561,10 +537,10 @@ ws_status cast_rays(ws_handle *h, const ws_aniso_params *ap, const ws_ray_params
     hipStream_t s = h->stream;
     auto &F = h->field;
     const size_t nr = q.count();
-    if (out_t && (st = F.ray_t.grow(h, nr * 4))) return st;
-    if (out_n && (st = F.ray_n.grow(h, nr * 12))) return st;
+    if (out_t && (st = F.ray_t.grow(h, nr * 4, kFieldScratch))) return st;
+    if (out_n && (st = F.ray_n.grow(h, nr * 12, kFieldScratch))) return st;
     if (!q.camera) {
-        if ((st = F.rays.grow(h, nr * 24))) return st;
+        if ((st = F.rays.grow(h, nr * 24, kFieldScratch))) return st;
         HIP_TRY(h, hipMemcpyAsync(F.rays.p, q.origin, nr * 12, hipMemcpyHostToDevice, s));
         HIP_TRY(h, hipMemcpyAsync(F.rays.p + 3 * nr, q.dir, nr * 12, hipMemcpyHostToDevice, s));
     }
@@ -591,8 +567,8 @@ ws_status sample_velocity(ws_handle *h, const FieldQuery &q, float *out_vel, flo
     auto &F = h->field;
     const size_t nq = (size_t)q.count();
     if (!q.grid && (st = field_upload(h, q))) return st;
-    if (out_rho && (st = F.rho.grow(h, nq * 4))) return st;
-    if (out_vel && (st = F.grad.grow(h, nq * 12))) return st;
+    if (out_rho && (st = F.rho.grow(h, nq * 4, kFieldScratch))) return st;
+    if (out_vel && (st = F.grad.grow(h, nq * 12, kFieldScratch))) return st;
     wsk_velocity_sample(h->stream, c.d, F.start.p, F.spos.p, F.svel.p, h->ieee, F.q.p, (uint32_t)nq, q.grid6(), q.dims3(),
                         q.bricks(c.d), out_vel ? F.grad.p : nullptr, out_rho ? F.rho.p : nullptr);
     HIP_TRY(h, hipGetLastError());
@@ -626,9 +602,9 @@ ws_status advect_points(ws_handle *h, const ws_advect_params *a, const float *xy
     if (st || c.contributed) return st;
     if ((st = field_bin_particles(h, c))) return st;
     auto &F = h->field;
-    if ((st = F.q.grow(h, (size_t)m * 12))) return st;
-    if (out_rho && (st = F.rho.grow(h, (size_t)m * 4))) return st;
-    if (out_vel && (st = F.grad.grow(h, (size_t)m * 12))) return st;
+    if ((st = F.q.grow(h, (size_t)m * 12, kFieldScratch))) return st;
+    if (out_rho && (st = F.rho.grow(h, (size_t)m * 4, kFieldScratch))) return st;
+    if (out_vel && (st = F.grad.grow(h, (size_t)m * 12, kFieldScratch))) return st;
     HIP_TRY(h, hipMemcpyAsync(F.q.p, xyz, (size_t)m * 12, hipMemcpyHostToDevice, h->stream));
     wsk_advect(h->stream, c.d, F.start.p, F.spos.p, F.svel.p, h->ieee, F.q.p, m, a->dt, a->substeps, out_vel ? F.grad.p : nullptr,
                out_rho ? F.rho.p : nullptr);
@@ -643,9 +619,9 @@ ws_status whitewater_stage(ws_handle *h, const FieldCtx &c)
     auto &F = h->field;
     const size_t n = c.n;
     ws_status st;
-    if ((st = F.wnrm.grow(h, n * 16))) return st;
-    if ((st = F.wst.grow(h, n * 28))) return st;
-    if ((st = F.wnb.grow(h, n * 4))) return st;
+    if ((st = F.wnrm.grow(h, n * 16, kFieldScratch))) return st;
+    if ((st = F.wst.grow(h, n * 28, kFieldScratch))) return st;
+    if ((st = F.wnb.grow(h, n * 4, kFieldScratch))) return st;
     wsk_whitewater_stage(h->stream, c.d, F.start.p, F.spos.p, F.svel.p, F.wnrm.p, F.wst.p, F.wst.p + n, F.wst.p + 2 * n,
                          F.wst.p + 3 * n, F.wst.p + 4 * n, F.wnb.p, (uint32_t)n);
     HIP_TRY(h, hipGetLastError());
@@ -706,9 +682,9 @@ ws_status emit_whitewater(ws_handle *h, const ws_whitewater_emit_params *e, uint
     if (n * e->max_per_particle > 0xFFFFFFFFull) return fail(h, WS_ERR_INVALID_ARG, "whitewater: n * max_per_particle exceeds 2^32 - 1");
     const size_t words = (n + 1 + 3) & ~(size_t)3;  // whole uint4 for the scan
     const size_t sw = (size_t)wsk_scan_state_words((uint32_t)n + 1u) * 4;
-    if ((st = F.wcnt.grow(h, words * 4))) return st;
-    if ((st = F.woff.grow(h, words * 4))) return st;
-    if ((st = F.wstate.grow(h, sw))) return st;
+    if ((st = F.wcnt.grow(h, words * 4, kFieldScratch))) return st;
+    if ((st = F.woff.grow(h, words * 4, kFieldScratch))) return st;
+    if ((st = F.wstate.grow(h, sw, kFieldScratch))) return st;
     // (the scan's tickets number its launches on a state buffer of a fixed length: fresh state for every call)
     HIP_TRY(h, hipMemsetAsync(F.wstate.p, 0, sw, s));
     HIP_TRY(h, hipMemsetAsync(F.wcnt.p, 0, words * 4, s));
@@ -727,7 +703,7 @@ ws_status emit_whitewater(ws_handle *h, const ws_whitewater_emit_params *e, uint
         return WS_OK;
     }
     const size_t T = total;
-    if ((st = F.wout.grow(h, T * 32))) return st;
+    if ((st = F.wout.grow(h, T * 32, kFieldScratch))) return st;
     float *xyz = F.wout.p, *vel = F.wout.p + 3 * T, *life = F.wout.p + 6 * T;
     uint32_t *src = reinterpret_cast<uint32_t *>(F.wout.p + 7 * T);
     // (the positions by id: field_source left them in F.vpos on a slab, in F.xyz on a single handle)
@@ -768,7 +744,7 @@ ws_status step_whitewater(ws_handle *h, const ws_whitewater_step_params *p, cons
     hipStream_t s = h->stream;
     auto &F = h->field;
     const size_t M = m;
-    if ((st = F.wpt.grow(h, M * 28 + M))) return st;
+    if ((st = F.wpt.grow(h, M * 28 + M, kFieldScratch))) return st;
     float *dp = F.wpt.p, *dv = F.wpt.p + 3 * M, *dl = F.wpt.p + 6 * M;
     uint8_t *dc = reinterpret_cast<uint8_t *>(F.wpt.p + 7 * M);
     HIP_TRY(h, hipMemcpyAsync(dp, xyz, M * 12, hipMemcpyHostToDevice, s));

@@ -177,19 +177,101 @@ struct WsEventPair {
     bool counts = true;  // false: the second launch of a kernel id within one step (time is added, the launch count is per step)
 };
 
-// Device scratch of the derived-field layer (csrc/ws_field.inc defines alloc and grow).  A failed allocation is
-// WS_ERR_OUT_OF_MEMORY with the sticky HIP error cleared, p == nullptr and bytes == 0: the handle stays usable.
-template <class T>
+// ---- who owns device memory ------------------------------------------------------------------------------------------
+// Every device allocation and every page-locked host allocation of a ws_handle / WsSlab has exactly ONE owner, of one of
+// the two forms below: the ONLY places of the host code that allocate or free (DESIGN.md 2 lists which lifetime owns
+// what).  Giving a lifetime up is one release() per owner, which cannot miss a member.  Nothing is freed by a destructor:
+// release is an explicit call, made with the handle's device current.
+//
+// A failed allocation (ws_api.cpp ws_alloc_failed) is WS_ERR_OUT_OF_MEMORY when HIP says so, else WS_ERR_HIP; `what`
+// names the buffer in ws_last_error; the sticky HIP error is cleared (the next ws_step checks hipGetLastError), so a
+// handle whose call could not get its scratch stays usable.
+ws_status ws_alloc_failed(ws_handle *h, const char *what, hipError_t e);
+
+// Outgrown buffers that could not be freed where they were replaced (WsScratch::grow_parked); freed with the handle.
+struct WsParked {
+    std::vector<void *> list;
+    void release()
+    {
+        for (void *q : list) (void)hipFree(q);
+        list.clear();
+    }
+};
+
+template <class... Owner>
+void release_all(Owner &...o)
+{
+    (o.release(), ...);
+}
+
+// Form 1: a buffer with a size of its own -- allocated on first use, grown on demand.  PINNED: page-locked host memory.
+// After a failed alloc() p == nullptr and bytes == 0.
+template <class T, bool PINNED = false>
 struct WsScratch {
     T *p = nullptr;
     size_t bytes = 0;
-    ws_status alloc(ws_handle *h, size_t need);  // release(), then `need` bytes
-    ws_status grow(ws_handle *h, size_t need);   // nothing when it holds `need` bytes already, else alloc()
+    // release(), then `need` bytes
+    ws_status alloc(ws_handle *h, size_t need, const char *what)
+    {
+        release();
+        return fresh(h, need, what);
+    }
+    // nothing when it holds `need` bytes already, else alloc()
+    ws_status grow(ws_handle *h, size_t need, const char *what) { return bytes >= need ? WS_OK : alloc(h, need, what); }
+    // grow() for a buffer that may be outgrown BETWEEN THE COLLECTIVES of a slab call: the old buffer is PARKED, not freed
+    // (WsSlab::retired, released with the handle).  hipFree waits for the whole device, and between the two all-gathers
+    // of a collective read a peer that is a step ahead on the host may already have its next transport kernel on the
+    // device, waiting for THIS rank's contribution -- with all ranks in one process on one GPU (in-process hosts; the
+    // tests' stand-in for librccl) that wait and hipFree's would wait for each other.  Growth is geometric -- to at least
+    // bytes + bytes / slack_div -- so the parked buffers add up to less than a small multiple of the live one.  A failure
+    // keeps the old buffer.
+    ws_status grow_parked(ws_handle *h, size_t need, size_t slack_div, WsParked *parked, const char *what)
+    {
+        if (bytes >= need) return WS_OK;
+        T *const old = p;
+        const size_t geometric = bytes + bytes / slack_div;
+        const ws_status st = fresh(h, need > geometric ? need : geometric, what);  // (p is replaced on success only)
+        if (!st && old) parked->list.push_back(old);
+        return st;
+    }
     void release()
     {
-        hipFree(p);
+        if (p) (void)(PINNED ? hipHostFree(p) : hipFree(p));
         p = nullptr;
         bytes = 0;
+    }
+
+private:
+    ws_status fresh(ws_handle *h, size_t want, const char *what)  // overwrites p, on success only
+    {
+        void *q = nullptr;
+        const size_t real = want > 4 ? want : 4;
+        const hipError_t e = PINNED ? hipHostMalloc(&q, real, hipHostMallocDefault) : hipMalloc(&q, real);
+        if (e != hipSuccess) return ws_alloc_failed(h, what, e);
+        p = static_cast<T *>(q);
+        bytes = want;
+        return WS_OK;
+    }
+};
+
+// Form 2: arrays that are allocated together and released together.  Most of them are members of the by-value
+// kernel-argument structs (WsSoA, WsSorted, WsXYZ, WsMask, WsSched, WsMig), which stay plain pointers: the group
+// allocates INTO a field and remembers the field's address; release() frees each buffer and nulls its field.  Handles
+// (ws_handle, WsSlab) are heap objects that never move or get copied, so the remembered addresses stay valid for as long
+// as the group lives.  A pointer that merely aliases a member (ws_handle::start, sched4[1].cost) is nulled by whoever
+// releases the group.
+struct WsGroup {
+    std::vector<void **> fields;
+    // zero: also cleared, on the handle's stream (ordered before everything that stream does with it)
+    template <class T>
+    ws_status alloc(ws_handle *h, T **field, size_t bytes, const char *what, bool zero = false);
+    void release()
+    {
+        for (void **f : fields) {
+            (void)hipFree(*f);
+            *f = nullptr;
+        }
+        fields.clear();
     }
 };
 
@@ -269,28 +351,31 @@ struct ws_handle {
     bool ieee = false;            // WS_FLAG_IEEE_DIVISION: correctly rounded sqrt / division in the pair terms
     uint32_t *stats = nullptr;    // device counters: [0] particle-steps with more candidates than the mask holds
     uint8_t *mult = nullptr;      // 27 stencil multiplicities (hash aliasing), device
-    uint32_t *force_cnt = nullptr;  // ws_apply_forces: WS_MAX_FORCES per-emitter counts (allocated by the first call that asks)
+    WsScratch<uint32_t> force_cnt;  // ws_apply_forces: WS_MAX_FORCES per-emitter counts (allocated by the first call that asks)
     bool alias = false;
-    size_t grid_alloc_cells = 0;
+    size_t grid_alloc_cells = 0;  // cells that count / cursor hold
+    // The owners of the arrays above, one per lifetime (ws_api.cpp):
+    WsGroup particles;  // cur, srt, sxyz, cid_*, accel, slot_tmp, mask.words: alloc_particle_arrays .. free_particle_arrays
+    WsGroup cells;      // count, cursor: kept by a re-grid that needs no more cells (alloc_grid)
+    WsGroup starts;     // start_alloc, bsum: rebuilt by every alloc_grid
+    WsGroup sched;      // the tile schedule's split / perm / cost (alloc_schedule .. free_schedule)
+    WsGroup fixed;      // stats, mult: created with the handle, freed with it
 
-    // staging for uploads / readback
+    // staging for uploads / readback (ws_api.cpp ensure_stage): `stage` is the alias of stage_mem.p that the calls use
+    WsScratch<char> stage_mem;
     void *stage = nullptr;
-    size_t stage_bytes = 0;
     // asynchronous position readback (ws_read_positions_begin / _end): own staging, own copy stream
     hipStream_t copy_stream = nullptr;
     hipEvent_t rb_gathered = nullptr, rb_done = nullptr;
-    float *rb_stage = nullptr;
-    size_t rb_bytes = 0;
+    WsScratch<float> rb_stage;
     bool rb_inflight = false;
     // ws_read_positions_begin(h, NULL): two page-locked buffers the library owns, filled alternately
-    float *rb_host[2] = {nullptr, nullptr};
-    size_t rb_host_bytes = 0;
+    WsScratch<float, true> rb_host[2];
     int rb_fill = 0, rb_last = -1;  // the buffer the readback in flight fills; the one the last finished readback filled
     bool rb_owned = false;          // the readback in flight goes into rb_host[rb_fill]
 
     // reference-layout sort view (lazy)
-    uint32_t *v_keys = nullptr, *v_perm = nullptr, *v_tmp = nullptr, *v_count = nullptr,
-             *v_cursor = nullptr, *v_start = nullptr, *v_bsum = nullptr, *v_off = nullptr;
+    WsScratch<uint32_t> v_keys, v_perm, v_tmp, v_count, v_cursor, v_start, v_bsum, v_off;
 
     WsField field;  // derived-field calls (csrc/ws_field.inc)
 
@@ -331,6 +416,18 @@ struct ws_handle {
     std::string err;
 };
 
+template <class T>
+ws_status WsGroup::alloc(ws_handle *h, T **field, size_t bytes, const char *what, bool zero)
+{
+    void *q = nullptr;
+    hipError_t e = hipMalloc(&q, bytes);
+    if (e != hipSuccess) return ws_alloc_failed(h, what, e);
+    *field = static_cast<T *>(q);
+    fields.push_back(reinterpret_cast<void **>(field));
+    if (zero && (e = hipMemsetAsync(q, 0, bytes, h->stream)) != hipSuccess) return ws_alloc_failed(h, what, e);
+    return WS_OK;
+}
+
 struct WsGraphEntry {
     uint32_t n_bound = 0, mig_cur = 0, mig_next = 0, halo = 0, far_cur = 0, far_next = 0;  // what a captured step has baked in
     hipGraphExec_t exec = nullptr;
@@ -360,7 +457,8 @@ struct WsSlab {
     // WS_FLAG_EXACT_MESSAGES: every message carries exactly what its sender has for it -- ws_step waits for the counts
     // (one all-gather of four words per rank before the migration, one before the halos, behind the early K4)
     bool exact_messages = false;
-    uint32_t *xs_send[2] = {nullptr, nullptr}, *xs_all[2] = {nullptr, nullptr}, *xs_host[2] = {nullptr, nullptr};  // [migration | halo]
+    uint32_t *xs_send[2] = {nullptr, nullptr}, *xs_all[2] = {nullptr, nullptr};  // [migration | halo]
+    WsScratch<uint32_t, true> xs_host[2];
     hipEvent_t ev_sizes[2] = {nullptr, nullptr};
     uint32_t *far_pack = nullptr;     // the far messages at the stride of what travels
     uint32_t exact_now[3] = {0, 0, 0};  // the records the last step's migration / halo / far messages carried
@@ -378,7 +476,8 @@ struct WsSlab {
     uint32_t *halo_sendL = nullptr, *halo_sendR = nullptr, *halo_recvL = nullptr, *halo_recvR = nullptr;
     bool binned = false;              // cid_cur / count describe the current owned set
     // what the host knows about the device state, two steps late
-    uint32_t *status_dev = nullptr, *status_host = nullptr;  // ring of per-rank header rows (pinned on the host)
+    uint32_t *status_dev = nullptr;  // ring of per-rank header rows, and its page-locked copy on the host
+    WsScratch<uint32_t, true> status_host;
     hipEvent_t ev_status[4] = {nullptr, nullptr, nullptr, nullptr};
     uint32_t n_known = 0;             // owned count as of step n_known_step
     uint64_t n_known_step = 0;
@@ -387,13 +486,14 @@ struct WsSlab {
     uint32_t cfg_ghost_capacity = 0;  // ws_device_cfg.ghost_capacity as given (0 = derive from the grid)
     // id-ordered global views (ws_read_positions & co. on a slab handle): count words, packed records of this rank,
     // every rank's records, the id-ordered result
-    uint32_t *cnt_send = nullptr, *cnt_all = nullptr;
-    uint32_t *g_send = nullptr, *g_all = nullptr, *g_out = nullptr;
-    size_t g_send_bytes = 0, g_all_bytes = 0, g_out_bytes = 0;
-    uint32_t *hist_dev = nullptr;     // x-layer histogram of a re-grid (one buffer, grown by doubling)
-    uint32_t hist_cap = 0;
-    uint32_t *agree_send = nullptr, *agree_all = nullptr;  // one word per rank: verdicts and the mode word (slab_agree_words)
-    std::vector<uint32_t *> retired;  // outgrown gather buffers (freed with the handle: ws_slab.inc slab_grow)
+    WsScratch<uint32_t> cnt_send, cnt_all;
+    WsScratch<uint32_t> g_send, g_all, g_out;  // (grown by half: grow_parked)
+    WsScratch<uint32_t> hist;         // x-layer histogram of a re-grid (one buffer, grown by doubling: slab_layer_hist)
+    WsScratch<uint32_t> agree_send, agree_all;  // one word per rank: verdicts and the mode word (slab_agree_words)
+    WsParked retired;                 // outgrown gather and histogram buffers (WsScratch::grow_parked)
+    // The owners of the plain pointers of this struct (ws_slab.inc):
+    WsGroup fixed;                    // dyn, status_dev, xs_send[], xs_all[]: created with the handle, freed with it
+    WsGroup geometry;                 // cuts_dev .. far_pack, the messages: slab_alloc_arrays .. slab_free_arrays (a re-grid)
     std::vector<uint32_t> counts;     // owned particles per rank as of the last gather
     std::vector<uint32_t> caps;       // ... and every rank's owned capacity (a re-grid decides for all ranks alike)
     uint64_t left_base = 0, arrived_base = 0, far_base = 0;  // cumulative counters carried over the loads (ws_slab_counters)

@@ -78,7 +78,7 @@ ws_status slab_sizes_begin(ws_handle *h, hipStream_t stream, int which, const ui
     HIP_TRY(h, hipGetLastError());
     const int rc = S->tr.allgather_dev(S->tr.ctx, S->xs_send[which], S->xs_all[which], 16, stream);
     if (rc) return slab_fail_tr(h, "allgather_dev", rc);
-    HIP_TRY(h, hipMemcpyAsync(S->xs_host[which], S->xs_all[which], (size_t)S->world * 16, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(h, hipMemcpyAsync(S->xs_host[which].p, S->xs_all[which], (size_t)S->world * 16, hipMemcpyDeviceToHost, stream));
     HIP_TRY(h, hipEventRecord(S->ev_sizes[which], stream));
     return WS_OK;
 }
@@ -115,7 +115,7 @@ ws_status slab_consume_status(ws_handle *h, uint64_t step)
     WsSlab *S = h->slab;
     const uint32_t slot = (uint32_t)(step % kStatusSlots);
     HIP_TRY(h, hipEventSynchronize(S->ev_status[slot]));
-    const uint32_t *tab = S->status_host + (size_t)slot * S->world * WS_HDR_WORDS_HOST;
+    const uint32_t *tab = S->status_host.p + (size_t)slot * S->world * WS_HDR_WORDS_HOST;
     uint32_t err = 0;
     for (uint32_t r = 0; r < S->world; r++) err |= tab[r * WS_HDR_WORDS_HOST + 1];
     S->n_known = tab[S->rank * WS_HDR_WORDS_HOST + 2];
@@ -227,7 +227,7 @@ ws_status slab_enqueue(ws_handle *h, uint32_t n_bound, bool first, bool capturin
         st = slab_sizes_begin(h, s, 0, S->mig_sendL, S->mig_sendR, S->far_send);
         if (!st) st = slab_sizes_end(h, 0);
         if (st) return st;
-        const uint32_t *x = S->xs_host[0];
+        const uint32_t *x = S->xs_host[0].p;
         const uint32_t sL = slab_round_records(x[4 * me], S->mig_cap), sR = slab_round_records(x[4 * me + 1], S->mig_cap);
         const uint32_t rL = left ? slab_round_records(x[4 * (me - 1) + 1], S->mig_cap) : 0u;
         const uint32_t rR = right ? slab_round_records(x[4 * (me + 1)], S->mig_cap) : 0u;
@@ -341,7 +341,7 @@ ws_status slab_enqueue(ws_handle *h, uint32_t n_bound, bool first, bool capturin
         }
         st = slab_sizes_end(h, 1);
         if (st) return st;
-        const uint32_t *x = S->xs_host[1];
+        const uint32_t *x = S->xs_host[1].p;
         const uint32_t sL = slab_round_records(x[4 * me], S->halo_cap), sR = slab_round_records(x[4 * me + 1], S->halo_cap);
         const uint32_t rL = left ? slab_round_records(x[4 * (me - 1) + 1], S->halo_cap) : 0u;
         const uint32_t rR = right ? slab_round_records(x[4 * (me + 1)], S->halo_cap) : 0u;
@@ -404,12 +404,12 @@ ws_status slab_enqueue(ws_handle *h, uint32_t n_bound, bool first, bool capturin
     if (capturing) {
         // the slot depends on the step: copy the whole ring (a few hundred bytes) and join the copy stream back, which
         // also orders the next step's k_migrate_fill behind this copy -- no slot is ever read while it is written
-        HIP_TRY(h, hipMemcpyAsync(S->status_host, S->status_dev, row_bytes * kStatusSlots, hipMemcpyDeviceToHost, S->copy));
+        HIP_TRY(h, hipMemcpyAsync(S->status_host.p, S->status_dev, row_bytes * kStatusSlots, hipMemcpyDeviceToHost, S->copy));
         HIP_TRY(h, hipEventRecord(S->ev_copied, S->copy));
         HIP_TRY(h, hipStreamWaitEvent(s, S->ev_copied, 0));
     } else {
         const uint32_t slot = (uint32_t)(h->steps % kStatusSlots);
-        HIP_TRY(h, hipMemcpyAsync(S->status_host + (size_t)slot * W * WS_HDR_WORDS_HOST,
+        HIP_TRY(h, hipMemcpyAsync(S->status_host.p + (size_t)slot * W * WS_HDR_WORDS_HOST,
                                   S->status_dev + (size_t)slot * W * WS_HDR_WORDS_HOST, row_bytes, hipMemcpyDeviceToHost, S->copy));
         HIP_TRY(h, hipEventRecord(S->ev_status[slot], S->copy));
     }
@@ -546,7 +546,7 @@ ws_status slab_settle_bits(ws_handle *h, uint32_t *bits)
     uint32_t err = dyn[DY_ERR];
     // the other ranks' bits arrive with the status tables: look at every table written so far
     for (uint64_t k = std::max<uint64_t>(h->steps > kStatusSlots ? h->steps - kStatusSlots : 0, S->t0); k < h->steps; k++) {
-        const uint32_t *tab = S->status_host + (size_t)(k % kStatusSlots) * S->world * WS_HDR_WORDS_HOST;
+        const uint32_t *tab = S->status_host.p + (size_t)(k % kStatusSlots) * S->world * WS_HDR_WORDS_HOST;
         for (uint32_t r = 0; r < S->world; r++) err |= tab[r * WS_HDR_WORDS_HOST + 1];
     }
     *bits = err;
@@ -572,17 +572,9 @@ void slab_drop_graphs(WsSlab *S)
 // the arrays whose size follows from the slab's geometry (cell grid, capacities, message sizes)
 void slab_free_arrays(ws_handle *h)
 {
-    WsSlab *S = h->slab;
     free_particle_arrays(h);
     free_grid(h);
-    hipFree(S->cuts_dev); hipFree(S->mig_dev); hipFree(S->hole); hipFree(S->tgt); hipFree(S->src);
-    hipFree(S->mig_sendL); hipFree(S->mig_sendR); hipFree(S->mig_recvL); hipFree(S->mig_recvR);
-    hipFree(S->far_send); hipFree(S->far_all); hipFree(S->far_pack);
-    S->far_pack = nullptr;
-    hipFree(S->halo_sendL); hipFree(S->halo_sendR); hipFree(S->halo_recvL); hipFree(S->halo_recvR);
-    S->cuts_dev = nullptr; S->mig_dev = nullptr; S->hole = S->tgt = S->src = nullptr;
-    S->mig_sendL = S->mig_sendR = S->mig_recvL = S->mig_recvR = S->far_send = S->far_all = nullptr;
-    S->halo_sendL = S->halo_sendR = S->halo_recvL = S->halo_recvR = nullptr;
+    h->slab->geometry.release();
 }
 
 void slab_free(ws_handle *h)
@@ -592,17 +584,10 @@ void slab_free(ws_handle *h)
     if (S->comm) hipStreamSynchronize(S->comm);
     if (S->copy) hipStreamSynchronize(S->copy);
     slab_free_arrays(h);
-    hipFree(S->dyn);
-    hipFree(S->status_dev);
-    hipFree(S->hist_dev); hipFree(S->agree_send); hipFree(S->agree_all);
-    hipFree(S->cnt_send); hipFree(S->cnt_all); hipFree(S->g_send); hipFree(S->g_all); hipFree(S->g_out);
-    for (uint32_t *p : S->retired) hipFree(p);
-    for (int k = 0; k < 2; k++) {
-        hipFree(S->xs_send[k]); hipFree(S->xs_all[k]);
-        if (S->xs_host[k]) hipHostFree(S->xs_host[k]);
-        if (S->ev_sizes[k]) hipEventDestroy(S->ev_sizes[k]);
-    }
-    if (S->status_host) hipHostFree(S->status_host);
+    release_all(S->fixed, S->hist, S->agree_send, S->agree_all, S->cnt_send, S->cnt_all, S->g_send, S->g_all, S->g_out, S->retired,
+                S->xs_host[0], S->xs_host[1], S->status_host);
+    for (hipEvent_t e : S->ev_sizes)
+        if (e) hipEventDestroy(e);
     for (hipEvent_t e : {S->ev_sorted, S->ev_halo_a, S->ev_k4_late, S->ev_halo_b, S->ev_filled, S->ev_copied})
         if (e) hipEventDestroy(e);
     slab_drop_graphs(S);
@@ -703,47 +688,34 @@ ws_status slab_alloc_arrays(ws_handle *h, const SlabGeometry &geo)
     S->halo_cap = geo.halo_cap; S->mig_cap = geo.mig_cap; S->far_cap = geo.far_cap; S->hole_cap = geo.hole_cap;
     S->max_arrivals = geo.max_arrivals;
     h->dev = geo.d;
-    const size_t tot = geo.tot, n16 = (tot + 16) * 16;
-    HIP_TRY(h, hipMalloc(&h->cur.pv, 2 * n16)); HIP_TRY(h, hipMalloc(&h->cur.pred, n16));
-    HIP_TRY(h, hipMalloc(&h->srt.pos, n16)); HIP_TRY(h, hipMalloc(&h->srt.pv, 2 * n16));
-    HIP_TRY(h, hipMalloc(&h->sxyz.x, n16 / 4)); HIP_TRY(h, hipMalloc(&h->sxyz.y, n16 / 4)); HIP_TRY(h, hipMalloc(&h->sxyz.z, n16 / 4));
-    HIP_TRY(h, hipMemsetAsync(h->sxyz.x, 0, n16 / 4, h->stream)); HIP_TRY(h, hipMemsetAsync(h->sxyz.y, 0, n16 / 4, h->stream));
-    HIP_TRY(h, hipMemsetAsync(h->sxyz.z, 0, n16 / 4, h->stream));
-    HIP_TRY(h, hipMalloc(&h->cid_cur, tot * 4)); HIP_TRY(h, hipMalloc(&h->cid_srt, tot * 4));
-    HIP_TRY(h, hipMalloc(&h->cur.rank, tot * 4));
-    HIP_TRY(h, hipMalloc(&h->accel, n16));
-    HIP_TRY(h, hipMalloc(&h->slot_tmp, tot * 4));
-    if (h->variant == WS_VARIANT_LISTED) {
-        h->mask.stride = S->cap;  // owned slots only: ghosts have no masks
-        HIP_TRY(h, hipMalloc(&h->mask.words, (size_t)wsk_mask_words() * S->cap * 4));
-    }
-    HIP_TRY(h, hipMalloc(&S->cuts_dev, (size_t)(W + 1) * 4));
+    ws_status st = alloc_particle_arrays(h, geo.tot, S->cap);
+    WsGroup &G = S->geometry;
+    if (!st) st = G.alloc(h, &S->cuts_dev, (size_t)(W + 1) * 4, "slab cuts");
+    if (st) return st;
     HIP_TRY(h, copy_now(h, S->cuts_dev, S->cuts.data(), (size_t)(W + 1) * 4, hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMalloc(&S->hole, (size_t)S->hole_cap * 4));
-    HIP_TRY(h, hipMalloc(&S->tgt, (size_t)(S->hole_cap + S->max_arrivals) * 4));
-    HIP_TRY(h, hipMalloc(&S->src, (size_t)(S->hole_cap + S->max_arrivals) * 4));
+    st = G.alloc(h, &S->hole, (size_t)S->hole_cap * 4, "migration index lists");
+    if (!st) st = G.alloc(h, &S->tgt, (size_t)(S->hole_cap + S->max_arrivals) * 4, "migration index lists");
+    if (!st) st = G.alloc(h, &S->src, (size_t)(S->hole_cap + S->max_arrivals) * 4, "migration index lists");
+    // every message starts zeroed
     const size_t mb = mig_msg_bytes(S->mig_cap), fb = mig_msg_bytes(S->far_cap);
-    for (uint32_t **p : {&S->mig_sendL, &S->mig_sendR, &S->mig_recvL, &S->mig_recvR}) {
-        HIP_TRY(h, hipMalloc(p, mb));
-        HIP_TRY(h, hipMemsetAsync(*p, 0, mb, h->stream));
-    }
+    for (uint32_t **p : {&S->mig_sendL, &S->mig_sendR, &S->mig_recvL, &S->mig_recvR})
+        if (!st) st = G.alloc(h, p, mb, "migration messages", true);
     // far messages: one per destination rank out, one per source rank in (exchanged all-to-all)
-    HIP_TRY(h, hipMalloc(&S->far_send, fb * W)); HIP_TRY(h, hipMemsetAsync(S->far_send, 0, fb * W, h->stream));
-    HIP_TRY(h, hipMalloc(&S->far_all, fb * W)); HIP_TRY(h, hipMemsetAsync(S->far_all, 0, fb * W, h->stream));
-    if (S->exact_messages) HIP_TRY(h, hipMalloc(&S->far_pack, fb * W));
+    if (!st) st = G.alloc(h, &S->far_send, fb * W, "far messages", true);
+    if (!st) st = G.alloc(h, &S->far_all, fb * W, "far messages", true);
+    if (!st && S->exact_messages) st = G.alloc(h, &S->far_pack, fb * W, "far messages");
+    if (!st) st = G.alloc(h, &S->mig_dev, sizeof(WsMig), "migration targets");
+    if (st) return st;
     {
         // where the force kernel's epilogue sends a particle that left the slab (migration part 1, fused)
         const WsMig m = {S->cuts_dev, W, S->rank, S->dyn, S->hole, S->hole_cap, S->mig_sendL, S->mig_sendR, S->mig_cap,
                          S->far_send, S->far_cap};
-        HIP_TRY(h, hipMalloc(&S->mig_dev, sizeof m));
         HIP_TRY(h, copy_now(h, S->mig_dev, &m, sizeof m, hipMemcpyHostToDevice));
         h->dev.mig = S->mig_dev;
     }
     const size_t hb = halo_msg_bytes((uint32_t)(geo.d.dim[1] * geo.d.dim[2]), S->halo_cap);
-    for (uint32_t **p : {&S->halo_sendL, &S->halo_sendR, &S->halo_recvL, &S->halo_recvR}) {
-        HIP_TRY(h, hipMalloc(p, hb));
-        HIP_TRY(h, hipMemsetAsync(*p, 0, hb, h->stream));
-    }
+    for (uint32_t **p : {&S->halo_sendL, &S->halo_sendR, &S->halo_recvL, &S->halo_recvR})
+        if ((st = G.alloc(h, p, hb, "halo messages", true))) return st;
     return alloc_grid(h);
 }
 
@@ -858,23 +830,6 @@ ws_status slab_write_particles(ws_handle *h, const ws_particle80 *in)
     return slab_load_global(h, 1, in, sizeof(ws_particle80));
 }
 
-// Grow one of the gather buffers.  The old one is RETIRED, not freed (slab_free frees the list): hipFree waits for the
-// whole device, and between the two all-gathers of a collective read a peer that is a step ahead on the host may
-// already have its next transport kernel on the device, waiting for THIS rank's contribution -- with all ranks in one
-// process on one GPU (in-process hosts; the tests' stand-in for librccl) that wait and hipFree's would wait for each
-// other.  Growth is geometric, so the retired buffers add up to less than the live one.
-ws_status slab_grow(ws_handle *h, uint32_t **buf, size_t *have, size_t need)
-{
-    if (*have >= need) return WS_OK;
-    const size_t want = std::max(need, *have + *have / 2);
-    uint32_t *fresh = nullptr;
-    HIP_TRY(h, hipMalloc(&fresh, want));
-    if (*buf) h->slab->retired.push_back(*buf);
-    *buf = fresh;
-    *have = want;
-    return WS_OK;
-}
-
 // ---- id-ordered global views -------------------------------------------------------------------------------
 // COLLECTIVE: every rank packs {id, payload} records of the particles it owns, one all-gather of the counts and one
 // of the records bring every rank's records to every rank.  On return S->g_all holds them (rank r at r * stride),
@@ -891,22 +846,19 @@ ws_status slab_gather(ws_handle *h, int kind, size_t *stride_words_out, uint32_t
     ws_status st = slab_settle_bits(h, &my_bits);
     if (st) return st;
     if (S->comm_failed) return fail(h, WS_ERR_COMM, "an earlier transport call failed; the slab handle is unusable");
-    if (!S->cnt_send) {
-        HIP_TRY(h, hipMalloc(&S->cnt_send, 16));
-        HIP_TRY(h, hipMalloc(&S->cnt_all, (size_t)W * 16));
-    }
+    if ((st = S->cnt_send.grow(h, 16, "gather counts")) || (st = S->cnt_all.grow(h, (size_t)W * 16, "gather counts"))) return st;
     const uint32_t mine[4] = {h->n, (uint32_t)kind, my_bits, S->cap};
-    wsk_set_words4(h->stream, S->cnt_send, mine[0], mine[1], mine[2], mine[3]);
+    wsk_set_words4(h->stream, S->cnt_send.p, mine[0], mine[1], mine[2], mine[3]);
     HIP_TRY(h, hipGetLastError());
     if (W > 1) {
-        const int rc = S->tr.allgather_dev(S->tr.ctx, S->cnt_send, S->cnt_all, 16, h->stream);
+        const int rc = S->tr.allgather_dev(S->tr.ctx, S->cnt_send.p, S->cnt_all.p, 16, h->stream);
         if (rc) return slab_fail_tr(h, "allgather_dev", rc);
         HIP_TRY(h, hipStreamSynchronize(h->stream));
     } else {
-        HIP_TRY(h, copy_now(h, S->cnt_all, S->cnt_send, 16, hipMemcpyDeviceToDevice));
+        HIP_TRY(h, copy_now(h, S->cnt_all.p, S->cnt_send.p, 16, hipMemcpyDeviceToDevice));
     }
     std::vector<uint32_t> tab((size_t)W * 4);
-    HIP_TRY(h, copy_now(h, tab.data(), S->cnt_all, tab.size() * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(h, copy_now(h, tab.data(), S->cnt_all.p, tab.size() * 4, hipMemcpyDeviceToHost));
     S->counts.resize(W);
     uint64_t total = 0;
     uint32_t max_n = 0;
@@ -928,10 +880,10 @@ ws_status slab_gather(ws_handle *h, int kind, size_t *stride_words_out, uint32_t
     max_n = (max_n + 63u) & ~63u;
     const uint32_t rw = wsk_pack_words(kind) + 1u;
     const size_t stride = (size_t)max_n * rw, each = stride * 4;
-    st = slab_grow(h, &S->g_send, &S->g_send_bytes, each);
+    st = S->g_send.grow_parked(h, each, 2, &S->retired, "gather buffer");  // (by half; no hipFree between the collectives of a read)
     if (st) return st;
     if (W > 1) {
-        st = slab_grow(h, &S->g_all, &S->g_all_bytes, each * W);
+        st = S->g_all.grow_parked(h, each * W, 2, &S->retired, "gather buffer");
         if (st) return st;
     }
     WsDev d = h->dev;
@@ -941,10 +893,10 @@ ws_status slab_gather(ws_handle *h, int kind, size_t *stride_words_out, uint32_t
         st = refresh_accel(h);
         if (st) return st;
     }
-    wsk_slab_pack(h->stream, d, kind, h->cur, h->srt, h->accel, h->steps > S->t0, S->g_send);
+    wsk_slab_pack(h->stream, d, kind, h->cur, h->srt, h->accel, h->steps > S->t0, S->g_send.p);
     HIP_TRY(h, hipGetLastError());
     if (W > 1) {
-        const int rc = S->tr.allgather_dev(S->tr.ctx, S->g_send, S->g_all, each, h->stream);
+        const int rc = S->tr.allgather_dev(S->tr.ctx, S->g_send.p, S->g_all.p, each, h->stream);
         if (rc) return slab_fail_tr(h, "allgather_dev", rc);
     }
     *stride_words_out = stride;
@@ -952,7 +904,7 @@ ws_status slab_gather(ws_handle *h, int kind, size_t *stride_words_out, uint32_t
     return WS_OK;
 }
 
-const uint32_t *slab_gathered(const WsSlab *S) { return S->world > 1 ? S->g_all : S->g_send; }
+const uint32_t *slab_gathered(const WsSlab *S) { return S->world > 1 ? S->g_all.p : S->g_send.p; }
 
 // ... scattered by id into S->g_out (n_global records of the kind's payload words) on the handle's stream
 ws_status slab_gather_by_id(ws_handle *h, int kind)
@@ -966,9 +918,9 @@ ws_status slab_gather_by_id(ws_handle *h, int kind)
     if (st) return st;
     const uint32_t pw = wsk_pack_words(kind);
     const size_t bytes = (size_t)S->n_global * pw * 4;
-    st = slab_grow(h, &S->g_out, &S->g_out_bytes, bytes);
+    st = S->g_out.grow_parked(h, bytes, 2, &S->retired, "gather buffer");
     if (st) return st;
-    wsk_slab_unpack_by_id(h->stream, slab_gathered(S), S->cnt_all, S->world, max_n, stride, pw, S->n_global, S->g_out);
+    wsk_slab_unpack_by_id(h->stream, slab_gathered(S), S->cnt_all.p, S->world, max_n, stride, pw, S->n_global, S->g_out.p);
     HIP_TRY(h, hipGetLastError());
     return WS_OK;
 }
@@ -981,7 +933,7 @@ ws_status slab_read_by_id(ws_handle *h, int kind, void *out)
     ws_status st = slab_gather_by_id(h, kind);
     if (st) return st;
     if (out)
-        HIP_TRY(h, hipMemcpyAsync(out, S->g_out, (size_t)S->n_global * wsk_pack_words(kind) * 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(out, S->g_out.p, (size_t)S->n_global * wsk_pack_words(kind) * 4, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return WS_OK;
 }
@@ -1000,16 +952,15 @@ ws_status slab_agree_words(ws_handle *h, uint32_t mine, std::vector<uint32_t> *t
 {
     WsSlab *S = h->slab;
     const uint32_t W = S->world;
-    if (!S->agree_send) {
-        HIP_TRY(h, hipMalloc(&S->agree_send, 16));
-        HIP_TRY(h, hipMalloc(&S->agree_all, (size_t)W * 16));
-    }
-    wsk_set_words4(h->stream, S->agree_send, mine, 0u, 0u, 0u);
+    ws_status st = S->agree_send.grow(h, 16, "agreement words");
+    if (!st) st = S->agree_all.grow(h, (size_t)W * 16, "agreement words");
+    if (st) return st;
+    wsk_set_words4(h->stream, S->agree_send.p, mine, 0u, 0u, 0u);
     HIP_TRY(h, hipGetLastError());
-    const int rc = S->tr.allgather_dev(S->tr.ctx, S->agree_send, S->agree_all, 16, h->stream);
+    const int rc = S->tr.allgather_dev(S->tr.ctx, S->agree_send.p, S->agree_all.p, 16, h->stream);
     if (rc) return slab_fail_tr(h, "allgather_dev", rc);
     table->resize((size_t)W * 4);
-    HIP_TRY(h, copy_now(h, table->data(), S->agree_all, table->size() * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(h, copy_now(h, table->data(), S->agree_all.p, table->size() * 4, hipMemcpyDeviceToHost));
     return WS_OK;
 }
 
@@ -1049,6 +1000,28 @@ ws_status slab_agree_mode(ws_handle *h)
     return WS_OK;
 }
 
+// The x-layer histogram of the gathered records `recs` on the grid of `d`, on the host: the same on every rank.
+// ONE histogram buffer per handle, grown by doubling (a HUD that changes the radius on every key press re-grids every
+// time: round 4 allocated a new buffer per re-grid and parked it until ws_destroy); the outgrown one is parked -- the
+// callers stand between collectives (WsScratch::grow_parked).  A failure here is this rank's alone -- an allocation, a
+// copy -- so the callers make it common before anybody goes on: the peers would otherwise give their arrays up and wait
+// for this rank in the next collective (ADVICE r4).
+ws_status slab_layer_hist(ws_handle *h, const WsDev &d, const uint32_t *recs, uint32_t max_n, size_t stride, std::vector<uint32_t> *hist)
+{
+    WsSlab *S = h->slab;
+    const size_t bytes = hist->size() * 4;
+    const ws_status st = S->hist.grow_parked(h, bytes, 1, &S->retired, "x-layer histogram");
+    if (st) return st;
+    hipError_t e = hipMemsetAsync(S->hist.p, 0, bytes, h->stream);
+    if (e == hipSuccess) {
+        wsk_slab_layer_hist(h->stream, d, recs, S->cnt_all.p, S->world, max_n, stride, S->hist.p);
+        e = copy_now(h, hist->data(), S->hist.p, bytes, hipMemcpyDeviceToHost);
+    }
+    if (e == hipSuccess) return WS_OK;
+    (void)hipGetLastError();
+    return fail(h, e == hipErrorOutOfMemory ? WS_ERR_OUT_OF_MEMORY : WS_ERR_HIP, "x-layer histogram", e);
+}
+
 ws_status slab_regrid(ws_handle *h, const ws_params *params, bool rebalance)
 {
     WsSlab *S = h->slab;
@@ -1067,28 +1040,12 @@ ws_status slab_regrid(ws_handle *h, const ws_params *params, bool rebalance)
     const uint32_t nx = (uint32_t)geo.d.gdim_x;
     std::vector<uint32_t> hist(nx);
     {
-        // ONE histogram buffer per handle, grown geometrically (a HUD that changes the radius on every key press re-grids
-        // every time: round 4 allocated a new buffer per re-grid and parked it until ws_destroy).  A failure here is this
-        // rank's alone -- an allocation, a copy -- so it is made common before anybody goes on: the peers would otherwise
-        // give their arrays up and wait for this rank in the next collective (ADVICE r4).
-        hipError_t e = hipSuccess;
-        if (S->hist_cap < nx) {
-            if (S->hist_dev) S->retired.push_back(S->hist_dev);  // (no hipFree between collectives: slab_grow; bounded by the doubling)
-            S->hist_dev = nullptr;
-            const uint32_t want = std::max(nx, 2u * S->hist_cap);
-            e = hipMalloc(&S->hist_dev, (size_t)want * 4);
-            S->hist_cap = e == hipSuccess ? want : 0u;
-        }
-        if (e == hipSuccess) e = hipMemsetAsync(S->hist_dev, 0, (size_t)nx * 4, h->stream);
-        if (e == hipSuccess) {
-            wsk_slab_layer_hist(h->stream, geo.d, slab_gathered(S), S->cnt_all, W, max_n, stride, S->hist_dev);
-            e = copy_now(h, hist.data(), S->hist_dev, (size_t)nx * 4, hipMemcpyDeviceToHost);
-        }
-        if (e != hipSuccess) (void)hipGetLastError();
+        const ws_status mine = slab_layer_hist(h, geo.d, slab_gathered(S), max_n, stride, &hist);
+        const std::string why = h->err;
         uint32_t anybody = 0;
-        const ws_status st_agree = slab_agree(h, e != hipSuccess ? 1u : 0u, &anybody);
+        const ws_status st_agree = slab_agree(h, mine ? 1u : 0u, &anybody);
         if (st_agree) return st_agree;
-        if (e != hipSuccess) return fail(h, e == hipErrorOutOfMemory ? WS_ERR_OUT_OF_MEMORY : WS_ERR_HIP, "re-grid: layer histogram; nothing was changed", e);
+        if (mine) return fail(h, mine, ("re-grid: " + why + "; nothing was changed").c_str());
         if (anybody) return fail(h, WS_ERR_OUT_OF_MEMORY, "re-grid: another slab could not build its layer histogram; nothing was changed");
     }
     // cuts of equal particle counts where the host asked for them -- now (ws_slab_rebalance) or earlier (a re-grid
@@ -1121,7 +1078,7 @@ ws_status slab_regrid(ws_handle *h, const ws_params *params, bool rebalance)
     if (!st) st = upload_mult(h);
     if (!st) st = slab_load_begin(h);
     if (!st) {
-        wsk_slab_select(h->stream, h->dev, 2, S->cuts_dev, S->world, S->rank, slab_gathered(S), 0, max_n, S->cnt_all, stride, h->cur,
+        wsk_slab_select(h->stream, h->dev, 2, S->cuts_dev, S->world, S->rank, slab_gathered(S), 0, max_n, S->cnt_all.p, stride, h->cur,
                         S->cap, S->dyn);
         if (hipGetLastError() != hipSuccess) st = fail(h, WS_ERR_HIP, "k_slab_select");
     }
@@ -1189,27 +1146,21 @@ ws_status slab_apply_forces(ws_handle *h, const ws_force *f, uint32_t k, float d
     const uint32_t nx = (uint32_t)h->dev.gdim_x;
     std::vector<uint32_t> hist(nx);
     {
-        hipError_t e = hipSuccess;
-        wsk_apply_forces_records(h->stream, recs, S->cnt_all, W, max_n, stride, fs, k, dt, out_affected ? h->force_cnt : nullptr);
-        if (S->hist_cap < nx) {
-            if (S->hist_dev) S->retired.push_back(S->hist_dev);  // (no hipFree between collectives: slab_grow)
-            S->hist_dev = nullptr;
-            const uint32_t want = std::max(nx, 2u * S->hist_cap);
-            e = hipMalloc(&S->hist_dev, (size_t)want * 4);
-            S->hist_cap = e == hipSuccess ? want : 0u;
+        wsk_apply_forces_records(h->stream, recs, S->cnt_all.p, W, max_n, stride, fs, k, dt, out_affected ? h->force_cnt.p : nullptr);
+        ws_status mine = slab_layer_hist(h, h->dev, recs, max_n, stride, &hist);
+        if (!mine) {
+            hipError_t e = hipGetLastError();
+            if (e == hipSuccess && out_affected) e = copy_now(h, out_affected, h->force_cnt.p, (size_t)k * 4, hipMemcpyDeviceToHost);
+            if (e != hipSuccess) {
+                (void)hipGetLastError();
+                mine = fail(h, e == hipErrorOutOfMemory ? WS_ERR_OUT_OF_MEMORY : WS_ERR_HIP, "edit of the gathered state", e);
+            }
         }
-        if (e == hipSuccess) e = hipMemsetAsync(S->hist_dev, 0, (size_t)nx * 4, h->stream);
-        if (e == hipSuccess) {
-            wsk_slab_layer_hist(h->stream, h->dev, recs, S->cnt_all, W, max_n, stride, S->hist_dev);
-            e = copy_now(h, hist.data(), S->hist_dev, (size_t)nx * 4, hipMemcpyDeviceToHost);
-        }
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e == hipSuccess && out_affected) e = copy_now(h, out_affected, h->force_cnt, (size_t)k * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) (void)hipGetLastError();
+        const std::string why_failed = h->err;
         uint32_t failed = 0;
-        const ws_status st_agree = slab_agree(h, e != hipSuccess ? 1u : 0u, &failed);
+        const ws_status st_agree = slab_agree(h, mine ? 1u : 0u, &failed);
         if (st_agree) return st_agree;
-        if (e != hipSuccess) return fail(h, e == hipErrorOutOfMemory ? WS_ERR_OUT_OF_MEMORY : WS_ERR_HIP, "forces: edit of the gathered state; nothing was changed", e);
+        if (mine) return fail(h, mine, ("forces: " + why_failed + "; nothing was changed").c_str());
         if (failed) return fail(h, WS_ERR_OUT_OF_MEMORY, "forces: another slab could not edit the gathered state; nothing was changed");
     }
     for (uint32_t r = 0; r < W; r++) {
@@ -1225,7 +1176,7 @@ ws_status slab_apply_forces(ws_handle *h, const ws_force *f, uint32_t k, float d
     // ---- mutation: the re-grid's tail on the unchanged geometry
     st = slab_load_begin(h);
     if (!st) {
-        wsk_slab_select(h->stream, h->dev, 2, S->cuts_dev, W, S->rank, recs, 0, max_n, S->cnt_all, stride, h->cur, S->cap, S->dyn);
+        wsk_slab_select(h->stream, h->dev, 2, S->cuts_dev, W, S->rank, recs, 0, max_n, S->cnt_all.p, stride, h->cur, S->cap, S->dyn);
         if (hipGetLastError() != hipSuccess) st = fail(h, WS_ERR_HIP, "k_slab_select");
     }
     if (!st) st = slab_load_end(h);
@@ -1253,7 +1204,7 @@ ws_status slab_field_positions(ws_handle *h, const float **xyz, WsDev *global, b
     if (st) return st;
     st = global_grid(&h->params, S->n_global, global);
     if (st) return fail(h, st, g_create_error.c_str());
-    *xyz = reinterpret_cast<const float *>(S->g_out);
+    *xyz = reinterpret_cast<const float *>(S->g_out.p);
     return WS_OK;
 }
 
@@ -1338,40 +1289,27 @@ ws_status ws_slab_create(const ws_params *params, const float *pos_xyz, const ui
         delete h;
         return s_;
     };
-#define SLAB_HIP(expr)                                                                                    \
-    do {                                                                                                  \
-        hipError_t e_ = (expr);                                                                           \
-        if (e_ != hipSuccess)                                                                             \
-            return bail(fail(h, e_ == hipErrorOutOfMemory ? WS_ERR_OUT_OF_MEMORY : WS_ERR_HIP, #expr, e_)); \
-    } while (0)
-#define SLAB_TRY(expr)                \
-    do {                              \
-        const ws_status s_ = (expr);  \
-        if (s_) return bail(s_);      \
-    } while (0)
     SlabGeometry geo;
-    SLAB_TRY(slab_geometry(h, params, &geo));
-    SLAB_HIP(hipSetDevice(cfg->device));
+    CREATE_TRY(slab_geometry(h, params, &geo));
+    CREATE_HIP(hipSetDevice(cfg->device));
     if (cfg->stream) {
         h->stream = (hipStream_t)cfg->stream;
         h->own_stream = false;
     } else {
-        SLAB_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+        CREATE_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     }
-    SLAB_HIP(hipEventCreateWithFlags(&h->done, hipEventDisableTiming));
+    CREATE_HIP(hipEventCreateWithFlags(&h->done, hipEventDisableTiming));
     ws_rccl_transport_bind_stream(&S->tr, h->stream);  // (the library's own RCCL transport: one communicator per stream)
     ws_get_smoothing_kernel(params, &h->sk);
-    SLAB_HIP(hipMalloc(&h->stats, 64)); SLAB_HIP(hipMemsetAsync(h->stats, 0, 64, h->stream));
-    SLAB_HIP(hipMalloc(&S->dyn, WS_DYN_WORDS * 4));
-    SLAB_HIP(hipMemsetAsync(S->dyn, 0, WS_DYN_WORDS * 4, h->stream));
+    CREATE_TRY(h->fixed.alloc(h, &h->stats, 64, "device counters", true));
+    CREATE_TRY(S->fixed.alloc(h, &S->dyn, WS_DYN_WORDS * 4, "slab state words", true));
     const size_t status_words = (size_t)kStatusSlots * W * WS_HDR_WORDS_HOST;
-    SLAB_HIP(hipMalloc(&S->status_dev, status_words * 4));
-    SLAB_HIP(hipMemsetAsync(S->status_dev, 0, status_words * 4, h->stream));
-    SLAB_HIP(hipHostMalloc((void **)&S->status_host, status_words * 4));
-    memset(S->status_host, 0, status_words * 4);
+    CREATE_TRY(S->fixed.alloc(h, &S->status_dev, status_words * 4, "status ring", true));
+    CREATE_TRY(S->status_host.alloc(h, status_words * 4, "page-locked status ring"));
+    memset(S->status_host.p, 0, status_words * 4);
     for (hipEvent_t *e : {&S->ev_sorted, &S->ev_halo_a, &S->ev_k4_late, &S->ev_halo_b, &S->ev_filled, &S->ev_copied})
-        SLAB_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
-    for (hipEvent_t &e : S->ev_status) SLAB_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        CREATE_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    for (hipEvent_t &e : S->ev_status) CREATE_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     {
         // The communication stream gets the HIGHEST priority: halo pack -> transport -> unpack are a few short kernels
         // that run behind an early K4 which fills every CU with one-wave workgroups; at the step stream's priority
@@ -1381,13 +1319,13 @@ ws_status ws_slab_create(const ws_params *params, const float *pos_xyz, const ui
         int lo = 0, hi = 0;
         const char *pr = WS_DEV_ENV("WS_SLAB_COMM_PRIORITY");
         if (pr && strcmp(pr, "default") == 0) {
-            SLAB_HIP(hipStreamCreateWithFlags(&S->comm, hipStreamNonBlocking));
+            CREATE_HIP(hipStreamCreateWithFlags(&S->comm, hipStreamNonBlocking));
         } else {
-            SLAB_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));  // (numerically lowest = highest priority)
-            SLAB_HIP(hipStreamCreateWithPriority(&S->comm, hipStreamNonBlocking, hi));
+            CREATE_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));  // (numerically lowest = highest priority)
+            CREATE_HIP(hipStreamCreateWithPriority(&S->comm, hipStreamNonBlocking, hi));
         }
     }
-    SLAB_HIP(hipStreamCreateWithFlags(&S->copy, hipStreamNonBlocking));
+    CREATE_HIP(hipStreamCreateWithFlags(&S->copy, hipStreamNonBlocking));
     // halo / compute overlap: on unless WS_FLAG_NO_OVERLAP
     S->overlap = !(cfg->flags & WS_FLAG_NO_OVERLAP);
     // How the messages are sized (include/wsfluid.h): exact (the default; host-synchronised, cannot be captured),
@@ -1406,37 +1344,35 @@ ws_status ws_slab_create(const ws_params *params, const float *pos_xyz, const ui
     if (S->exact_messages) {
         S->fixed_messages = true;
         for (int k = 0; k < 2; k++) {
-            SLAB_HIP(hipMalloc(&S->xs_send[k], 16));
-            SLAB_HIP(hipMalloc(&S->xs_all[k], (size_t)W * 16));
-            SLAB_HIP(hipHostMalloc((void **)&S->xs_host[k], (size_t)W * 16));
-            SLAB_HIP(hipEventCreateWithFlags(&S->ev_sizes[k], hipEventDisableTiming));
+            CREATE_TRY(S->fixed.alloc(h, &S->xs_send[k], 16, "message sizes"));
+            CREATE_TRY(S->fixed.alloc(h, &S->xs_all[k], (size_t)W * 16, "message sizes"));
+            CREATE_TRY(S->xs_host[k].alloc(h, (size_t)W * 16, "page-locked message sizes"));
+            CREATE_HIP(hipEventCreateWithFlags(&S->ev_sizes[k], hipEventDisableTiming));
         }
     }
     // (developer builds: the floors of the message sizes, records)
     if (const char *v = WS_DEV_ENV("WS_SLAB_FLOOR_MIGRATION")) S->floor_mig = (uint32_t)std::max(1, atoi(v));
     if (const char *v = WS_DEV_ENV("WS_SLAB_FLOOR_FAR")) S->floor_far = (uint32_t)std::max(1, atoi(v));
     if (const char *v = WS_DEV_ENV("WS_SLAB_FLOOR_HALO")) S->floor_halo = ((uint32_t)std::max(64, atoi(v)) + 63u) & ~63u;
-    SLAB_TRY(slab_alloc_arrays(h, geo));
-    SLAB_TRY(upload_mult(h));
+    CREATE_TRY(slab_alloc_arrays(h, geo));
+    CREATE_TRY(upload_mult(h));
     // upload this slab's particles at the owned base; the first ws_step migrates (a no-op when the
     // caller followed ws_slab_assign) and bins them
-    SLAB_TRY(slab_load_begin(h));
+    CREATE_TRY(slab_load_begin(h));
     if (n_local) {
         const size_t pb = (size_t)n_local * 12, ib = (size_t)n_local * 4;
-        SLAB_TRY(ensure_stage(h, pb + ib));
-        SLAB_HIP(hipMemcpyAsync(h->stage, pos_xyz, pb, hipMemcpyHostToDevice, h->stream));
-        SLAB_HIP(hipMemcpyAsync((char *)h->stage + pb, ids, ib, hipMemcpyHostToDevice, h->stream));
+        CREATE_TRY(ensure_stage(h, pb + ib));
+        CREATE_HIP(hipMemcpyAsync(h->stage, pos_xyz, pb, hipMemcpyHostToDevice, h->stream));
+        CREATE_HIP(hipMemcpyAsync((char *)h->stage + pb, ids, ib, hipMemcpyHostToDevice, h->stream));
         const uint32_t base = h->dev.base;
         WsSoA cur_owned = {h->cur.pv + 2 * (size_t)base, h->cur.pred + base, nullptr};
         wsk_upload_positions_ids(h->stream, (const float *)h->stage, (const uint32_t *)((char *)h->stage + pb), cur_owned,
                                  n_local);
-        SLAB_HIP(hipGetLastError());
-        SLAB_HIP(hipMemcpyAsync(S->dyn + DY_N, &n_local, 4, hipMemcpyHostToDevice, h->stream));
+        CREATE_HIP(hipGetLastError());
+        CREATE_HIP(hipMemcpyAsync(S->dyn + DY_N, &n_local, 4, hipMemcpyHostToDevice, h->stream));
     }
-    SLAB_TRY(slab_load_end(h));
-    SLAB_TRY(slab_agree_mode(h));
-#undef SLAB_HIP
-#undef SLAB_TRY
+    CREATE_TRY(slab_load_end(h));
+    CREATE_TRY(slab_agree_mode(h));
     *out = h;
     return WS_OK;
 }
