@@ -800,6 +800,61 @@ typedef struct ws_force {      /* 48 bytes */
 } ws_force;
 ws_status ws_apply_forces(ws_handle *h, const ws_force *f, uint32_t k, float dt, uint32_t *out_affected);
 
+/* ---- the fluid acting on things that float in it: buoyancy and drag on host-owned bodies (no reference
+ *      counterpart) ----------------------------------------------------------------------------------------------------
+ * One-way coupling, water to body.  The HOST owns the bodies, as it owns whitewater's diffuse particles: it describes each
+ * body by sample points (position p_s, material velocity w_s -- from the body's linear and angular velocity -- and the
+ * share V_s of the body's volume the sample stands for), gets one force and one torque per body back, and integrates the
+ * bodies itself.  The library keeps nothing between calls and ws_step is not touched; a host that wants the body to shove
+ * water aside puts a WS_FORCE_RADIAL emitter at it with ws_apply_forces.
+ * m samples in all, grouped by body: body b owns the samples body_start[b] .. body_start[b+1]-1 (nb + 1 entries,
+ * non-decreasing, body_start[0] == 0, body_start[nb] == m; an empty body is allowed).  body_centre: nb*3 floats, the point
+ * c_b the torque of body b is taken about.
+ * Below fl() is a rounding to float; every operation is rounded once, nothing is contracted, and division is correctly
+ * rounded whatever the handle's flags -- only the field itself follows WS_FLAG_IEEE_DIVISION (ws_step_whitewater's split).
+ * Per sample, independently of every other sample:
+ *   1. (u, rho) = the field at p_s exactly as ws_sample_velocity_points defines it, in the HANDLE's arithmetic; g = the
+ *      handle's gravity; rho_0 = rest_density, or the handle's target_density when rest_density == 0.
+ *   2. If !(rho > 0) the sample is DRY: f = +0, vol = +0, F = T = (+0, +0, +0), wet = 0.
+ *   3. Otherwise it is WET: f = fminf(rho / rho_0, 1.0f); vol = fl(V_s * f); lift = fl(fluid_density * vol);
+ *      kd = fl(drag * vol); per axis F_a = fl(fl(kd * fl(u_a - w_a)) - fl(lift * g_a)); wet = 1.
+ *   4. (wet samples) r_a = fl(p_a - c_b,a); T_x = fl(fl(r_y * F_z) - fl(r_z * F_y)), and cyclically for T_y and T_z.
+ * Per body, the CANONICAL SUM of each of the seven floats F (3), T (3) and vol: a fixed binary tree over the body's c
+ * samples in the order given.  With P the smallest power of two > c, the leaves are t_0 .. t_{c-1} followed by +0 up to
+ * P; every level computes v[i] = fl(v[2i] + v[2i+1]) until one value is left.  An empty body gives +0.  Consequences: at
+ * least one +0 leaf always enters, so no per-body output is ever -0; and padding further with +0 changes no bit, so the
+ * library is free to sum a fixed number of levels per pass.  The wet count is an integer sum.  The order is part of the
+ * contract: the results are bit-identical across launch shapes, slab counts and WS_FLAG_GRAPH, and a host that repeats
+ * the arithmetic above on ws_sample_velocity_points' output gets the same bits, in either arithmetic of the handle.
+ * Outputs, any of which may be NULL (all NULL: WS_ERR_INVALID_ARG on a single handle, contribute-only on a slab):
+ *   out_force, out_torque nb*3 (the sums of F and T), out_volume nb (the submerged volume), out_wet nb (wet samples),
+ *   out_sample_force m*3 (F per sample), out_sample_fraction m (f per sample).
+ * The call waits for enqueued steps, writes nothing ws_step reads, recomputes the sampler's binning from the current state
+ * on every call and keeps its scratch in the sampler's (grow-only, freed by ws_destroy, allocated on the first body call
+ * only).  It may be made between ws_read_positions_begin and _end; ws_steps_done is unchanged.
+ * Slab handles: COLLECTIVE on the gathered global {position, velocity} set, the same bits as a single handle; a rank that
+ * passes every output NULL only contributes, and a rank validates its arguments only after the gather, so a refused rank
+ * leaves no peer waiting.
+ * Errors: WS_ERR_INVALID_ARG (NULL handle, p, sample_xyz, sample_velocity, sample_volume, body_start or body_centre; every
+ *   output NULL on a single handle; m == 0 or more than 2^28; nb == 0 or more than 2^24; a body_start that does not start
+ *   at 0, does not end at m or decreases; a non-finite value or a magnitude above 1e15 in any input array; a negative
+ *   volume; fluid_density, drag or rest_density not finite or negative; a non-zero reserved): nothing is written;
+ *   WS_ERR_UNSUPPORTED (WS_FLAG_REFERENCE_ORDER handles); WS_ERR_OUT_OF_MEMORY (scratch allocation failed: the handle
+ *   stays usable); WS_ERR_HIP on an unusable handle. */
+typedef struct ws_body_params {   /* 16 bytes */
+    float fluid_density;          /* offset 0: lift per unit of submerged volume, in units of -gravity (Archimedes); finite, >= 0 */
+    float drag;                   /* 4: force per unit of submerged volume and of (u - w); finite, >= 0 */
+    float rest_density;           /* 8: field density at which a sample counts as fully submerged; 0 = the handle's target_density */
+    uint32_t reserved;            /* 12: must be 0 */
+} ws_body_params;
+/* Host-only (no device needed; WS_ERR_INVALID_ARG for NULL): fluid_density 1000 (water, SI), drag 500 (half of it: a unit of
+ * relative velocity pulls half as hard as a unit of -gravity lifts), rest_density 0 (the handle's target_density). */
+ws_status ws_default_body_params(ws_body_params *out);
+ws_status ws_body_forces(ws_handle *h, const ws_body_params *p, const float *sample_xyz, const float *sample_velocity,
+                         const float *sample_volume, uint32_t m, const uint32_t *body_start, const float *body_centre,
+                         uint32_t nb, float *out_force, float *out_torque, float *out_volume, uint32_t *out_wet,
+                         float *out_sample_force, float *out_sample_fraction);
+
 /* ---- introspection ------------------------------------------------------------- */
 const char *ws_last_error(ws_handle *h);
 uint32_t ws_num_particles(ws_handle *h);

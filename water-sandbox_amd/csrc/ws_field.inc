@@ -1,5 +1,5 @@
 // ws_field.inc -- the derived-field calls of include/wsfluid.h (density field, surface, anisotropic kernels, rays, velocity
-// field and advection, whitewater): host-only, part of ws_api.cpp's translation unit.  Every call is a list of stages over
+// field and advection, whitewater, bodies): host-only, part of ws_api.cpp's translation unit.  Every call is a list of stages over
 // ws_handle::field (ws_internal.h WsField):
 //   field_enter         dead handle, reference-order mode, nothing wanted on a single handle
 //   field_source        the collective protocol and the inputs by id: positions, on request velocities
@@ -26,6 +26,7 @@ void free_field_cells(ws_handle *h)
 void free_field(ws_handle *h)
 {
     auto &F = h->field;
+    release_all(F.body);
     free_field_cells(h);
     release_all(F.xyz, F.keys, F.tmp, F.perm, F.spos, F.q, F.rho, F.grad, F.code, F.vbase, F.bcnt, F.bstart, F.bstate, F.tri,
                 F.mxyz, F.mnrm, F.vxyz, F.vpos, F.svel, F.wnrm, F.wst, F.wout, F.wpt, F.wnb, F.wcnt, F.woff, F.wstate, F.cxyz,
@@ -757,6 +758,95 @@ ws_status step_whitewater(ws_handle *h, const ws_whitewater_step_params *p, cons
     return field_finish(h, {{out_xyz, dp, M * 12}, {out_vel, dv, M * 12}, {out_life, dl, M * 4}, {out_class, dc, M}});
 }
 
+// ---- bodies in the fluid (include/wsfluid.h defines a sample's terms and the order of a body's sums) -------------------
+ws_status body_check(ws_handle *h, const ws_body_params *p, const float *xyz, const float *vel, const float *vol, uint32_t m,
+                     const uint32_t *body_start, const float *centre, uint32_t nb)
+{
+    if (!p) return fail(h, WS_ERR_INVALID_ARG, "bodies: the parameters are required");
+    if (!isfinite(p->fluid_density) || !(p->fluid_density >= 0.0f) || !isfinite(p->drag) || !(p->drag >= 0.0f))
+        return fail(h, WS_ERR_INVALID_ARG, "bodies: fluid_density and drag must be finite and >= 0");
+    if (!isfinite(p->rest_density) || !(p->rest_density >= 0.0f))
+        return fail(h, WS_ERR_INVALID_ARG, "bodies: rest_density must be finite and >= 0");
+    if (p->reserved != 0u) return fail(h, WS_ERR_INVALID_ARG, "bodies: reserved must be 0");
+    if (!xyz || !vel || !vol || m == 0u) return fail(h, WS_ERR_INVALID_ARG, "bodies: no samples");
+    if (m > (1u << 28)) return fail(h, WS_ERR_INVALID_ARG, "bodies: more than 2^28 samples");
+    if (!body_start || !centre || nb == 0u) return fail(h, WS_ERR_INVALID_ARG, "bodies: no bodies");
+    if (nb > (1u << 24)) return fail(h, WS_ERR_INVALID_ARG, "bodies: more than 2^24 bodies");
+    if (body_start[0] != 0u || body_start[nb] != m)
+        return fail(h, WS_ERR_INVALID_ARG, "bodies: body_start must start at 0 and end at m");
+    for (size_t b = 0; b < nb; b++)
+        if (body_start[b] > body_start[b + 1]) return fail(h, WS_ERR_INVALID_ARG, "bodies: body_start must not decrease");
+    auto in_range = [](const float *v, size_t k) {
+        for (size_t t = 0; t < k; t++)
+            if (!isfinite(v[t]) || fabsf(v[t]) > 1e15f) return false;
+        return true;
+    };
+    if (!in_range(xyz, (size_t)m * 3) || !in_range(vel, (size_t)m * 3) || !in_range(vol, m) || !in_range(centre, (size_t)nb * 3))
+        return fail(h, WS_ERR_INVALID_ARG, "bodies: positions, velocities, volumes and centres must be finite and within 1e15");
+    for (size_t t = 0; t < m; t++)
+        if (vol[t] < 0.0f) return fail(h, WS_ERR_INVALID_ARG, "bodies: a volume is negative");
+    return WS_OK;
+}
+
+// ws_body_forces: the binning with velocities, the chunk table (built here from body_start), samples and centres up, the
+// sweep with the first eight levels of every body's tree, the finishing kernel, the results out.
+ws_status body_forces(ws_handle *h, const ws_body_params *p, const float *xyz, const float *vel, const float *vol, uint32_t m,
+                      const uint32_t *body_start, const float *centre, uint32_t nb, float *out_force, float *out_torque,
+                      float *out_volume, uint32_t *out_wet, float *out_sforce, float *out_sfrac)
+{
+    FieldCtx c;
+    c.want = out_force || out_torque || out_volume || out_wet || out_sforce || out_sfrac;
+    ws_status st = field_enter(h, c, "bodies", "bodies: every output is NULL");
+    if (st) return st;
+    st = field_source(h, &c, FIELD_POSITIONS_AND_VELOCITIES, [&]() { return body_check(h, p, xyz, vel, vol, m, body_start, centre, nb); });
+    if (st || c.contributed) return st;
+    if ((st = field_bin_particles(h, c))) return st;
+    hipStream_t s = h->stream;
+    auto &F = h->field;
+    // the chunks: wsk_body_chunk() consecutive samples of one body each, then the bodies' first chunks
+    const uint32_t per = wsk_body_chunk();
+    size_t nch = 0;
+    for (size_t b = 0; b < nb; b++) nch += ((size_t)(body_start[b + 1] - body_start[b]) + per - 1) / per;
+    std::vector<uint32_t> table(4 * nch + nb + 1);
+    uint32_t *cstart = table.data() + 4 * nch;
+    size_t at = 0;
+    for (size_t b = 0; b < nb; b++) {
+        cstart[b] = (uint32_t)at;
+        for (uint32_t first = body_start[b]; first < body_start[b + 1]; first += per, at++) {
+            uint32_t *ch = table.data() + 4 * at;
+            ch[0] = (uint32_t)b;
+            ch[1] = first;
+            ch[2] = std::min(per, body_start[b + 1] - first);
+            ch[3] = 0u;
+        }
+    }
+    cstart[nb] = (uint32_t)at;
+    // F.body in words: chunks 4 nch | partials 8 nch | first chunks nb + 1 | xyz 3 m | velocity 3 m | volume m | centres 3 nb |
+    // sample force 3 m | sample fraction m | force 3 nb | torque 3 nb | volume nb | wet nb
+    const size_t M = m, NB = nb;
+    if ((st = F.body.grow(h, (12 * nch + 11 * M + 12 * NB + 1) * 4, kFieldScratch))) return st;
+    float *d_chunks = F.body.p, *d_part = d_chunks + 4 * nch, *d_cstart = d_part + 8 * nch, *d_xyz = d_cstart + NB + 1;
+    float *d_vel = d_xyz + 3 * M, *d_vol = d_vel + 3 * M, *d_centre = d_vol + M, *d_sforce = d_centre + 3 * NB;
+    float *d_sfrac = d_sforce + 3 * M, *d_force = d_sfrac + M, *d_torque = d_force + 3 * NB, *d_volume = d_torque + 3 * NB;
+    uint32_t *d_wet = reinterpret_cast<uint32_t *>(d_volume + NB);
+    HIP_TRY(h, hipMemcpyAsync(d_chunks, table.data(), 4 * nch * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(d_cstart, cstart, (NB + 1) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(d_xyz, xyz, M * 12, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(d_vel, vel, M * 12, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(d_vol, vol, M * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(d_centre, centre, NB * 12, hipMemcpyHostToDevice, s));
+    const float rho0 = p->rest_density == 0.0f ? c.d.target_density : p->rest_density;
+    const WsBodyParams bp = {p->fluid_density, p->drag, rho0};
+    wsk_body_forces(s, c.d, F.start.p, F.spos.p, F.svel.p, h->ieee, bp, reinterpret_cast<const uint32_t *>(d_chunks), (uint32_t)nch,
+                    reinterpret_cast<const uint32_t *>(d_cstart), nb, d_xyz, d_vel, d_vol, d_centre, d_part,
+                    out_sforce ? d_sforce : nullptr, out_sfrac ? d_sfrac : nullptr, out_force ? d_force : nullptr,
+                    out_torque ? d_torque : nullptr, out_volume ? d_volume : nullptr, out_wet ? d_wet : nullptr);
+    HIP_TRY(h, hipGetLastError());
+    // (field_finish synchronises: the table outlives its upload)
+    return field_finish(h, {{out_force, d_force, NB * 12}, {out_torque, d_torque, NB * 12}, {out_volume, d_volume, NB * 4},
+                            {out_wet, d_wet, NB * 4}, {out_sforce, d_sforce, M * 12}, {out_sfrac, d_sfrac, M * 4}});
+}
+
 }  // namespace
 
 extern "C" {
@@ -921,6 +1011,29 @@ ws_status ws_step_whitewater(ws_handle *h, const ws_whitewater_step_params *p, c
 {
     if (!h) return WS_ERR_INVALID_ARG;
     return step_whitewater(h, p, xyz, velocity, life, m, out_xyz, out_velocity, out_life, out_class);
+}
+
+// ======================================================================================
+// bodies in the fluid: buoyancy and drag (include/wsfluid.h defines a sample's terms and the order of the sums)
+// ======================================================================================
+ws_status ws_default_body_params(ws_body_params *out)
+{
+    if (!out) return WS_ERR_INVALID_ARG;
+    out->fluid_density = 1000.0f;
+    out->drag = 500.0f;
+    out->rest_density = 0.0f;
+    out->reserved = 0u;
+    return WS_OK;
+}
+
+ws_status ws_body_forces(ws_handle *h, const ws_body_params *p, const float *sample_xyz, const float *sample_velocity,
+                         const float *sample_volume, uint32_t m, const uint32_t *body_start, const float *body_centre, uint32_t nb,
+                         float *out_force, float *out_torque, float *out_volume, uint32_t *out_wet, float *out_sample_force,
+                         float *out_sample_fraction)
+{
+    if (!h) return WS_ERR_INVALID_ARG;
+    return body_forces(h, p, sample_xyz, sample_velocity, sample_volume, m, body_start, body_centre, nb, out_force, out_torque,
+                       out_volume, out_wet, out_sample_force, out_sample_fraction);
 }
 
 }  // extern "C"

@@ -311,6 +311,10 @@ struct WsField {
     WsScratch<float4> wnrm;
     WsScratch<float> wst, wout, wpt;
     WsScratch<uint32_t> wnb, wcnt, woff, wstate;
+    // bodies (ws_body_forces), one array of words: the chunk table (4 per chunk) and the chunks' partial sums (8 per chunk),
+    // the bodies' first chunks (nb + 1), the samples (xyz, velocity: 3 floats, volume: 1) and the centres (3 per body), the
+    // per-sample results (force: 3, fraction: 1) and the per-body ones (force, torque: 3, volume, wet count: 1)
+    WsScratch<float> body;
     // anisotropic kernels (ws_read_anisotropy, ws_sample_aniso_*, ws_extract_aniso_surface): centres, ellipsoids and
     // neighbour counts by id, the centres' ellipsoids in their cell order (their {c, id} reuse spos)
     WsScratch<float> cxyz;
@@ -605,6 +609,20 @@ void wsk_whitewater_spawn(hipStream_t s, const WsWhiteEmit &e, const float *pxyz
                           const uint32_t *off, float *out_xyz, float *out_vel, float *out_life, uint32_t *out_src, uint32_t n);
 void wsk_whitewater_step(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, const float4 *svel, bool ieee,
                          const WsWhiteStep &sp, float *pts, float *vel, float *life, uint8_t *cls, uint32_t m);
+// bodies (ws_body_forces) over the velocity field's binning.  chunks: nchunks x {body, first sample, samples (1 .. the
+// workgroup size), 0}, a body's chunks consecutive and in order; cstart: the first chunk of every body, nb + 1 entries;
+// part: 8 words per chunk (written, then read by the finishing kernel).  One workgroup per chunk sweeps the field at the
+// chunk's samples, stores the per-sample results (sforce, sfrac: either may be nullptr) and its node of the body's
+// summation tree; then one wave per body finishes the tree into force, torque, volume and wet (any may be nullptr; all:
+// no finishing launch).  rho0 is the density a sample counts as fully submerged at.
+struct WsBodyParams {
+    float fluid_density, drag, rho0;
+};
+uint32_t wsk_body_chunk(void);  // samples per chunk
+void wsk_body_forces(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, const float4 *svel, bool ieee,
+                     const WsBodyParams &bp, const uint32_t *chunks, uint32_t nchunks, const uint32_t *cstart, uint32_t nb,
+                     const float *xyz, const float *vel, const float *vol, const float *centre, float *part, float *sforce,
+                     float *sfrac, float *force, float *torque, float *volume, uint32_t *wet);
 // anisotropic kernels (ws_read_anisotropy / ws_sample_aniso_* / ws_extract_aniso_surface): the per-particle stage over
 // the sampler's binning of the positions (by id: centres, ellipsoids as 2 float4, neighbour counts), then the records
 // of the centres in their own cell order

@@ -3623,6 +3623,161 @@ void wsk_whitewater_step(hipStream_t s, const WsDev &d, const uint32_t *start, c
 }
 
 // ---------------------------------------------------------------------------------
+// buoyancy and drag on host-owned bodies (ws_body_forces; never inside ws_step)
+//
+// include/wsfluid.h pins every rounding of a sample's terms and the ORDER of a body's sums: a fixed binary tree over the
+// body's samples in the order given, padded with +0 to a power of two above their number.  No float atomics anywhere: the
+// tree is walked level by level, level L pairing slot i with slot i ^ (1 << L) of the body-relative sample index.
+//
+// k_body_forces, one workgroup per chunk = WS_BLOCK consecutive body-relative samples of ONE body (the host's chunk table
+// says which): a lane sweeps the velocity field at its sample (field_sweep, the points sampler's own definition), forms the
+// sample's F, T, vol and wet in registers, stores the per-sample outputs, then the workgroup sums the seven floats and the
+// count over levels 0 .. 7 of the tree -- 0 .. 5 across the lanes of a wave, 6 and 7 across the four waves through LDS.
+// A lane without a sample holds +0.  The chunk's partial is the tree's node at level 8.
+// k_body_finish, one wave per body: the same tree continued over the body's chunk partials, 64 at a time across the lanes
+// (6 more levels per block), the blocks' nodes merged like the carries of a binary counter (a stack of one node per level,
+// in LDS, each lane owning one of the eight values), and what is left on the stack folded from the lowest level up into a
+// carry that starts at +0 -- the padding: at least one +0 always enters, and further +0 change no bit.
+// ---------------------------------------------------------------------------------
+// levels 0 .. 5: every lane ends with the sum of its wave in tree order (a + b and b + a are the same bits)
+__device__ __forceinline__ float body_wave_tree(float v)
+{
+#pragma unroll
+    for (int sh = 1; sh <= 32; sh <<= 1) v = v + __shfl_xor(v, sh, 64);
+    return v;
+}
+__device__ __forceinline__ uint32_t body_wave_count(uint32_t v)
+{
+#pragma unroll
+    for (int sh = 1; sh <= 32; sh <<= 1) v += (uint32_t)__shfl_xor((int)v, sh, 64);
+    return v;
+}
+// one node from two: values 0 .. 6 are floats, value 7 is the wet count (its bits travel in a float)
+__device__ __forceinline__ float body_node(float lo, float hi, bool count)
+{
+    return count ? __uint_as_float(__float_as_uint(lo) + __float_as_uint(hi)) : lo + hi;
+}
+
+#define WS_BODY_LEVELS 16  // stack levels of the finishing tree: a call's 2^28 samples are at most 2^14 blocks of 64 chunks
+
+template <bool IEEE>
+__global__ void __launch_bounds__(WS_BLOCK) k_body_forces(WsDev d, const uint32_t *__restrict__ start, FieldVel src, WsBodyParams bp,
+                                                          const uint4 *__restrict__ chunks, const float *__restrict__ xyz,
+                                                          const float *__restrict__ wvel, const float *__restrict__ vol,
+                                                          const float *__restrict__ centre, float *__restrict__ part,
+                                                          float *__restrict__ sforce, float *__restrict__ sfrac)
+{
+    __shared__ float s_part[WS_BLOCK / 64][8];
+    const uint4 ch = chunks[blockIdx.x];  // {body, first sample, samples, 0}
+    const uint32_t lane = threadIdx.x;
+    float v[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // F, T, vol
+    uint32_t wet = 0u;
+    if (lane < ch.z) {
+        const size_t t = (size_t)ch.y + lane;
+        const float p[3] = {xyz[3 * t], xyz[3 * t + 1], xyz[3 * t + 2]};
+        const FieldAcc a = field_sweep<IEEE, true>(d, start, src, make_float4(p[0], p[1], p[2], 0.f));
+        float f = 0.f;
+        if (a.rho > 0.f) {
+            const float4 u4 = field_velocity(a);
+            const float u[3] = {u4.x, u4.y, u4.z};
+            f = fminf(a.rho / bp.rho0, 1.0f);
+            const float sv = vol[t] * f;
+            const float lift = bp.fluid_density * sv, kd = bp.drag * sv;
+            float r[3];
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                v[k] = kd * (u[k] - wvel[3 * t + k]) - lift * d.grav[k];
+                r[k] = p[k] - centre[3 * (size_t)ch.x + k];
+            }
+            v[3] = r[1] * v[2] - r[2] * v[1];
+            v[4] = r[2] * v[0] - r[0] * v[2];
+            v[5] = r[0] * v[1] - r[1] * v[0];
+            v[6] = sv;
+            wet = 1u;
+        }
+        if (sforce) field_store3(sforce, t, make_float4(v[0], v[1], v[2], 0.f));
+        if (sfrac) sfrac[t] = f;
+    }
+#pragma unroll
+    for (int k = 0; k < 7; k++) v[k] = body_wave_tree(v[k]);
+    wet = body_wave_count(wet);
+    if ((lane & 63u) == 0u) {
+#pragma unroll
+        for (int k = 0; k < 7; k++) s_part[lane >> 6][k] = v[k];
+        s_part[lane >> 6][7] = __uint_as_float(wet);
+    }
+    __syncthreads();
+    if (lane < 8u) {  // levels 6 and 7: waves 0 + 1 and 2 + 3, then the two
+        const bool count = lane == 7u;
+        const float lo = body_node(s_part[0][lane], s_part[1][lane], count), hi = body_node(s_part[2][lane], s_part[3][lane], count);
+        part[8 * (size_t)blockIdx.x + lane] = body_node(lo, hi, count);
+    }
+}
+
+__global__ void __launch_bounds__(WS_BLOCK) k_body_finish(const uint32_t *__restrict__ cstart, const float *__restrict__ part,
+                                                          uint32_t nb, float *__restrict__ force, float *__restrict__ torque,
+                                                          float *__restrict__ volume, uint32_t *__restrict__ wet)
+{
+    __shared__ float s_stack[WS_BLOCK / 64][WS_BODY_LEVELS][8];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t b = blockIdx.x * (WS_BLOCK / 64) + wave;
+    if (b >= nb) return;  // (wave-uniform; the kernel has no barrier)
+    const uint32_t c0 = cstart[b], nc = cstart[b + 1] - c0;  // the body's chunks (none: an empty body)
+    const uint32_t nblk = (nc + 63u) >> 6;
+    const bool count = lane == 7u;
+    for (uint32_t blk = 0; blk < nblk; blk++) {
+        const uint32_t i = blk * 64u + lane;
+        float4 a = make_float4(0.f, 0.f, 0.f, 0.f), c = a;  // an absent chunk: +0, count 0
+        if (i < nc) {
+            const float4 *q = reinterpret_cast<const float4 *>(part + 8 * ((size_t)c0 + i));
+            a = q[0];
+            c = q[1];
+        }
+        const float v0 = body_wave_tree(a.x), v1 = body_wave_tree(a.y), v2 = body_wave_tree(a.z), v3 = body_wave_tree(a.w);
+        const float v4 = body_wave_tree(c.x), v5 = body_wave_tree(c.y), v6 = body_wave_tree(c.z);
+        const float v7 = __uint_as_float(body_wave_count(__float_as_uint(c.w)));
+        if (lane < 8u) {  // lane k keeps value k; it alone reads and writes column k of the stack
+            float node = lane == 0u ? v0 : lane == 1u ? v1 : lane == 2u ? v2 : lane == 3u ? v3 : lane == 4u ? v4 : lane == 5u ? v5
+                         : lane == 6u ? v6 : v7;
+            uint32_t l = 0;
+            for (; (blk >> l) & 1u; l++) node = body_node(s_stack[wave][l][lane], node, count);
+            s_stack[wave][l][lane] = node;
+        }
+    }
+    if (lane >= 8u) return;
+    float carry = 0.f;
+    for (uint32_t l = 0; (nblk >> l) != 0u; l++)
+        if ((nblk >> l) & 1u) carry = body_node(s_stack[wave][l][lane], carry, count);
+    if (lane < 3u) {
+        if (force) force[3 * (size_t)b + lane] = carry;
+    } else if (lane < 6u) {
+        if (torque) torque[3 * (size_t)b + (lane - 3u)] = carry;
+    } else if (lane == 6u) {
+        if (volume) volume[b] = carry;
+    } else if (wet) {
+        wet[b] = __float_as_uint(carry);
+    }
+}
+
+uint32_t wsk_body_chunk(void) { return WS_BLOCK; }
+
+void wsk_body_forces(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, const float4 *svel, bool ieee,
+                     const WsBodyParams &bp, const uint32_t *chunks, uint32_t nchunks, const uint32_t *cstart, uint32_t nb,
+                     const float *xyz, const float *vel, const float *vol, const float *centre, float *part, float *sforce,
+                     float *sfrac, float *force, float *torque, float *volume, uint32_t *wet)
+{
+    const FieldVel src = {spos, svel};
+    if (nchunks != 0u)
+        ws_dispatch([&](auto I) {
+            hipLaunchKernelGGL(k_body_forces<I()>, dim3(nchunks), dim3(WS_BLOCK), 0, s, d, start, src, bp,
+                               reinterpret_cast<const uint4 *>(chunks), xyz, vel, vol, centre, part, sforce, sfrac);
+        }, ieee);
+    if (force || torque || volume || wet)
+        hipLaunchKernelGGL(k_body_finish, dim3(cdiv(nb, WS_BLOCK / 64)), dim3(WS_BLOCK), 0, s, cstart, part, nb, force, torque,
+                           volume, wet);
+}
+
+// ---------------------------------------------------------------------------------
 // rays at the fluid surface (ws_cast_rays / ws_cast_camera; never inside ws_step)
 //
 // include/wsfluid.h pins the march bit for bit: samples t_k = t_start + k * dt at p = o + t * v, the first k with

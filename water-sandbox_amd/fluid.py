@@ -5,6 +5,7 @@ This module is plumbing over the C ABI in include/wsfluid.h.  It never computes 
 itself and has no CPU fallback: if the HIP library is missing or no gfx950 device is
 visible, construction raises.
 """
+import collections
 import ctypes as C
 import os
 
@@ -54,7 +55,7 @@ ABI_SYMBOLS = [
     "ws_extract_aniso_surface", "ws_cast_rays", "ws_cast_camera",
     "ws_read_velocities", "ws_sample_velocity_grid", "ws_sample_velocity_points", "ws_advect_points",
     "ws_default_whitewater_emit_params", "ws_default_whitewater_step_params", "ws_read_whitewater", "ws_emit_whitewater",
-    "ws_step_whitewater", "ws_apply_forces",
+    "ws_step_whitewater", "ws_apply_forces", "ws_default_body_params", "ws_body_forces",
 ]
 
 
@@ -150,6 +151,17 @@ class WsForce(C.Structure):
         ("strength", C.c_float),
         ("damping", C.c_float),
         ("reserved", C.c_uint32 * 2),
+    ]
+
+
+class WsBodyParams(C.Structure):
+    """ws_body_params: buoyancy and drag of ws_body_forces (include/wsfluid.h)."""
+
+    _fields_ = [
+        ("fluid_density", C.c_float),
+        ("drag", C.c_float),
+        ("rest_density", C.c_float),
+        ("reserved", C.c_uint32),
     ]
 
 
@@ -272,6 +284,8 @@ def bind_library(path):
     L.ws_emit_whitewater.argtypes = [vp, vp, u32, vp, vp, vp, vp, vp]
     L.ws_step_whitewater.argtypes = [vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]
     L.ws_apply_forces.argtypes = [vp, vp, u32, C.c_float, vp]
+    L.ws_default_body_params.argtypes = [vp]
+    L.ws_body_forces.argtypes = [vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, vp]
     return L
 
 
@@ -541,6 +555,37 @@ def apply_forces(L, h, check, forces, dt, counts=True):
     out = np.zeros(max(len(forces), 1), np.uint32) if counts else None
     check(L.ws_apply_forces(h, C.byref(arr), len(forces), dt, out.ctypes.data if counts else None))
     return out[:len(forces)] if counts else None
+
+
+def body_params(**fields):
+    """ws_default_body_params with the given fields replaced (fluid_density, drag, rest_density)."""
+    return _whitewater_params(WsBodyParams, load_library().ws_default_body_params, fields)
+
+
+BodyForces = collections.namedtuple("BodyForces", "force torque volume wet sample_force sample_fraction")
+
+
+def body_forces(L, h, check, params, xyz, velocity, volume, body_start, centres, samples=False, want=True):
+    """ws_body_forces: buoyancy and drag of the fluid on nb host-owned bodies described by m samples -- xyz, velocity
+    (m, 3), volume (m,), body_start (nb + 1,) uint32, centres (nb, 3).  A BodyForces of force, torque (nb, 3), volume
+    (nb,) float32, wet (nb,) uint32 and, with samples=True, sample_force (m, 3) and sample_fraction (m,), else None.
+    params: a WsBodyParams.  want=False (slab handles): contribute and return None."""
+    p = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    w = np.ascontiguousarray(velocity, np.float32).reshape(-1, 3)
+    v = np.ascontiguousarray(volume, np.float32).reshape(-1)
+    bs = np.ascontiguousarray(body_start, np.uint32).reshape(-1)
+    c = np.ascontiguousarray(centres, np.float32).reshape(-1, 3)
+    m, nb = p.shape[0], c.shape[0]
+    assert w.shape[0] == m and v.shape[0] == m and bs.shape[0] == nb + 1
+    args = (h, C.byref(params), p.ctypes.data, w.ctypes.data, v.ctypes.data, m, bs.ctypes.data, c.ctypes.data, nb)
+    if not want:
+        check(L.ws_body_forces(*args, None, None, None, None, None, None))
+        return None
+    out = BodyForces(np.empty((nb, 3), np.float32), np.empty((nb, 3), np.float32), np.empty(nb, np.float32),
+                     np.empty(nb, np.uint32), np.empty((m, 3), np.float32) if samples else None,
+                     np.empty(m, np.float32) if samples else None)
+    check(L.ws_body_forces(*args, *(None if a is None else a.ctypes.data for a in out)))
+    return out
 
 
 def extract_surface(L, h, check, origin, spacing, dims, iso, normals=True, want=True, collective=False, cap=None,
@@ -866,6 +911,13 @@ class FluidWorker:
         to the velocities as one Euler step of dt.  The per-emitter counts of affected particles, or None with
         counts=False (the call then only enqueues)."""
         return apply_forces(self._L, self._h, self._check, forces, dt, counts)
+
+    def body_forces(self, params, xyz, velocity, volume, body_start, centres, samples=False):
+        """What the fluid does to things floating in it: buoyancy and drag on nb host-owned bodies, each a group of sample
+        points (xyz, the material's velocity there, the share of the body's volume), as one force and one torque about
+        centres[b] per body.  params = body_params(...).  A BodyForces (force, torque, volume, wet, sample_force,
+        sample_fraction; the last two with samples=True) -- include/wsfluid.h ws_body_forces has the definition."""
+        return body_forces(self._L, self._h, self._check, params, xyz, velocity, volume, body_start, centres, samples)
 
     def steps_done(self):
         return int(self._L.ws_steps_done(self._h))

@@ -352,6 +352,32 @@ class FluidWorker {
         check(ws_step_whitewater(h_, &p, x, v, d.life.data(), (uint32_t)d.xyz.size(), x, v, d.life.data(), d.kind.data()));
     }
 
+    // Things that float (include/wsfluid.h ws_body_forces).  The host owns the bodies: each is a run of sample points --
+    // position, the material's velocity there, the share of the body's volume -- and the centre its torque is taken about.
+    struct Bodies {
+        std::vector<Vec3> xyz, velocity;   // per sample, grouped by body
+        std::vector<float> volume;         // per sample
+        std::vector<uint32_t> start;       // bodies + 1 entries: body b owns the samples start[b] .. start[b + 1] - 1
+        std::vector<Vec3> centre;          // per body
+        std::vector<Vec3> force, torque;   // per body, after body_forces
+        std::vector<float> submerged;      // per body: the submerged volume
+        std::vector<uint32_t> wet;         // per body: samples that touch the fluid
+    };
+    // Buoyancy and drag of the current fluid state on the bodies: one force and one torque each, for the host to integrate.
+    void body_forces(const ws_body_params &p, Bodies &b)
+    {
+        const size_t nb = b.centre.size();
+        if (nb == 0 || b.xyz.empty()) return;
+        b.force.resize(nb);
+        b.torque.resize(nb);
+        b.submerged.resize(nb);
+        b.wet.resize(nb);
+        check(ws_body_forces(h_, &p, reinterpret_cast<const float *>(b.xyz.data()), reinterpret_cast<const float *>(b.velocity.data()),
+                             b.volume.data(), (uint32_t)b.xyz.size(), b.start.data(), reinterpret_cast<const float *>(b.centre.data()),
+                             (uint32_t)nb, reinterpret_cast<float *>(b.force.data()), reinterpret_cast<float *>(b.torque.data()),
+                             b.submerged.data(), b.wet.data(), nullptr, nullptr));
+    }
+
     std::vector<float> read_speeds()
     {
         std::vector<float> out(n_);

@@ -450,6 +450,10 @@ class SlabWorker:
         emitters); the counts are global.  counts=False: this rank applies without asking for them (None)."""
         return fluid.apply_forces(self._L, self._h, self._check, forces, dt, counts)
 
+    def body_forces(self, params, xyz, velocity, volume, body_start, centres, samples=False, want=True):
+        """FluidWorker.body_forces over the GLOBAL particle set (COLLECTIVE); want=False: only contribute (None)."""
+        return fluid.body_forces(self._L, self._h, self._check, params, xyz, velocity, volume, body_start, centres, samples, want)
+
     def read_positions_begin(self, buf):
         assert buf.dtype == np.float32 and buf.shape == (self.n_global, 3) and buf.flags.c_contiguous
         self._check(self._L.ws_read_positions_begin(self._h, buf.ctypes.data))
