@@ -800,13 +800,92 @@ typedef struct ws_force {      /* 48 bytes */
 } ws_force;
 ws_status ws_apply_forces(ws_handle *h, const ws_force *f, uint32_t k, float dt, uint32_t *out_affected);
 
+/* ---- solid things in the water: the fluid goes round them, and they feel it (no reference counterpart) --
+ * An emitter is a hint; a solid is a wall.  ws_collide_solids resolves the state the enqueued steps leave against k solids
+ * (spheres, boxes, capsules, each optionally HOLLOW: the fluid is kept inside), stream-ordered after the steps enqueued so
+ * far and before the next ws_step; ws_step itself knows nothing of solids.  A particle nearer to a solid than `margin` is
+ * pushed out along the surface normal to exactly that distance, the part of its velocity that goes into the solid is
+ * reflected (restitution) and its sliding braked (friction), both relative to the solid's own motion, and the momentum
+ * the particles took is summed per solid: with ws_body_forces (what the water does to a body) and this call (what the
+ * body does to the water, and the reaction) a floating body is complete.
+ * Below fl() is a rounding to float; arithmetic is IEEE whatever the handle's flags: every operation is rounded once, sqrt
+ * and division are correctly rounded, nothing is contracted; dot(a, b) = fl(fl(fl(a.x*b.x) + fl(a.y*b.y)) + fl(a.z*b.z))
+ * (the whitewater block's); a cross product a x b has x = fl(fl(a.y*b.z) - fl(a.z*b.y)) and cyclically (the forces
+ * block's); x * y + z is fl(fl(x*y) + z).  Indices a, i run over 0 .. 2.
+ * Per particle, with a RUNNING (p, v) that starts from what ws_read_positions / ws_read_velocities return, for the solids
+ * e = 0 .. k-1 in the order given -- collisions resolve in sequence -- with c = centre, R_i = rot[3i .. 3i+2] (row i: the
+ * solid's i-th local axis in world coordinates, used as given), V = velocity, W = angular_velocity:
+ *   1. q_a = p_a - c_a; for BOX and CAPSULE l_i = dot(R_i, q).
+ *   2. signed distance s and outward unit normal n:
+ *      WS_SOLID_SPHERE:  r = size[0]; d = sqrt(dot(q, q)); s = d - r; n_a = q_a / d if d > 0, else n = (0, 1, 0).
+ *      WS_SOLID_CAPSULE: r = size[0], L = size[1]; t = fminf(fmaxf(l_1, -L), L); w_a = q_a - t * R_1,a;
+ *                        d = sqrt(dot(w, w)); s = d - r; n_a = w_a / d if d > 0, else n = R_0.
+ *      WS_SOLID_BOX:     b = size; a_i = |l_i| - b_i; g = fmaxf(fmaxf(a_0, a_1), a_2).
+ *                        If g > 0: u_i = copysignf(fmaxf(a_i, 0), l_i); d = sqrt(dot(u, u)); s = d; m_i = u_i / d.
+ *                        Otherwise: i* = the lowest i with a_i == g; s = g; m = copysignf(1, l_i*) at i*, +0 elsewhere.
+ *                        n_a = (m_0 * R_0,a + m_1 * R_1,a) + m_2 * R_2,a.
+ *      WS_SOLID_HOLLOW (flags bit 0): s = -s, n_a = -n_a.
+ *   3. a contact exists iff s < margin.  Without one: on to the next solid.  With one the particle is TOUCHED and the
+ *      solid's contact count n_e rises by one.
+ *   4. push out: p_a = p_a + (margin - s) * n_a.
+ *   5. with the new p: r_a = p_a - c_a; u_a = V_a + (W x r)_a; rel_a = v_a - u_a; vn = dot(rel, n).
+ *      If vn < 0: j = (1 + restitution) * (-vn); tang_a = rel_a - vn * n_a; dv_a = j * n_a - friction * tang_a;
+ *      v_a = v_a + dv_a.  Otherwise the particle is moved, not kicked, and contributes nothing to 6.
+ *   6. the reaction on the solid per unit of particle mass: I_a = -dv_a, H = r x I.  Each of the six floats x enters a
+ *      64-bit FIXED-POINT sum as llrintf(fminf(fmaxf(x, -0x1p31f), 0x1p31f) * 0x1p24f) (the scaling is exact, llrintf
+ *      rounds to nearest, ties to even); the sums wrap modulo 2^64.  Integer addition has no order: the result does not
+ *      depend on the launch shape, on the number of slabs or on graphs.  out_impulse[3e + a] = (double)sum * 0x1p-24, the
+ *      sum of I_a over the contacts of solid e; out_angular likewise for H (about `centre`); the host multiplies by its
+ *      particle mass and divides by its frame time to get a force and a torque.
+ * After the loop a TOUCHED particle goes through the step's own container rule: nd = -1 * collision_damping; per axis, if
+ * p_a < ext_min_a: v_a = v_a * nd, p_a = ext_min_a; else if p_a > ext_max_a: v_a = v_a * nd, p_a = ext_max_a.  That
+ * velocity change does not enter the reaction.  A particle no solid touches keeps its position and velocity bit for bit
+ * (a -0 stays -0).  The predicted position of EVERY particle becomes pred_a = fl(p_a + fl(v_a * 0.02f)) and the state is
+ * binned again, as after ws_apply_forces.  out_contacts, if not NULL, receives the k counts n_e.
+ * Afterwards, on a single handle: ws_steps_done is unchanged; ws_read_particles reports the new position, velocity and
+ * predicted position and the LAST STEP's density, pressure and acceleration; every read-only call sees the new positions;
+ * a WS_FLAG_GRAPH handle keeps replaying its captured step.  The call may be made between ws_read_positions_begin and
+ * _end (the readback keeps the positions it captured).  With all three outputs NULL a single handle only enqueues and
+ * returns without waiting; with any of them the call waits for the sums.
+ * Slab handles: COLLECTIVE, the same bits as a single handle, by ws_apply_forces' route (gather, every rank applies the
+ * definition to the global set and reloads the particles it owns; the 80-byte view reports zero density / pressure /
+ * acceleration until the next ws_step).  The outputs are the GLOBAL sums on every rank that passes them.  The verdict is
+ * common: if any rank refuses its arguments, or the ranks' solids differ, ALL return WS_ERR_INVALID_ARG and nothing is
+ * changed.
+ * Errors: WS_ERR_INVALID_ARG (NULL handle or s; k outside 1 .. WS_MAX_SOLIDS; a kind > 2; flag bits other than bit 0; a
+ * non-zero reserved word; any non-finite value or magnitude above 1e15 in any field, used or not; a used size not > 0 --
+ * SPHERE size[0], BOX size[0 .. 2], CAPSULE size[0]; a capsule's half length size[1] may be 0 but not negative;
+ * restitution or friction outside [0, 1]; margin < 0): nothing is touched and the handle steps on.  `rot` is not checked
+ * for orthonormality: it is the host's, as an emitter's axis is.  WS_ERR_UNSUPPORTED (WS_FLAG_REFERENCE_ORDER handles);
+ * WS_ERR_HIP on an unusable handle. */
+#define WS_SOLID_SPHERE  0u
+#define WS_SOLID_BOX     1u
+#define WS_SOLID_CAPSULE 2u
+#define WS_SOLID_HOLLOW  1u   /* flags bit 0: the fluid is kept INSIDE (a glass, a bowl) */
+#define WS_MAX_SOLIDS    16u
+typedef struct ws_solid {      /* 112 bytes */
+    uint32_t kind;             /* offset 0 */
+    uint32_t flags;            /* offset 4 */
+    float centre[3];           /* offset 8 */
+    float rot[9];              /* offset 20: rows R_0 R_1 R_2 = the solid's local axes in world coordinates; ignored by SPHERE */
+    float size[3];             /* offset 56: SPHERE [0] = radius; BOX half extents; CAPSULE [0] = radius, [1] = half length along R_1 */
+    float velocity[3];         /* offset 68: of the solid */
+    float angular_velocity[3]; /* offset 80: of the solid, about `centre` (radians per unit of time) */
+    float restitution;         /* offset 92: in [0, 1] */
+    float friction;            /* offset 96: in [0, 1] */
+    float margin;              /* offset 100: >= 0 */
+    uint32_t reserved[2];      /* offset 104: must be 0 */
+} ws_solid;
+ws_status ws_collide_solids(ws_handle *h, const ws_solid *s, uint32_t k, uint32_t *out_contacts, double *out_impulse,
+                            double *out_angular);
+
 /* ---- the fluid acting on things that float in it: buoyancy and drag on host-owned bodies (no reference
  *      counterpart) ----------------------------------------------------------------------------------------------------
  * One-way coupling, water to body.  The HOST owns the bodies, as it owns whitewater's diffuse particles: it describes each
  * body by sample points (position p_s, material velocity w_s -- from the body's linear and angular velocity -- and the
  * share V_s of the body's volume the sample stands for), gets one force and one torque per body back, and integrates the
  * bodies itself.  The library keeps nothing between calls and ws_step is not touched; a host that wants the body to shove
- * water aside puts a WS_FORCE_RADIAL emitter at it with ws_apply_forces.
+ * water aside puts a WS_FORCE_RADIAL emitter at it with ws_apply_forces, or makes it a solid with ws_collide_solids.
  * m samples in all, grouped by body: body b owns the samples body_start[b] .. body_start[b+1]-1 (nb + 1 entries,
  * non-decreasing, body_start[0] == 0, body_start[nb] == m; an empty body is allowed).  body_centre: nb*3 floats, the point
  * c_b the torque of body b is taken about.

@@ -31,6 +31,8 @@ ws_status slab_write_particles(ws_handle *h, const ws_particle80 *in);
 ws_status slab_regrid(ws_handle *h, const ws_params *params, bool rebalance);
 ws_status slab_field_positions(ws_handle *h, const float **xyz, WsDev *global, bool with_vel);
 ws_status slab_apply_forces(ws_handle *h, const ws_force *f, uint32_t k, float dt, uint32_t *out_affected);
+ws_status slab_collide_solids(ws_handle *h, const ws_solid *s, uint32_t k, uint32_t *out_contacts, double *out_impulse,
+                              double *out_angular);
 // ws_field.inc
 void free_field(ws_handle *h);
 
@@ -684,7 +686,7 @@ void free_all(ws_handle *h)
     for (auto e : h->pool) hipEventDestroy(e);
     free_grid(h);
     free_particle_arrays(h);
-    release_all(h->fixed, h->stage_mem, h->force_cnt, h->v_keys, h->v_perm, h->v_tmp, h->v_count, h->v_cursor, h->v_start, h->v_bsum,
+    release_all(h->fixed, h->stage_mem, h->force_cnt, h->solid_sums, h->v_keys, h->v_perm, h->v_tmp, h->v_count, h->v_cursor, h->v_start, h->v_bsum,
                 h->v_off);
     free_field(h);
 #ifdef WS_WITH_REFCHECK
@@ -1318,6 +1320,156 @@ ws_status ws_apply_forces(ws_handle *h, const ws_force *f, uint32_t k, float dt,
     HIP_TRY(h, hipGetLastError());
     h->pred_stale = true;  // cur.pred is behind the new velocities: k_reorder<true> / refresh_pred recompute it
     if (out_affected) HIP_TRY(h, copy_now(h, out_affected, h->force_cnt.p, (size_t)k * 4, hipMemcpyDeviceToHost));
+    return WS_OK;
+}
+
+// ======================================================================================
+// solid things in the water
+// ======================================================================================
+}  // extern "C"
+
+namespace {
+
+// the argument errors of ws_collide_solids (nullptr = acceptable); nothing is touched before this has passed
+const char *solids_refusal(const ws_solid *s, uint32_t k)
+{
+    const auto bad = [](float x) { return !isfinite(x) || fabsf(x) > 1e15f; };
+    if (!s) return "solids: s is NULL";
+    if (k < 1u || k > WS_MAX_SOLIDS) return "solids: k outside 1 .. WS_MAX_SOLIDS";
+    for (uint32_t e = 0; e < k; e++) {
+        const ws_solid &o = s[e];
+        if (o.kind > WS_SOLID_CAPSULE) return "solids: unknown kind";
+        if (o.flags & ~WS_SOLID_HOLLOW) return "solids: unknown flag bits";
+        if (o.reserved[0] || o.reserved[1]) return "solids: reserved words must be 0";
+        for (int c = 0; c < 9; c++)
+            if (bad(o.rot[c])) return "solids: rot must be finite and at most 1e15 in magnitude";
+        for (int c = 0; c < 3; c++)
+            if (bad(o.centre[c]) || bad(o.size[c]) || bad(o.velocity[c]) || bad(o.angular_velocity[c]))
+                return "solids: centre, size, velocity and angular_velocity must be finite and at most 1e15 in magnitude";
+        if (bad(o.restitution) || bad(o.friction) || bad(o.margin)) return "solids: restitution, friction and margin must be finite";
+        const int used = o.kind == WS_SOLID_BOX ? 3 : 1;
+        for (int c = 0; c < used; c++)
+            if (!(o.size[c] > 0.f)) return "solids: a radius or half extent must be > 0";
+        if (o.kind == WS_SOLID_CAPSULE && o.size[1] < 0.f) return "solids: a capsule's half length must be >= 0";
+        if (o.restitution < 0.f || o.restitution > 1.f || o.friction < 0.f || o.friction > 1.f) return "solids: restitution and friction must lie in [0, 1]";
+        if (o.margin < 0.f) return "solids: margin must be >= 0";
+    }
+    return nullptr;
+}
+
+// The squared distance from a solid's centre beyond which no particle can be in contact with it, whatever `rot` holds:
+// what lets a wave skip the solid without changing a bit.  A contact needs s < margin, and
+//   SPHERE:  s = fl(d - r) < margin                                   =>  d <= r + margin (up to roundings);
+//   CAPSULE: the same for d = |q - t R_1| with |t| <= L               =>  |q| <= r + margin + L |R_1|;
+//   BOX:     every |l_i| < b_i + margin, l = R q                      =>  |q| <= |b + margin| / sigma_min(R),
+// sigma_min = the smallest singular value of R (1 for a rotation; near 0 the bound is useless and the solid is never
+// skipped).  The float roundings of the kernel's q, dot products and differences are relative errors of a few 2^-24 at
+// the magnitudes |q| and |R_i| |q|: the 1e-3 margins below cover them a thousand times over.  HOLLOW solids touch
+// everything outside them: never skipped.
+float solids_reach2(const ws_solid &o)
+{
+    if (o.flags & WS_SOLID_HOLLOW) return INFINITY;
+    const double m = o.margin;
+    double reach;
+    if (o.kind == WS_SOLID_SPHERE) {
+        reach = o.size[0] + m;
+    } else if (o.kind == WS_SOLID_CAPSULE) {
+        reach = o.size[0] + m + (double)o.size[1] * sqrt((double)o.rot[3] * o.rot[3] + (double)o.rot[4] * o.rot[4] + (double)o.rot[5] * o.rot[5]);
+    } else {
+        // sigma_min(R)^2 = the smallest eigenvalue of the symmetric G = R R^T, from the characteristic cubic's trigonometric
+        // solution (G is 3 x 3 positive semi-definite)
+        double G[3][3];
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++)
+                G[i][j] = (double)o.rot[3 * i] * o.rot[3 * j] + (double)o.rot[3 * i + 1] * o.rot[3 * j + 1] + (double)o.rot[3 * i + 2] * o.rot[3 * j + 2];
+        const double tr = G[0][0] + G[1][1] + G[2][2], mean = tr / 3.0;
+        const double off = G[0][1] * G[0][1] + G[0][2] * G[0][2] + G[1][2] * G[1][2];
+        double dev = 2.0 * off;
+        for (int i = 0; i < 3; i++) dev += (G[i][i] - mean) * (G[i][i] - mean);
+        const double pp = sqrt(dev / 6.0);
+        double lam_min = mean;  // (a multiple of the identity)
+        if (pp > 0.0) {
+            double B[3][3];
+            for (int i = 0; i < 3; i++)
+                for (int j = 0; j < 3; j++) B[i][j] = (G[i][j] - (i == j ? mean : 0.0)) / pp;
+            const double det = B[0][0] * (B[1][1] * B[2][2] - B[1][2] * B[2][1]) - B[0][1] * (B[1][0] * B[2][2] - B[1][2] * B[2][0]) +
+                               B[0][2] * (B[1][0] * B[2][1] - B[1][1] * B[2][0]);
+            const double phi = acos(std::min(1.0, std::max(-1.0, det / 2.0))) / 3.0;
+            lam_min = mean + 2.0 * pp * cos(phi + 2.0 * 3.14159265358979323846 / 3.0);
+        }
+        // (the eigenvalue carries an absolute error of a few 1e-16 tr: taken off, with the kernel's roundings, as 1e-3 tr)
+        const double safe = lam_min - 1e-3 * tr;
+        if (!(safe > 0.0)) return INFINITY;
+        const double b0 = o.size[0] + m, b1 = o.size[1] + m, b2 = o.size[2] + m;
+        reach = sqrt((b0 * b0 + b1 * b1 + b2 * b2) / safe);
+    }
+    const double r2 = reach * reach * 1.002001;  // (reach + 0.1 %)^2
+    return r2 < 3e38 ? (float)r2 * 1.000001f : INFINITY;
+}
+
+// the kernel's argument: the solids' bytes as given, and each one's reach
+WsSolidSet solids_set(const ws_solid *s, uint32_t k)
+{
+    WsSolidSet ss{};
+    memcpy(ss.e, s, (size_t)k * sizeof(ws_solid));
+    for (uint32_t e = 0; e < k; e++) ss.reach2[e] = solids_reach2(s[e]);
+    return ss;
+}
+
+// the accumulator words on the device, zeroed on the handle's stream
+ws_status solids_sums(ws_handle *h)
+{
+    const size_t bytes = (size_t)WS_MAX_SOLIDS * WS_SOLID_WORDS * 8;
+    const ws_status st = h->solid_sums.grow(h, bytes, "solid reaction sums");
+    if (st) return st;
+    HIP_TRY(h, hipMemsetAsync(h->solid_sums.p, 0, bytes, h->stream));
+    return WS_OK;
+}
+
+// the accumulator words as the caller's outputs: counts, and the fixed-point sums as (double)sum * 2^-24
+void solids_outputs(const unsigned long long *sums, uint32_t k, uint32_t *out_contacts, double *out_impulse, double *out_angular)
+{
+    for (uint32_t e = 0; e < k; e++) {
+        const unsigned long long *w = sums + (size_t)e * WS_SOLID_WORDS;
+        if (out_contacts) out_contacts[e] = (uint32_t)w[0];
+        for (int c = 0; c < 3; c++) {
+            if (out_impulse) out_impulse[3 * e + c] = (double)(long long)w[1 + c] * 0x1p-24;
+            if (out_angular) out_angular[3 * e + c] = (double)(long long)w[4 + c] * 0x1p-24;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+// ws_apply_forces' pass with positions: one streaming kernel over `cur` behind the steps enqueued so far that edits both
+// record halves and leaves the binned state every ws_step starts from.  srt, the accept masks and accel[] are not touched
+// -- the 80-byte view keeps the last step's density, pressure and acceleration -- and no array moves, so a captured step
+// is replayed as it is.
+ws_status ws_collide_solids(ws_handle *h, const ws_solid *s, uint32_t k, uint32_t *out_contacts, double *out_impulse,
+                            double *out_angular)
+{
+    if (!h) return WS_ERR_INVALID_ARG;
+    WS_DEAD_CHECK(h);
+    if (h->flags & WS_FLAG_REFERENCE_ORDER) return fail(h, WS_ERR_UNSUPPORTED, "solids: not in the reference-order validation mode");
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (h->slab) return slab_collide_solids(h, s, k, out_contacts, out_impulse, out_angular);  // collective: validated after the gather
+    if (const char *why = solids_refusal(s, k)) return fail(h, WS_ERR_INVALID_ARG, why);
+    const bool react = out_contacts || out_impulse || out_angular;
+    if (react) {
+        const ws_status st = solids_sums(h);
+        if (st) return st;
+    }
+    HIP_TRY(h, hipMemsetAsync(h->count, 0, (size_t)h->dev.ncells * 4, h->stream));
+    wsk_collide_solids(h->stream, h->dev, h->cur, h->cid_cur, h->count, solids_set(s, k), k, react ? h->solid_sums.p : nullptr);
+    HIP_TRY(h, hipGetLastError());
+    h->pred_stale = true;  // cur.pred is behind the new positions and velocities: k_reorder<true> / refresh_pred recompute it
+    if (react) {
+        unsigned long long sums[WS_MAX_SOLIDS * WS_SOLID_WORDS];
+        HIP_TRY(h, copy_now(h, sums, h->solid_sums.p, sizeof sums, hipMemcpyDeviceToHost));
+        solids_outputs(sums, k, out_contacts, out_impulse, out_angular);
+    }
     return WS_OK;
 }
 

@@ -356,6 +356,7 @@ struct ws_handle {
     uint32_t *stats = nullptr;    // device counters: [0] particle-steps with more candidates than the mask holds
     uint8_t *mult = nullptr;      // 27 stencil multiplicities (hash aliasing), device
     WsScratch<uint32_t> force_cnt;  // ws_apply_forces: WS_MAX_FORCES per-emitter counts (allocated by the first call that asks)
+    WsScratch<unsigned long long> solid_sums;  // ws_collide_solids: WS_MAX_SOLIDS x WS_SOLID_WORDS sums (allocated by the first call that asks)
     bool alias = false;
     size_t grid_alloc_cells = 0;  // cells that count / cursor hold
     // The owners of the arrays above, one per lifetime (ws_api.cpp):
@@ -544,6 +545,20 @@ void wsk_apply_forces(hipStream_t s, const WsDev &d, WsSoA cur, uint32_t *cid, u
                       float dt, uint32_t *affected);
 void wsk_apply_forces_records(hipStream_t s, uint32_t *all, const uint32_t *cnt, uint32_t world, uint32_t max_n,
                               size_t stride_words, const WsForceSet &fs, uint32_t k, float dt, uint32_t *affected);
+// ws_collide_solids: the solids as ONE by-value kernel argument, each with its squared reach -- the squared distance from
+// its centre beyond which no particle can be in contact (solids_reach2 in ws_api.cpp; +inf = never skipped).  sums =
+// WS_MAX_SOLIDS x WS_SOLID_WORDS 64-bit device words the kernel adds to ({contacts, 3 x impulse, 3 x angular impulse} in
+// 2^-24 fixed point), or nullptr.  The first form edits `cur` in place and re-bins it, the second edits gathered
+// {id, pos, vel, pred} records (d: the container and its damping).
+#define WS_SOLID_WORDS 7u
+struct WsSolidSet {
+    ws_solid e[WS_MAX_SOLIDS];
+    float reach2[WS_MAX_SOLIDS];
+};
+void wsk_collide_solids(hipStream_t s, const WsDev &d, WsSoA cur, uint32_t *cid, uint32_t *count, const WsSolidSet &ss, uint32_t k,
+                        unsigned long long *sums);
+void wsk_collide_solids_records(hipStream_t s, const WsDev &d, uint32_t *all, const uint32_t *cnt, uint32_t world, uint32_t max_n,
+                                size_t stride_words, const WsSolidSet &ss, uint32_t k, unsigned long long *sums);
 void wsk_density(hipStream_t s, const WsDev &d, const uint32_t *start, const uint32_t *cid_srt, WsSorted srt,
                  const uint8_t *mult, bool alias, int variant, bool ieee, uint32_t *stats, WsMask mask, WsXYZ sxyz,
                  const WsEventPair *ev = nullptr, WsSched sched = WsSched{});

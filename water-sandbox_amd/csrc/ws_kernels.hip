@@ -709,6 +709,250 @@ void wsk_apply_forces_records(hipStream_t s, uint32_t *all, const uint32_t *cnt,
 }
 
 // ---------------------------------------------------------------------------------
+// ws_collide_solids: push the particles out of k solids, respond to the solids' motion, sum the reaction (never inside
+// ws_step)
+//
+// include/wsfluid.h pins every operation; IEEE arithmetic whatever the handle's flags.  The solids are a by-value kernel
+// argument (WsSolidSet: 16 x 112 B and one squared reach each): the loop over them is wave-uniform and reads them through
+// scalar loads -- no LDS and no device buffer for them.  A wave none of whose lanes lies within a solid's reach skips the
+// solid (reach2: wsk_solid_reach2, a bound no contact can lie beyond, so the skip changes no bit; +inf, never skipped,
+// for HOLLOW solids, which touch everything outside them).
+// REACT: the contact count and the six fixed-point reaction sums of every solid, reduced before they reach memory: across
+// the wave with shuffles (only in waves that have a contact), per workgroup in LDS (acc: WS_SOLID_WORDS 64-bit words per
+// solid, zeroed by the caller), and from there at most one 64-bit atomic per workgroup, solid and word
+// (solids_flush).  Every lane of the wave must call.  Returns whether any solid touched the particle.
+// ---------------------------------------------------------------------------------
+__device__ __forceinline__ long long solids_fixed(float x)
+{
+    return llrintf(fminf(fmaxf(x, -2147483648.f), 2147483648.f) * 16777216.f);
+}
+
+__device__ __forceinline__ long long wave_sum_i64(long long x)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+    return x;
+}
+
+template <bool REACT>
+__device__ __forceinline__ bool solids_eval(const WsDev &d, const WsSolidSet &ss, uint32_t k, bool active, float4 &p, float4 &v,
+                                            unsigned long long *acc)
+{
+    bool touched = false;
+    for (uint32_t e = 0; e < k; e++) {
+        const ws_solid &S = ss.e[e];
+        const float qx = p.x - S.centre[0], qy = p.y - S.centre[1], qz = p.z - S.centre[2];
+        const float q2 = qx * qx + qy * qy + qz * qz;
+        if (!__ballot(active && q2 <= ss.reach2[e])) continue;  // wave-uniform: nobody can be in contact
+        const float *R = S.rot;
+        float s, nx, ny, nz;
+        if (S.kind == WS_SOLID_SPHERE) {
+            const float dst = sqrtf(q2);
+            s = dst - S.size[0];
+            nx = dst > 0.f ? qx / dst : 0.f;
+            ny = dst > 0.f ? qy / dst : 1.f;
+            nz = dst > 0.f ? qz / dst : 0.f;
+        } else if (S.kind == WS_SOLID_CAPSULE) {
+            const float l1 = R[3] * qx + R[4] * qy + R[5] * qz;
+            const float t = fminf(fmaxf(l1, -S.size[1]), S.size[1]);
+            const float wx = qx - t * R[3], wy = qy - t * R[4], wz = qz - t * R[5];
+            const float dst = sqrtf(wx * wx + wy * wy + wz * wz);
+            s = dst - S.size[0];
+            nx = dst > 0.f ? wx / dst : R[0];
+            ny = dst > 0.f ? wy / dst : R[1];
+            nz = dst > 0.f ? wz / dst : R[2];
+        } else {
+            const float l0 = R[0] * qx + R[1] * qy + R[2] * qz;
+            const float l1 = R[3] * qx + R[4] * qy + R[5] * qz;
+            const float l2 = R[6] * qx + R[7] * qy + R[8] * qz;
+            const float a0 = fabsf(l0) - S.size[0], a1 = fabsf(l1) - S.size[1], a2 = fabsf(l2) - S.size[2];
+            const float g = fmaxf(fmaxf(a0, a1), a2);
+            float m0, m1, m2;
+            if (g > 0.f) {
+                const float u0 = copysignf(fmaxf(a0, 0.f), l0), u1 = copysignf(fmaxf(a1, 0.f), l1), u2 = copysignf(fmaxf(a2, 0.f), l2);
+                const float dst = sqrtf(u0 * u0 + u1 * u1 + u2 * u2);
+                s = dst;
+                m0 = u0 / dst; m1 = u1 / dst; m2 = u2 / dst;
+            } else {
+                const int star = a0 == g ? 0 : a1 == g ? 1 : 2;
+                s = g;
+                m0 = star == 0 ? copysignf(1.f, l0) : 0.f;
+                m1 = star == 1 ? copysignf(1.f, l1) : 0.f;
+                m2 = star == 2 ? copysignf(1.f, l2) : 0.f;
+            }
+            nx = (m0 * R[0] + m1 * R[3]) + m2 * R[6];
+            ny = (m0 * R[1] + m1 * R[4]) + m2 * R[7];
+            nz = (m0 * R[2] + m1 * R[5]) + m2 * R[8];
+        }
+        if (S.flags & WS_SOLID_HOLLOW) {
+            s = -s;
+            nx = -nx; ny = -ny; nz = -nz;
+        }
+        const bool hit = active && s < S.margin;
+        bool kicked = false;
+        float dvx = 0.f, dvy = 0.f, dvz = 0.f, rx = 0.f, ry = 0.f, rz = 0.f;
+        if (hit) {
+            touched = true;
+            const float out = S.margin - s;
+            p.x = p.x + out * nx;
+            p.y = p.y + out * ny;
+            p.z = p.z + out * nz;
+            rx = p.x - S.centre[0]; ry = p.y - S.centre[1]; rz = p.z - S.centre[2];
+            const float *W = S.angular_velocity;
+            const float ux = S.velocity[0] + (W[1] * rz - W[2] * ry);
+            const float uy = S.velocity[1] + (W[2] * rx - W[0] * rz);
+            const float uz = S.velocity[2] + (W[0] * ry - W[1] * rx);
+            const float relx = v.x - ux, rely = v.y - uy, relz = v.z - uz;
+            const float vn = relx * nx + rely * ny + relz * nz;
+            if (vn < 0.f) {
+                kicked = true;
+                const float j = (1.f + S.restitution) * (-vn);
+                const float tx = relx - vn * nx, ty = rely - vn * ny, tz = relz - vn * nz;
+                dvx = j * nx - S.friction * tx;
+                dvy = j * ny - S.friction * ty;
+                dvz = j * nz - S.friction * tz;
+                v.x = v.x + dvx;
+                v.y = v.y + dvy;
+                v.z = v.z + dvz;
+            }
+        }
+        if constexpr (REACT) {
+            const unsigned long long hits = __ballot(hit);
+            if (hits) {  // wave-uniform
+                const bool lead = (threadIdx.x & 63u) == 0u;
+                unsigned long long *a = acc + e * WS_SOLID_WORDS;
+                if (lead) atomicAdd(&a[0], (unsigned long long)__popcll(hits));
+                if (__ballot(kicked)) {
+                    long long w[6] = {0, 0, 0, 0, 0, 0};
+                    if (kicked) {
+                        const float ix = -dvx, iy = -dvy, iz = -dvz;
+                        w[0] = solids_fixed(ix);
+                        w[1] = solids_fixed(iy);
+                        w[2] = solids_fixed(iz);
+                        w[3] = solids_fixed(ry * iz - rz * iy);
+                        w[4] = solids_fixed(rz * ix - rx * iz);
+                        w[5] = solids_fixed(rx * iy - ry * ix);
+                    }
+#pragma unroll
+                    for (int c = 0; c < 6; c++) {
+                        const long long sum = wave_sum_i64(w[c]);
+                        if (lead && sum) atomicAdd(&a[1 + c], (unsigned long long)sum);
+                    }
+                }
+            }
+        }
+    }
+    if (touched) {  // the step's own container rule (force_integrate_bin)
+        const float nd = -1.f * d.damping;
+        if (p.x < d.ext_min[0]) { v.x *= nd; p.x = d.ext_min[0]; } else if (p.x > d.ext_max[0]) { v.x *= nd; p.x = d.ext_max[0]; }
+        if (p.y < d.ext_min[1]) { v.y *= nd; p.y = d.ext_min[1]; } else if (p.y > d.ext_max[1]) { v.y *= nd; p.y = d.ext_max[1]; }
+        if (p.z < d.ext_min[2]) { v.z *= nd; p.z = d.ext_min[2]; } else if (p.z > d.ext_max[2]) { v.z *= nd; p.z = d.ext_max[2]; }
+    }
+    return touched;
+}
+
+// the workgroup's sums on their way out: one 64-bit atomic per solid and word, only for the solids the workgroup touched
+// (word 0, the contact count, is non-zero exactly then).  Called by every thread, after a barrier.
+__device__ __forceinline__ void solids_flush(const unsigned long long *acc, uint32_t k, unsigned long long *__restrict__ sums)
+{
+    const uint32_t t = threadIdx.x;
+    if (t < k * WS_SOLID_WORDS && acc[t - t % WS_SOLID_WORDS] != 0ull && acc[t] != 0ull) atomicAdd(&sums[t], acc[t]);
+}
+
+// Single-GPU handles: one lane per slot of `cur` (two 16-byte loads), then what k_apply_forces does after its edit: the
+// predicted position in registers, its cell, cid[i], the per-cell count and the rank -- and BOTH record halves go back as
+// 16-byte stores, {p, id} and {v, cell id}.  cur.pred is not stored (k_reorder<true> and k_refresh_pred recompute it).
+template <bool REACT>
+__global__ void __launch_bounds__(WS_BLOCK) k_collide_solids(WsDev d, WsSoA cur, uint32_t *__restrict__ cid,
+                                                             uint32_t *__restrict__ count, WsSolidSet ss, uint32_t k,
+                                                             unsigned long long *__restrict__ sums)
+{
+    __shared__ unsigned long long acc[REACT ? WS_MAX_SOLIDS * WS_SOLID_WORDS : 1];
+    if constexpr (REACT) {
+        if (threadIdx.x < WS_MAX_SOLIDS * WS_SOLID_WORDS) acc[threadIdx.x] = 0ull;
+        __syncthreads();
+    }
+    const uint32_t i = blockIdx.x * WS_BLOCK + threadIdx.x;
+    const bool active = i < d.n;
+    float4 p = make_float4(0.f, 0.f, 0.f, 0.f), v = p;
+    if (active) {
+        p = cur.pos(i);
+        v = cur.vel(i);
+    }
+    solids_eval<REACT>(d, ss, k, active, p, v, acc);
+    uint32_t c = 0;
+    if (active) {
+        c = grid_cell(d, p.x + v.x * WS_LOOKAHEAD, p.y + v.y * WS_LOOKAHEAD, p.z + v.z * WS_LOOKAHEAD);
+        cid[i] = c;
+        cur.pos(i) = p;
+        cur.vel(i) = make_float4(v.x, v.y, v.z, __uint_as_float(c));
+    }
+    const uint32_t r = wave_run_atomic_inc(count, c, active);
+    if (active && cur.rank) cur.rank[i] = r;
+    if constexpr (REACT) {
+        __syncthreads();
+        solids_flush(acc, k, sums);
+    }
+}
+
+void wsk_collide_solids(hipStream_t s, const WsDev &d, WsSoA cur, uint32_t *cid, uint32_t *count, const WsSolidSet &ss, uint32_t k,
+                        unsigned long long *sums)
+{
+    if (!d.n) return;
+    const dim3 grid(cdiv(d.n, WS_BLOCK)), block(WS_BLOCK);
+    if (sums)
+        hipLaunchKernelGGL(k_collide_solids<true>, grid, block, 0, s, d, cur, cid, count, ss, k, sums);
+    else
+        hipLaunchKernelGGL(k_collide_solids<false>, grid, block, 0, s, d, cur, cid, count, ss, k, sums);
+}
+
+// Slab handles: the same definition on the gathered {id, pos, vel, pred} records of every rank (k_apply_forces_records'
+// layout), edited in place: position, velocity, and the predicted position by the library's own rule.  d: the GLOBAL
+// container and damping (the container rule).
+template <bool REACT>
+__global__ void __launch_bounds__(WS_BLOCK) k_collide_solids_records(WsDev d, uint32_t *__restrict__ all, const uint32_t *__restrict__ cnt,
+                                                                     uint32_t max_n, size_t stride_words, WsSolidSet ss, uint32_t k,
+                                                                     unsigned long long *__restrict__ sums)
+{
+    __shared__ unsigned long long acc[REACT ? WS_MAX_SOLIDS * WS_SOLID_WORDS : 1];
+    if constexpr (REACT) {
+        if (threadIdx.x < WS_MAX_SOLIDS * WS_SOLID_WORDS) acc[threadIdx.x] = 0ull;
+        __syncthreads();
+    }
+    const uint32_t t = blockIdx.x * WS_BLOCK + threadIdx.x, r = blockIdx.y;
+    const bool active = t < min(cnt[4 * r], max_n);
+    float *f = reinterpret_cast<float *>(all + (size_t)r * stride_words + (size_t)t * 10u + 1u);
+    float4 p = make_float4(0.f, 0.f, 0.f, 0.f), v = p;
+    if (active) {
+        p = make_float4(f[0], f[1], f[2], 0.f);
+        v = make_float4(f[3], f[4], f[5], 0.f);
+    }
+    const bool touched = solids_eval<REACT>(d, ss, k, active, p, v, acc);
+    if (active) {
+        if (touched) {
+            f[0] = p.x; f[1] = p.y; f[2] = p.z;
+            f[3] = v.x; f[4] = v.y; f[5] = v.z;
+        }
+        f[6] = p.x + v.x * WS_LOOKAHEAD; f[7] = p.y + v.y * WS_LOOKAHEAD; f[8] = p.z + v.z * WS_LOOKAHEAD;
+    }
+    if constexpr (REACT) {
+        __syncthreads();
+        solids_flush(acc, k, sums);
+    }
+}
+
+void wsk_collide_solids_records(hipStream_t s, const WsDev &d, uint32_t *all, const uint32_t *cnt, uint32_t world, uint32_t max_n,
+                                size_t stride_words, const WsSolidSet &ss, uint32_t k, unsigned long long *sums)
+{
+    if (!max_n) return;
+    const dim3 grid(cdiv(max_n, WS_BLOCK), world), block(WS_BLOCK);
+    if (sums)
+        hipLaunchKernelGGL(k_collide_solids_records<true>, grid, block, 0, s, d, all, cnt, max_n, stride_words, ss, k, sums);
+    else
+        hipLaunchKernelGGL(k_collide_solids_records<false>, grid, block, 0, s, d, all, cnt, max_n, stride_words, ss, k, sums);
+}
+
+// ---------------------------------------------------------------------------------
 // smoothing kernels, assets/simulation.wgsl:93-117 (evaluation order as written)
 // ---------------------------------------------------------------------------------
 __device__ __forceinline__ float sk_density(const WsDev &d, float dst)

@@ -1096,32 +1096,34 @@ ws_status slab_regrid(ws_handle *h, const ws_params *params, bool rebalance)
     return WS_OK;
 }
 
-// ws_apply_forces on slab handles (COLLECTIVE).  The re-grid's route on the UNCHANGED geometry: gather the state, run the
-// definition on the gathered global set on every rank (a pure per-particle function: the same records and the same
-// global counts everywhere), and reload the owned set from the edited records -- ownership follows the new predicted
-// position, exactly as a host edit through ws_write_particles would have it.  No array is freed or allocated.  (A kernel
-// applied in place to the steady-state arrays would have to undo migration decisions the force epilogue has already
-// packed; the form that moves only the particles in reach is the scale-out follow-up: DESIGN.md 9.6.)
+// ws_apply_forces and ws_collide_solids on slab handles (COLLECTIVE).  The re-grid's route on the UNCHANGED geometry:
+// gather the state, run the definition on the gathered global set on every rank (a pure per-particle function: the same
+// records and the same global sums everywhere), and reload the owned set from the edited records -- ownership follows the
+// new predicted position, exactly as a host edit through ws_write_particles would have it.  No array is freed or
+// allocated.  (A kernel applied in place to the steady-state arrays would have to undo migration decisions the force
+// epilogue has already packed; the form that moves only the particles in reach is the scale-out follow-up: DESIGN.md 9.6.)
 // The call mutates state, so its verdict is made common before anything is touched: bit 0 of the agreed word = this rank
-// refuses, the rest = a hash of k, dt and the emitters' bytes.
-ws_status slab_apply_forces(ws_handle *h, const ws_force *f, uint32_t k, float dt, uint32_t *out_affected)
+// refuses, the rest = a hash of the arguments' bytes.
+// tag / things name the call and its objects in ws_last_error.  refuse() = the argument error or nullptr; prepare() = this
+// rank's output scratch, zeroed on the stream; mix(m) hashes the arguments with m(pointer, bytes) -- the objects' bytes
+// only if `valid`; edit(recs, max_n, stride) launches the kernel on the gathered records; fetch() copies the outputs.
+template <class Refuse, class Prepare, class Mix, class Edit, class Fetch>
+ws_status slab_edit_gathered(ws_handle *h, const char *tag, const char *things, Refuse refuse, Prepare prepare, Mix mix, Edit edit, Fetch fetch)
 {
     WsSlab *S = h->slab;
     const uint32_t W = S->world;
+    const std::string pre = std::string(tag) + ": ";
     size_t stride = 0;
     uint32_t max_n = 0;
     ws_status st = slab_gather(h, WS_PACK_STATE_H, &stride, &max_n);  // (also brings every rank's capacity: S->caps)
     if (st) return st;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    const char *why = forces_refusal(f, k, dt);
-    const ws_status st_cnt = !why && out_affected ? forces_counters(h) : WS_OK;  // (this rank's alone: it refuses for all)
+    const char *why = refuse();
+    const ws_status st_cnt = !why ? prepare() : WS_OK;  // (this rank's alone: it refuses for all)
     uint32_t word = 2166136261u;  // FNV-1a
-    const auto mix = [&word](const void *p, size_t bytes) {
+    mix([&word](const void *p, size_t bytes) {
         for (size_t b = 0; b < bytes; b++) word = (word ^ static_cast<const uint8_t *>(p)[b]) * 16777619u;
-    };
-    mix(&k, 4);
-    mix(&dt, 4);
-    if (!why) mix(f, (size_t)k * sizeof(ws_force));
+    }, !why);
     word = (word << 1) | ((why || st_cnt) ? 1u : 0u);
     bool anybody = false, differ = false;
     if (W > 1) {
@@ -1135,10 +1137,8 @@ ws_status slab_apply_forces(ws_handle *h, const ws_force *f, uint32_t k, float d
     }
     if (why) return fail(h, WS_ERR_INVALID_ARG, why);
     if (st_cnt) return st_cnt;
-    if (anybody) return fail(h, WS_ERR_INVALID_ARG, "forces: another slab refused its arguments; nothing was changed");
-    if (differ) return fail(h, WS_ERR_INVALID_ARG, "forces: the slabs were given different emitters; nothing was changed");
-    WsForceSet fs{};
-    memcpy(fs.e, f, (size_t)k * sizeof(ws_force));
+    if (anybody) return fail(h, WS_ERR_INVALID_ARG, (pre + "another slab refused its arguments; nothing was changed").c_str());
+    if (differ) return fail(h, WS_ERR_INVALID_ARG, (pre + "the slabs were given different " + things + "; nothing was changed").c_str());
     uint32_t *recs = const_cast<uint32_t *>(slab_gathered(S));  // (scratch of the gather: nothing the step reads)
     // the edit, and the x-layer histogram of the edited set: every slab's owned count under the cuts against every slab's
     // capacity, all alike, before the old state is given up (slab_regrid).  A failure in here is this rank's alone and is
@@ -1146,11 +1146,11 @@ ws_status slab_apply_forces(ws_handle *h, const ws_force *f, uint32_t k, float d
     const uint32_t nx = (uint32_t)h->dev.gdim_x;
     std::vector<uint32_t> hist(nx);
     {
-        wsk_apply_forces_records(h->stream, recs, S->cnt_all.p, W, max_n, stride, fs, k, dt, out_affected ? h->force_cnt.p : nullptr);
+        edit(recs, max_n, stride);
         ws_status mine = slab_layer_hist(h, h->dev, recs, max_n, stride, &hist);
         if (!mine) {
             hipError_t e = hipGetLastError();
-            if (e == hipSuccess && out_affected) e = copy_now(h, out_affected, h->force_cnt.p, (size_t)k * 4, hipMemcpyDeviceToHost);
+            if (e == hipSuccess) e = fetch();
             if (e != hipSuccess) {
                 (void)hipGetLastError();
                 mine = fail(h, e == hipErrorOutOfMemory ? WS_ERR_OUT_OF_MEMORY : WS_ERR_HIP, "edit of the gathered state", e);
@@ -1160,16 +1160,16 @@ ws_status slab_apply_forces(ws_handle *h, const ws_force *f, uint32_t k, float d
         uint32_t failed = 0;
         const ws_status st_agree = slab_agree(h, mine ? 1u : 0u, &failed);
         if (st_agree) return st_agree;
-        if (mine) return fail(h, mine, ("forces: " + why_failed + "; nothing was changed").c_str());
-        if (failed) return fail(h, WS_ERR_OUT_OF_MEMORY, "forces: another slab could not edit the gathered state; nothing was changed");
+        if (mine) return fail(h, mine, (pre + why_failed + "; nothing was changed").c_str());
+        if (failed) return fail(h, WS_ERR_OUT_OF_MEMORY, (pre + "another slab could not edit the gathered state; nothing was changed").c_str());
     }
     for (uint32_t r = 0; r < W; r++) {
         uint64_t cnt = 0;
         for (uint32_t l = S->cuts[r]; l < S->cuts[r + 1] && l < nx; l++) cnt += hist[l];
         if (cnt > S->caps[r]) {
             char buf[200];
-            snprintf(buf, sizeof buf, "forces: slab %u would own %llu particles, its capacity is %u (ws_device_cfg.capacity); nothing was changed",
-                     r, (unsigned long long)cnt, S->caps[r]);
+            snprintf(buf, sizeof buf, "%s: slab %u would own %llu particles, its capacity is %u (ws_device_cfg.capacity); nothing was changed",
+                     tag, r, (unsigned long long)cnt, S->caps[r]);
             return fail(h, WS_ERR_OUT_OF_MEMORY, buf);
         }
     }
@@ -1185,11 +1185,51 @@ ws_status slab_apply_forces(ws_handle *h, const ws_force *f, uint32_t k, float d
     const ws_status st_agree = slab_agree(h, st ? 1u : 0u, &failed);
     if (st || st_agree || failed) {
         h->dead = true;
-        h->err = st ? "forces: the reload failed after the old state was given up (" + reason + "); the handle is unusable"
+        h->err = st ? pre + "the reload failed after the old state was given up (" + reason + "); the handle is unusable"
                     : "another slab failed its reload; the handle is unusable";
         return st ? st : (st_agree ? st_agree : WS_ERR_OUT_OF_MEMORY);
     }
     return WS_OK;
+}
+
+ws_status slab_apply_forces(ws_handle *h, const ws_force *f, uint32_t k, float dt, uint32_t *out_affected)
+{
+    WsSlab *S = h->slab;
+    return slab_edit_gathered(
+        h, "forces", "emitters", [&] { return forces_refusal(f, k, dt); }, [&] { return out_affected ? forces_counters(h) : WS_OK; },
+        [&](auto m, bool valid) {
+            m(&k, 4);
+            m(&dt, 4);
+            if (valid) m(f, (size_t)k * sizeof(ws_force));
+        },
+        [&](uint32_t *recs, uint32_t max_n, size_t stride) {
+            WsForceSet fs{};
+            memcpy(fs.e, f, (size_t)k * sizeof(ws_force));
+            wsk_apply_forces_records(h->stream, recs, S->cnt_all.p, S->world, max_n, stride, fs, k, dt, out_affected ? h->force_cnt.p : nullptr);
+        },
+        [&] { return out_affected ? copy_now(h, out_affected, h->force_cnt.p, (size_t)k * 4, hipMemcpyDeviceToHost) : hipSuccess; });
+}
+
+// (the outputs reach the caller only after the edit has been agreed on: a refused call writes nothing)
+ws_status slab_collide_solids(ws_handle *h, const ws_solid *s, uint32_t k, uint32_t *out_contacts, double *out_impulse,
+                              double *out_angular)
+{
+    WsSlab *S = h->slab;
+    const bool react = out_contacts || out_impulse || out_angular;
+    unsigned long long sums[WS_MAX_SOLIDS * WS_SOLID_WORDS];
+    const ws_status st = slab_edit_gathered(
+        h, "solids", "solids", [&] { return solids_refusal(s, k); }, [&] { return react ? solids_sums(h) : WS_OK; },
+        [&](auto m, bool valid) {
+            m(&k, 4);
+            if (valid) m(s, (size_t)k * sizeof(ws_solid));
+        },
+        [&](uint32_t *recs, uint32_t max_n, size_t stride) {
+            wsk_collide_solids_records(h->stream, h->dev, recs, S->cnt_all.p, S->world, max_n, stride, solids_set(s, k), k,
+                                       react ? h->solid_sums.p : nullptr);
+        },
+        [&] { return react ? copy_now(h, sums, h->solid_sums.p, sizeof sums, hipMemcpyDeviceToHost) : hipSuccess; });
+    if (!st && react) solids_outputs(sums, k, out_contacts, out_impulse, out_angular);
+    return st;
 }
 
 // ws_sample_density_* on a slab handle (COLLECTIVE): every rank's current positions all-gathered by id into S->g_out

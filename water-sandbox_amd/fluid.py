@@ -55,7 +55,7 @@ ABI_SYMBOLS = [
     "ws_extract_aniso_surface", "ws_cast_rays", "ws_cast_camera",
     "ws_read_velocities", "ws_sample_velocity_grid", "ws_sample_velocity_points", "ws_advect_points",
     "ws_default_whitewater_emit_params", "ws_default_whitewater_step_params", "ws_read_whitewater", "ws_emit_whitewater",
-    "ws_step_whitewater", "ws_apply_forces", "ws_default_body_params", "ws_body_forces",
+    "ws_step_whitewater", "ws_apply_forces", "ws_default_body_params", "ws_body_forces", "ws_collide_solids",
 ]
 
 
@@ -150,6 +150,29 @@ class WsForce(C.Structure):
         ("radius", C.c_float),
         ("strength", C.c_float),
         ("damping", C.c_float),
+        ("reserved", C.c_uint32 * 2),
+    ]
+
+
+WS_SOLID_SPHERE, WS_SOLID_BOX, WS_SOLID_CAPSULE = 0, 1, 2
+WS_SOLID_HOLLOW = 1
+WS_MAX_SOLIDS = 16
+
+
+class WsSolid(C.Structure):
+    """ws_solid: one obstacle of ws_collide_solids -- a sphere, a box or a capsule, solid or hollow (include/wsfluid.h)."""
+
+    _fields_ = [
+        ("kind", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("centre", C.c_float * 3),
+        ("rot", C.c_float * 9),
+        ("size", C.c_float * 3),
+        ("velocity", C.c_float * 3),
+        ("angular_velocity", C.c_float * 3),
+        ("restitution", C.c_float),
+        ("friction", C.c_float),
+        ("margin", C.c_float),
         ("reserved", C.c_uint32 * 2),
     ]
 
@@ -285,6 +308,7 @@ def bind_library(path):
     L.ws_step_whitewater.argtypes = [vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]
     L.ws_apply_forces.argtypes = [vp, vp, u32, C.c_float, vp]
     L.ws_default_body_params.argtypes = [vp]
+    L.ws_collide_solids.argtypes = [vp, vp, u32, vp, vp, vp]
     L.ws_body_forces.argtypes = [vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, vp]
     return L
 
@@ -555,6 +579,34 @@ def apply_forces(L, h, check, forces, dt, counts=True):
     out = np.zeros(max(len(forces), 1), np.uint32) if counts else None
     check(L.ws_apply_forces(h, C.byref(arr), len(forces), dt, out.ctypes.data if counts else None))
     return out[:len(forces)] if counts else None
+
+
+def solid(kind, centre, size, rot=(1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0), hollow=False, velocity=(0.0, 0.0, 0.0),
+          angular_velocity=(0.0, 0.0, 0.0), restitution=0.0, friction=0.0, margin=0.0):
+    """One ws_solid: kind = WS_SOLID_SPHERE / _BOX / _CAPSULE (or "sphere" / "box" / "capsule"); size = a radius, three
+    half extents or (radius, half length); rot = the nine floats of the rows R_0 R_1 R_2 (or a 3 x 3 nested sequence)."""
+    kind = {"sphere": WS_SOLID_SPHERE, "box": WS_SOLID_BOX, "capsule": WS_SOLID_CAPSULE}.get(kind, kind)
+    size = [float(x) for x in np.atleast_1d(np.asarray(size, np.float64))]
+    rot = [float(x) for x in np.asarray(rot, np.float64).reshape(-1)]
+    return WsSolid(kind, WS_SOLID_HOLLOW if hollow else 0, (C.c_float * 3)(*centre), (C.c_float * 9)(*rot),
+                   (C.c_float * 3)(*(size + [0.0] * (3 - len(size)))), (C.c_float * 3)(*velocity), (C.c_float * 3)(*angular_velocity),
+                   restitution, friction, margin, (C.c_uint32 * 2)(0, 0))
+
+
+def collide_solids(L, h, check, solids, reaction=True):
+    """ws_collide_solids: push the fluid out of the solids, respond to their motion, sum the reaction (include/wsfluid.h
+    has the definition).  solids: a WsSolid or a sequence of them.  Returns (contacts (k,) uint32, impulse (k, 3) float64,
+    angular (k, 3) float64) -- per unit of particle mass, angular about each solid's centre -- or None with
+    reaction=False (a single handle then only enqueues)."""
+    solids = [solids] if isinstance(solids, WsSolid) else list(solids)
+    k = len(solids)
+    arr = (WsSolid * max(k, 1))(*solids)
+    if not reaction:
+        check(L.ws_collide_solids(h, C.byref(arr), k, None, None, None))
+        return None
+    contacts, impulse, angular = np.zeros(max(k, 1), np.uint32), np.zeros((max(k, 1), 3)), np.zeros((max(k, 1), 3))
+    check(L.ws_collide_solids(h, C.byref(arr), k, contacts.ctypes.data, impulse.ctypes.data, angular.ctypes.data))
+    return contacts[:k], impulse[:k], angular[:k]
 
 
 def body_params(**fields):
@@ -911,6 +963,13 @@ class FluidWorker:
         to the velocities as one Euler step of dt.  The per-emitter counts of affected particles, or None with
         counts=False (the call then only enqueues)."""
         return apply_forces(self._L, self._h, self._check, forces, dt, counts)
+
+    def collide_solids(self, solids, reaction=True):
+        """Put solid things in the water between two steps: solids = solid(...) or a list of up to 16.  Particles nearer
+        than a solid's margin are pushed out and bounce off its moving surface.  (contacts, impulse, angular): per solid
+        the contact count and the momentum the solid took per unit of particle mass, linear and about its centre -- or None
+        with reaction=False (the call then only enqueues)."""
+        return collide_solids(self._L, self._h, self._check, solids, reaction)
 
     def body_forces(self, params, xyz, velocity, volume, body_start, centres, samples=False):
         """What the fluid does to things floating in it: buoyancy and drag on nb host-owned bodies, each a group of sample

@@ -378,6 +378,28 @@ class FluidWorker {
                              b.submerged.data(), b.wet.data(), nullptr, nullptr));
     }
 
+    // Solid things in the water (include/wsfluid.h ws_collide_solids): the fluid is pushed out of the solids and bounces
+    // off their moving surfaces; per solid the contacts and the momentum it took per unit of particle mass -- the other
+    // half of body_forces.  react = false: only enqueue, nothing is waited for.
+    struct SolidReaction {
+        std::vector<uint32_t> contacts;      // per solid
+        std::vector<double> impulse, angular;  // per solid x 3; angular about the solid's centre
+    };
+    SolidReaction collide_solids(const std::vector<ws_solid> &solids, bool react = true)
+    {
+        SolidReaction r;
+        if (solids.empty()) return r;
+        if (!react) {
+            check(ws_collide_solids(h_, solids.data(), (uint32_t)solids.size(), nullptr, nullptr, nullptr));
+            return r;
+        }
+        r.contacts.resize(solids.size());
+        r.impulse.resize(3 * solids.size());
+        r.angular.resize(3 * solids.size());
+        check(ws_collide_solids(h_, solids.data(), (uint32_t)solids.size(), r.contacts.data(), r.impulse.data(), r.angular.data()));
+        return r;
+    }
+
     std::vector<float> read_speeds()
     {
         std::vector<float> out(n_);

@@ -450,6 +450,11 @@ class SlabWorker:
         emitters); the counts are global.  counts=False: this rank applies without asking for them (None)."""
         return fluid.apply_forces(self._L, self._h, self._check, forces, dt, counts)
 
+    def collide_solids(self, solids, reaction=True):
+        """FluidWorker.collide_solids on the GLOBAL particle set (COLLECTIVE: every rank makes the same call with the same
+        solids); the outputs are global.  reaction=False: this rank applies without asking for them (None)."""
+        return fluid.collide_solids(self._L, self._h, self._check, solids, reaction)
+
     def body_forces(self, params, xyz, velocity, volume, body_start, centres, samples=False, want=True):
         """FluidWorker.body_forces over the GLOBAL particle set (COLLECTIVE); want=False: only contribute (None)."""
         return fluid.body_forces(self._L, self._h, self._check, params, xyz, velocity, volume, body_start, centres, samples, want)
