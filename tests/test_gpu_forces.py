@@ -11,7 +11,7 @@ from test_gpu_aniso_surface import _slab_run, same_bits
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
-BLOCK = 256  # threads per workgroup of k_apply_forces (WS_BLOCK)
+BLOCK = 256  # threads per workgroup of k_edit_current (WS_BLOCK)
 
 
 def _xyz(rec, field):

@@ -1,21 +1,23 @@
 """ws_collide_solids on the GPU: bit for bit against the numpy restatement (tests/solids_ref.py) at every launch shape --
 positions, velocities, predicted positions, contact counts and both reaction sums -- the step picking the edit up exactly
 as it picks up a host edit through ws_write_particles, a call that touches nothing changing nothing (a captured step
-included), the views the call must leave alone, water that stays out of a sphere and inside a hollow box, slabs,
-refusals."""
+included), the views the call must leave alone, water that stays out of a sphere and inside a hollow box, slabs, this
+call and ws_apply_forces between the same two steps in either order, refusals."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import forces_ref as F
 import solids_ref as S
 from test_gpu_aniso_surface import _slab_run, same_bits
-from test_gpu_forces import _scene, _xyz
+from test_gpu_forces import _emitter_sets, _host_apply, _scene, _xyz
+from test_gpu_forces import _moving as _moving_forces
 from test_solids_reference import bounds
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
-BLOCK = 256  # threads per workgroup of k_collide_solids (WS_BLOCK)
+BLOCK = 256  # threads per workgroup of k_edit_current (WS_BLOCK)
 
 
 def _ext(params):
@@ -358,7 +360,91 @@ def test_slabs_give_the_same_bits_and_the_same_global_sums_as_a_single_handle(ws
                 assert all(np.array_equal(x, y) for x, y in zip(a, b)), (r, a, b)
 
 
-# ---- 7. refusals ------------------------------------------------------------------------------------------------------------------
+# ---- 7. two edits between the same two steps ------------------------------------------------------------------------------------
+ORDERS = {"forces-then-solids": ("forces", "solids"), "solids-then-forces": ("solids", "forces")}
+STATE = ("position", "velocity", "predicted_position")
+
+
+def _host_two_edits(order, forces, solids, dt, params, host):
+    """Both edits in `order` on `host` with no step between them, each one the host's route: a read, the restatement, a
+    write back.  Returns the particles that both edits changed, the restatements' outputs per edit and the state."""
+    both, outputs = np.ones(host.n, bool), []
+    for what in order:
+        rec = host.read_vec("particles")
+        if what == "forces":
+            both &= F.accelerate(_xyz(rec, "position"), _xyz(rec, "velocity"), forces)[1]
+            outputs.append(_host_apply(host, forces, dt))
+        else:
+            outputs.append(_host_collide(host, solids, params))
+            both &= outputs[-1]["touched"]
+    return both, outputs, host.read_vec("particles")
+
+
+def _call_two_edits(ws, w, order, forces, solids, dt, outputs):
+    """The two calls on `w`, counts and reaction on: the restatements' outputs, and the state they leave."""
+    for what, want in zip(order, outputs):
+        if what == "forces":
+            got = w.apply_forces(F.to_ws(ws, forces), dt)
+            assert got.dtype == np.uint32 and np.array_equal(got, want), (order, got, want)
+        else:
+            _same_reaction(w.collide_solids(S.to_ws(ws, solids)), want, order)
+    return w.read_vec("particles")
+
+
+def _same_state(got, want, fields, what):
+    for f in fields:
+        assert np.array_equal(got[f].view(np.uint32), want[f].view(np.uint32)), (what, f)
+
+
+@pytest.mark.parametrize("order", list(ORDERS))
+def test_two_edits_between_two_steps_are_two_host_edits(ws, order):
+    n = BLOCK + 1  # two workgroups, the second with one lane
+    params = ws.make_params(container_size=(4.0, 4.0, 4.0))
+    rng = np.random.default_rng(n)
+    pos = rng.uniform(-1.0, 1.0, (n, 3)).astype(F32)
+    vel = rng.normal(0.0, 2.0, (n, 3)).astype(F32)
+    forces, solids = _emitter_sets()["mixed16"], _solid_sets()["mixed16"]
+    a, b = ws.FluidWorker(pos, params), ws.FluidWorker(pos, params)
+    for w in (a, b):
+        _load(w, w.read_vec("particles"), vel=vel)
+    dt = F32(1.0 / 60.0)
+    both, outputs, want = _host_two_edits(ORDERS[order], forces, solids, dt, params, b)
+    assert both.any()  # some particle is seen by an emitter AND touched by a solid
+    got = _call_two_edits(ws, a, ORDERS[order], forces, solids, dt, outputs)
+    _same_state(got, want, STATE, order)
+    assert not same_bits(_xyz(want, "position"), pos) and not same_bits(_xyz(want, "velocity"), vel)
+    a.run(1)
+    b.run(1)
+    _same_state(a.read_vec("particles"), b.read_vec("particles"), want.dtype.names, order)
+    assert a.steps_done() == 1
+    a.close()
+    b.close()
+
+
+@pytest.mark.parametrize("order", list(ORDERS))
+def test_two_edits_between_two_steps_on_slabs(ws, order):
+    pos, params, _, centre, reach = _scene(ws, "merged-4096")
+    forces = _moving_forces(2, centre, reach, float(params.smoothing_radius))
+    solids = _moving(2, centre, reach)
+    host = ws.FluidWorker(pos, params)
+    dt = F32(params.delta_time)
+    both, outputs, want = _host_two_edits(ORDERS[order], forces, solids, dt, params, host)
+    assert both.any()
+    host.run(1)
+    want_stepped = host.read_vec("particles")
+    host.close()
+
+    def program(s, r):
+        got = _call_two_edits(ws, s, ORDERS[order], forces, solids, dt, outputs)  # (global outputs on every rank)
+        s.run(1)
+        return got, s.read_vec("particles")
+
+    for r, (got, stepped) in enumerate(_slab_run(ws, params, pos, 2, 0, program)):
+        _same_state(got, want, STATE, (order, r))
+        _same_state(stepped, want_stepped, want.dtype.names, (order, r))
+
+
+# ---- 8. refusals ------------------------------------------------------------------------------------------------------------------
 def test_invalid_arguments_are_refused_and_the_handle_steps_on(ws):
     pos, params = ws.workloads.make_workload("c1", "cloud")
     w = ws.FluidWorker(pos, params)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Timing of k_apply_forces (ws_apply_forces) beside three things from the SAME trace: the five kernels
+"""Timing of k_edit_current<EditForces<..>> (ws_apply_forces) beside three things from the SAME trace: the five kernels
 of the step that follows it, the kernel as a share of that step, and the floor for the bytes it must move -- the record
 read (32 B), the velocity record written (16 B) and cell id, rank and count (about 12 B) per particle -- at the float4
 copy rate bench.py's roofline uses (HBM_COPY_GBS).
@@ -75,19 +75,19 @@ def main():
     kt = glob.glob(os.path.join(out, "trace", "**", "*_kernel_trace.csv"), recursive=True)[0]
     rows = sorted(csv.DictReader(open(kt)), key=lambda r: int(r["Start_Timestamp"]))
     disp = [(r["Kernel_Name"], (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) * 1e-3) for r in rows
-            if "k_apply_forces" in r["Kernel_Name"] or any(k in r["Kernel_Name"] for k in STEP_KERNELS)]
+            if "k_edit_current" in r["Kernel_Name"] or any(k in r["Kernel_Name"] for k in STEP_KERNELS)]
     cases = json.load(open(cases_path))
     result = []
     i = 0
     for at in sorted({c["step"] for c in cases}):
         mine = [c for c in cases if c["step"] == at]
-        while "k_apply_forces" not in disp[i][0]:  # the steps before this state
+        while "k_edit_current" not in disp[i][0]:  # the steps before this state
             i += 1
         for c in mine:
             times = []
             for _ in range(c["repeats"]):
                 name, us = disp[i]
-                assert ("k_apply_forces<true>" if c["counts"] else "k_apply_forces<false>") in name, (c, name)
+                assert "k_edit_current<EditForces<%s>" % ("true" if c["counts"] else "false") in name, (c, name)
                 times.append(us)
                 i += 1
             c["us"] = float(np.median(times))

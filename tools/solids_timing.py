@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""Timing of k_collide_solids (ws_collide_solids) beside three things from the SAME trace: the floor for the
+"""Timing of k_edit_current<EditSolids<..>> (ws_collide_solids) beside three things from the SAME trace: the floor for the
 bytes it must move -- both record halves read and written (64 B) and cell id and rank (8 B) per particle -- at the float4
 copy rate bench.py's roofline uses (HBM_COPY_GBS); the five kernels of the step that follows, for the share; and
-k_apply_forces with 16 emitters with and without counts, whose counted / uncounted ratio is the price of per-wave
+k_edit_current<EditForces<..>> with 16 emitters with and without counts, whose counted / uncounted ratio is the price of per-wave
 atomics that the workgroup reduction of the reaction is there to avoid.
 
 C3 (4 M particles, lattice) in the sparse window (step 10) and settled (step 400): k = 1 and k = 16 solids, with and
@@ -65,7 +65,7 @@ def child(out_path, repeats):
         for counts in (False, True):
             for _ in range(repeats):
                 affected = w.apply_forces(many, dt, counts=counts)
-            cases.append(dict(step=at, kernel="k_apply_forces", k=16, react=counts, repeats=repeats, n=len(pos),
+            cases.append(dict(step=at, kernel="EditForces", k=16, react=counts, repeats=repeats, n=len(pos),
                               contacts=None if affected is None else [int(a) for a in affected]))
         for k in (1, 16):
             for react in (False, True):
@@ -73,7 +73,7 @@ def child(out_path, repeats):
                 for _ in range(repeats):
                     launch += 1
                     got = w.collide_solids(solids(k, 0.25 * h * launch), reaction=react)
-                cases.append(dict(step=at, kernel="k_collide_solids", k=k, react=react, repeats=repeats, n=len(pos),
+                cases.append(dict(step=at, kernel="EditSolids", k=k, react=react, repeats=repeats, n=len(pos),
                                   contacts=None if got is None else [int(c) for c in got[0]]))
         w.run(1)  # the step the shares are taken of
         w.sync()
@@ -94,7 +94,7 @@ def main():
     subprocess.check_call(cmd, timeout=1100, env=env)
     kt = glob.glob(os.path.join(out, "trace", "**", "*_kernel_trace.csv"), recursive=True)[0]
     rows = sorted(csv.DictReader(open(kt)), key=lambda r: int(r["Start_Timestamp"]))
-    edits = ("k_apply_forces", "k_collide_solids")
+    edits = ("k_edit_current",)
     disp = [(r["Kernel_Name"], (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) * 1e-3) for r in rows
             if any(k in r["Kernel_Name"] for k in edits + STEP_KERNELS)]
     cases = json.load(open(cases_path))
@@ -108,7 +108,7 @@ def main():
             times = []
             for _ in range(c["repeats"]):
                 name, us = disp[i]
-                assert "%s<%s>" % (c["kernel"], "true" if c["react"] else "false") in name, (c, name)
+                assert "k_edit_current<%s<%s>" % (c["kernel"], "true" if c["react"] else "false") in name, (c, name)
                 times.append(us)
                 i += 1
             c["us"] = float(np.median(times))
@@ -122,11 +122,11 @@ def main():
                 break
         total = sum(step.values())
         for c in mine:
-            floor_us = c["n"] * BYTES_PER_PARTICLE / (HBM_COPY_GBS * 1e9) * 1e6 if c["kernel"] == "k_collide_solids" else None
+            floor_us = c["n"] * BYTES_PER_PARTICLE / (HBM_COPY_GBS * 1e9) * 1e6 if c["kernel"] == "EditSolids" else None
             result.append({"step": at, "kernel": c["kernel"], "k": c["k"], "react": c["react"], "us": c["us"], "floor_us": floor_us,
                            "floor_frac": None if floor_us is None else floor_us / c["us"], "share_of_step": c["us"] / total,
                            "step_us": total, "contacts": c["contacts"]})
-    print("%-6s %-18s %-4s %-9s %10s %10s %12s %10s %10s" % ("step", "kernel", "k", "sums", "us", "floor us", "floor / us", "step us", "share"))
+    print("%-6s %-18s %-4s %-9s %10s %10s %12s %10s %10s" % ("step", "k_edit_current", "k", "sums", "us", "floor us", "floor / us", "step us", "share"))
     for r in result:
         print("%-6d %-18s %-4d %-9s %10.1f %10s %12s %10.1f %9.1f%%" % (
             r["step"], r["kernel"], r["k"], "yes" if r["react"] else "no", r["us"],
@@ -135,9 +135,8 @@ def main():
     for at in sorted({r["step"] for r in result}):
         def us(kernel, k, react):
             return next(r["us"] for r in result if (r["step"], r["kernel"], r["k"], r["react"]) == (at, kernel, k, react))
-        print("step %d, k = 16: reaction on / off %.2f (k_collide_solids), counts on / off %.2f (k_apply_forces)" % (
-            at, us("k_collide_solids", 16, True) / us("k_collide_solids", 16, False),
-            us("k_apply_forces", 16, True) / us("k_apply_forces", 16, False)))
+        print("step %d, k = 16: reaction on / off %.2f (EditSolids), counts on / off %.2f (EditForces)" % (
+            at, us("EditSolids", 16, True) / us("EditSolids", 16, False), us("EditForces", 16, True) / us("EditForces", 16, False)))
     json.dump(result, open(os.path.join(out, "solids_timing.json"), "w"), indent=1)
     print(json.dumps(result))
 

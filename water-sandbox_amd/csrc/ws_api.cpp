@@ -30,9 +30,8 @@ ws_status slab_reset(ws_handle *h, const float *pos_xyz);
 ws_status slab_write_particles(ws_handle *h, const ws_particle80 *in);
 ws_status slab_regrid(ws_handle *h, const ws_params *params, bool rebalance);
 ws_status slab_field_positions(ws_handle *h, const float **xyz, WsDev *global, bool with_vel);
-ws_status slab_apply_forces(ws_handle *h, const ws_force *f, uint32_t k, float dt, uint32_t *out_affected);
-ws_status slab_collide_solids(ws_handle *h, const ws_solid *s, uint32_t k, uint32_t *out_contacts, double *out_impulse,
-                              double *out_angular);
+template <class Call>
+ws_status slab_edit_gathered(ws_handle *h, Call &call);
 // ws_field.inc
 void free_field(ws_handle *h);
 
@@ -78,6 +77,16 @@ hipError_t copy_now(ws_handle *h, void *dst, const void *src, size_t bytes, hipM
 {
     const hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, h->stream);
     return e != hipSuccess ? e : hipStreamSynchronize(h->stream);
+}
+
+// `bytes` of a call's output scratch: grown if need be, and zeroed on the handle's stream
+template <class T>
+ws_status scratch_zeroed(ws_handle *h, WsScratch<T> &buf, size_t bytes, const char *what)
+{
+    const ws_status st = buf.grow(h, bytes, what);
+    if (st) return st;
+    HIP_TRY(h, hipMemsetAsync(buf.p, 0, bytes, h->stream));
+    return WS_OK;
 }
 
 // Rust f32::powi -> llvm.powi -> compiler-rt __powisf2 (square-and-multiply).
@@ -1265,62 +1274,97 @@ ws_status ws_write_particles(ws_handle *h, const ws_particle80 *in)
 
 namespace {
 
-// the argument errors of ws_apply_forces (nullptr = acceptable); nothing is touched before this has passed
+// ws_apply_forces and ws_collide_solids are one route around two descriptions.  A description (ForcesCall, SolidsCall)
+// carries
+//   tag, things     the call and its objects in ws_last_error;
+//   refuse()        the argument error, or nullptr; nothing is touched before it has passed;
+//   prepare(h)      after that: `args`, the kernel's argument, built once, and the output scratch it points to, grown
+//                   and zeroed on the handle's stream;
+//   mix(m, valid)   the arguments hashed with m(pointer, bytes) for the slabs' agreement -- the objects' bytes only if
+//                   `valid`;
+//   fetch(h)        the kernel's sums, complete on return.
+// The route: a single handle validates, then one streaming pass over `cur` behind the steps enqueued so far leaves the
+// edited records and the binned state every ws_step starts from (bin_current's pair: the counts zeroed, then the kernel
+// that draws cell ids, counts and ranks).  srt, the accept masks and accel[] are not touched -- the 80-byte view keeps
+// the last step's density, pressure and acceleration -- and no array moves, so a captured step is replayed as it is.
+// Slab handles gather first and validate in common (slab_edit_gathered, ws_slab.inc).
+template <class Call>
+ws_status edit_fluid(ws_handle *h, Call &call)
+{
+    if (!h) return WS_ERR_INVALID_ARG;
+    WS_DEAD_CHECK(h);
+    if (h->flags & WS_FLAG_REFERENCE_ORDER)
+        return fail(h, WS_ERR_UNSUPPORTED, (std::string(call.tag) + ": not in the reference-order validation mode").c_str());
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (h->slab) return slab_edit_gathered(h, call);  // collective: validated after the gather
+    if (const char *why = call.refuse()) return fail(h, WS_ERR_INVALID_ARG, why);
+    const ws_status st = call.prepare(h);
+    if (st) return st;
+    HIP_TRY(h, hipMemsetAsync(h->count, 0, (size_t)h->dev.ncells * 4, h->stream));
+    wsk_edit_current(h->stream, h->dev, h->cur, h->cid_cur, h->count, call.args);
+    HIP_TRY(h, hipGetLastError());
+    h->pred_stale = true;  // cur.pred is behind the edited records: k_reorder<true> / refresh_pred recompute it
+    HIP_TRY(h, call.fetch(h));
+    return WS_OK;
+}
+
+// the argument errors of ws_apply_forces (nullptr = acceptable)
 const char *forces_refusal(const ws_force *f, uint32_t k, float dt)
 {
-    const auto bad = [](float x) { return !isfinite(x) || fabsf(x) > 1e15f; };
     if (!f) return "forces: f is NULL";
     if (k < 1u || k > WS_MAX_FORCES) return "forces: k outside 1 .. WS_MAX_FORCES";
-    if (bad(dt) || !(dt > 0.f)) return "forces: dt must be finite, > 0 and at most 1e15";
+    if (ws_bad_float(dt) || !(dt > 0.f)) return "forces: dt must be finite, > 0 and at most 1e15";
     for (uint32_t e = 0; e < k; e++) {
         if (f[e].kind > WS_FORCE_VORTEX) return "forces: unknown kind";
         if (f[e].reserved[0] || f[e].reserved[1]) return "forces: reserved words must be 0";
         for (int c = 0; c < 3; c++)
-            if (bad(f[e].centre[c]) || bad(f[e].axis[c])) return "forces: centre and axis must be finite and at most 1e15 in magnitude";
-        if (bad(f[e].strength) || bad(f[e].damping)) return "forces: strength and damping must be finite and at most 1e15 in magnitude";
+            if (ws_bad_float(f[e].centre[c]) || ws_bad_float(f[e].axis[c])) return "forces: centre and axis must be finite and at most 1e15 in magnitude";
+        if (ws_bad_float(f[e].strength) || ws_bad_float(f[e].damping)) return "forces: strength and damping must be finite and at most 1e15 in magnitude";
         if (f[e].damping < 0.f) return "forces: damping must be >= 0";
-        if (bad(f[e].radius) || !(f[e].radius > 0.f)) return "forces: radius must be finite, > 0 and at most 1e15";
+        if (ws_bad_float(f[e].radius) || !(f[e].radius > 0.f)) return "forces: radius must be finite, > 0 and at most 1e15";
     }
     return nullptr;
 }
 
-// the k per-emitter counters on the device, zeroed on the handle's stream
-ws_status forces_counters(ws_handle *h)
-{
-    const ws_status st = h->force_cnt.grow(h, WS_MAX_FORCES * 4, "force counters");
-    if (st) return st;
-    HIP_TRY(h, hipMemsetAsync(h->force_cnt.p, 0, WS_MAX_FORCES * 4, h->stream));
-    return WS_OK;
-}
+struct ForcesCall {
+    const ws_force *f;
+    uint32_t k;
+    float dt;
+    uint32_t *out_affected;
+    const char *tag = "forces", *things = "emitters";
+    WsForceArgs args{};
+    const char *refuse() const { return forces_refusal(f, k, dt); }
+    ws_status prepare(ws_handle *h)  // (the k per-emitter counters only if the caller asks for them)
+    {
+        memcpy(args.fs.e, f, (size_t)k * sizeof(ws_force));
+        args.k = k;
+        args.dt = dt;
+        if (!out_affected) return WS_OK;
+        const ws_status st = scratch_zeroed(h, h->force_cnt, WS_MAX_FORCES * 4, "force counters");
+        args.affected = h->force_cnt.p;
+        return st;
+    }
+    template <class M>
+    void mix(M m, bool valid) const
+    {
+        m(&k, 4);
+        m(&dt, 4);
+        if (valid) m(f, (size_t)k * sizeof(ws_force));
+    }
+    hipError_t fetch(ws_handle *h) const
+    {
+        return out_affected ? copy_now(h, out_affected, h->force_cnt.p, (size_t)k * 4, hipMemcpyDeviceToHost) : hipSuccess;
+    }
+};
 
 }  // namespace
 
 extern "C" {
 
-// One streaming pass over `cur` behind the steps enqueued so far: new velocities, and the binned state every ws_step
-// starts from (bin_current's pair: the counts zeroed, then the kernel that draws cell ids, counts and ranks).  srt, the
-// accept masks and accel[] are not touched -- the 80-byte view keeps the last step's density, pressure and
-// acceleration -- and no array moves, so a captured step is replayed as it is.
 ws_status ws_apply_forces(ws_handle *h, const ws_force *f, uint32_t k, float dt, uint32_t *out_affected)
 {
-    if (!h) return WS_ERR_INVALID_ARG;
-    WS_DEAD_CHECK(h);
-    if (h->flags & WS_FLAG_REFERENCE_ORDER) return fail(h, WS_ERR_UNSUPPORTED, "forces: not in the reference-order validation mode");
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (h->slab) return slab_apply_forces(h, f, k, dt, out_affected);  // collective: validated after the gather
-    if (const char *why = forces_refusal(f, k, dt)) return fail(h, WS_ERR_INVALID_ARG, why);
-    WsForceSet fs{};
-    memcpy(fs.e, f, (size_t)k * sizeof(ws_force));
-    if (out_affected) {
-        const ws_status st = forces_counters(h);
-        if (st) return st;
-    }
-    HIP_TRY(h, hipMemsetAsync(h->count, 0, (size_t)h->dev.ncells * 4, h->stream));
-    wsk_apply_forces(h->stream, h->dev, h->cur, h->cid_cur, h->count, fs, k, dt, out_affected ? h->force_cnt.p : nullptr);
-    HIP_TRY(h, hipGetLastError());
-    h->pred_stale = true;  // cur.pred is behind the new velocities: k_reorder<true> / refresh_pred recompute it
-    if (out_affected) HIP_TRY(h, copy_now(h, out_affected, h->force_cnt.p, (size_t)k * 4, hipMemcpyDeviceToHost));
-    return WS_OK;
+    ForcesCall call{f, k, dt, out_affected};
+    return edit_fluid(h, call);
 }
 
 // ======================================================================================
@@ -1333,7 +1377,6 @@ namespace {
 // the argument errors of ws_collide_solids (nullptr = acceptable); nothing is touched before this has passed
 const char *solids_refusal(const ws_solid *s, uint32_t k)
 {
-    const auto bad = [](float x) { return !isfinite(x) || fabsf(x) > 1e15f; };
     if (!s) return "solids: s is NULL";
     if (k < 1u || k > WS_MAX_SOLIDS) return "solids: k outside 1 .. WS_MAX_SOLIDS";
     for (uint32_t e = 0; e < k; e++) {
@@ -1342,11 +1385,11 @@ const char *solids_refusal(const ws_solid *s, uint32_t k)
         if (o.flags & ~WS_SOLID_HOLLOW) return "solids: unknown flag bits";
         if (o.reserved[0] || o.reserved[1]) return "solids: reserved words must be 0";
         for (int c = 0; c < 9; c++)
-            if (bad(o.rot[c])) return "solids: rot must be finite and at most 1e15 in magnitude";
+            if (ws_bad_float(o.rot[c])) return "solids: rot must be finite and at most 1e15 in magnitude";
         for (int c = 0; c < 3; c++)
-            if (bad(o.centre[c]) || bad(o.size[c]) || bad(o.velocity[c]) || bad(o.angular_velocity[c]))
+            if (ws_bad_float(o.centre[c]) || ws_bad_float(o.size[c]) || ws_bad_float(o.velocity[c]) || ws_bad_float(o.angular_velocity[c]))
                 return "solids: centre, size, velocity and angular_velocity must be finite and at most 1e15 in magnitude";
-        if (bad(o.restitution) || bad(o.friction) || bad(o.margin)) return "solids: restitution, friction and margin must be finite";
+        if (ws_bad_float(o.restitution) || ws_bad_float(o.friction) || ws_bad_float(o.margin)) return "solids: restitution, friction and margin must be finite";
         const int used = o.kind == WS_SOLID_BOX ? 3 : 1;
         for (int c = 0; c < used; c++)
             if (!(o.size[c] > 0.f)) return "solids: a radius or half extent must be > 0";
@@ -1407,70 +1450,59 @@ float solids_reach2(const ws_solid &o)
     return r2 < 3e38 ? (float)r2 * 1.000001f : INFINITY;
 }
 
-// the kernel's argument: the solids' bytes as given, and each one's reach
-WsSolidSet solids_set(const ws_solid *s, uint32_t k)
-{
-    WsSolidSet ss{};
-    memcpy(ss.e, s, (size_t)k * sizeof(ws_solid));
-    for (uint32_t e = 0; e < k; e++) ss.reach2[e] = solids_reach2(s[e]);
-    return ss;
-}
-
-// the accumulator words on the device, zeroed on the handle's stream
-ws_status solids_sums(ws_handle *h)
-{
-    const size_t bytes = (size_t)WS_MAX_SOLIDS * WS_SOLID_WORDS * 8;
-    const ws_status st = h->solid_sums.grow(h, bytes, "solid reaction sums");
-    if (st) return st;
-    HIP_TRY(h, hipMemsetAsync(h->solid_sums.p, 0, bytes, h->stream));
-    return WS_OK;
-}
-
-// the accumulator words as the caller's outputs: counts, and the fixed-point sums as (double)sum * 2^-24
-void solids_outputs(const unsigned long long *sums, uint32_t k, uint32_t *out_contacts, double *out_impulse, double *out_angular)
-{
-    for (uint32_t e = 0; e < k; e++) {
-        const unsigned long long *w = sums + (size_t)e * WS_SOLID_WORDS;
-        if (out_contacts) out_contacts[e] = (uint32_t)w[0];
-        for (int c = 0; c < 3; c++) {
-            if (out_impulse) out_impulse[3 * e + c] = (double)(long long)w[1 + c] * 0x1p-24;
-            if (out_angular) out_angular[3 * e + c] = (double)(long long)w[4 + c] * 0x1p-24;
+struct SolidsCall {
+    const ws_solid *s;
+    uint32_t k;
+    uint32_t *out_contacts;
+    double *out_impulse, *out_angular;
+    const char *tag = "solids", *things = "solids";
+    WsSolidArgs args{};
+    unsigned long long sums[WS_MAX_SOLIDS * WS_SOLID_WORDS];  // fetch()'s copy of the accumulator words
+    bool react() const { return out_contacts || out_impulse || out_angular; }
+    const char *refuse() const { return solids_refusal(s, k); }
+    ws_status prepare(ws_handle *h)  // the solids' bytes as given, and each one's reach
+    {
+        memcpy(args.ss.e, s, (size_t)k * sizeof(ws_solid));
+        for (uint32_t e = 0; e < k; e++) args.ss.reach2[e] = solids_reach2(s[e]);
+        args.k = k;
+        if (!react()) return WS_OK;
+        const ws_status st = scratch_zeroed(h, h->solid_sums, sizeof sums, "solid reaction sums");
+        args.sums = h->solid_sums.p;
+        return st;
+    }
+    template <class M>
+    void mix(M m, bool valid) const
+    {
+        m(&k, 4);
+        if (valid) m(s, (size_t)k * sizeof(ws_solid));
+    }
+    hipError_t fetch(ws_handle *h) { return react() ? copy_now(h, sums, h->solid_sums.p, sizeof sums, hipMemcpyDeviceToHost) : hipSuccess; }
+    // the accumulator words as the caller's outputs: counts, and the fixed-point sums as (double)sum * 2^-24.  Only after
+    // the whole call has succeeded -- on slab handles after the edit has been agreed on: a refused call writes nothing.
+    void outputs() const
+    {
+        for (uint32_t e = 0; react() && e < k; e++) {
+            const unsigned long long *w = sums + (size_t)e * WS_SOLID_WORDS;
+            if (out_contacts) out_contacts[e] = (uint32_t)w[0];
+            for (int c = 0; c < 3; c++) {
+                if (out_impulse) out_impulse[3 * e + c] = (double)(long long)w[1 + c] * 0x1p-24;
+                if (out_angular) out_angular[3 * e + c] = (double)(long long)w[4 + c] * 0x1p-24;
+            }
         }
     }
-}
+};
 
 }  // namespace
 
 extern "C" {
 
-// ws_apply_forces' pass with positions: one streaming kernel over `cur` behind the steps enqueued so far that edits both
-// record halves and leaves the binned state every ws_step starts from.  srt, the accept masks and accel[] are not touched
-// -- the 80-byte view keeps the last step's density, pressure and acceleration -- and no array moves, so a captured step
-// is replayed as it is.
 ws_status ws_collide_solids(ws_handle *h, const ws_solid *s, uint32_t k, uint32_t *out_contacts, double *out_impulse,
                             double *out_angular)
 {
-    if (!h) return WS_ERR_INVALID_ARG;
-    WS_DEAD_CHECK(h);
-    if (h->flags & WS_FLAG_REFERENCE_ORDER) return fail(h, WS_ERR_UNSUPPORTED, "solids: not in the reference-order validation mode");
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (h->slab) return slab_collide_solids(h, s, k, out_contacts, out_impulse, out_angular);  // collective: validated after the gather
-    if (const char *why = solids_refusal(s, k)) return fail(h, WS_ERR_INVALID_ARG, why);
-    const bool react = out_contacts || out_impulse || out_angular;
-    if (react) {
-        const ws_status st = solids_sums(h);
-        if (st) return st;
-    }
-    HIP_TRY(h, hipMemsetAsync(h->count, 0, (size_t)h->dev.ncells * 4, h->stream));
-    wsk_collide_solids(h->stream, h->dev, h->cur, h->cid_cur, h->count, solids_set(s, k), k, react ? h->solid_sums.p : nullptr);
-    HIP_TRY(h, hipGetLastError());
-    h->pred_stale = true;  // cur.pred is behind the new positions and velocities: k_reorder<true> / refresh_pred recompute it
-    if (react) {
-        unsigned long long sums[WS_MAX_SOLIDS * WS_SOLID_WORDS];
-        HIP_TRY(h, copy_now(h, sums, h->solid_sums.p, sizeof sums, hipMemcpyDeviceToHost));
-        solids_outputs(sums, k, out_contacts, out_impulse, out_angular);
-    }
-    return WS_OK;
+    SolidsCall call{s, k, out_contacts, out_impulse, out_angular};
+    const ws_status st = edit_fluid(h, call);
+    if (!st) call.outputs();
+    return st;
 }
 
 // ======================================================================================

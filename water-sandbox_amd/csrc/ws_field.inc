@@ -586,7 +586,7 @@ ws_status advect_check(ws_handle *h, const ws_advect_params *a, const float *xyz
     if (m > (1u << 28)) return fail(h, WS_ERR_INVALID_ARG, "advection: more than 2^28 points");
     if (!out_xyz) return fail(h, WS_ERR_INVALID_ARG, "advection: out_xyz is required");
     for (size_t t = 0; t < (size_t)m * 3; t++)
-        if (!isfinite(xyz[t]) || fabsf(xyz[t]) > 1e15f)
+        if (ws_bad_float(xyz[t]))
             return fail(h, WS_ERR_INVALID_ARG, "advection: points must be finite and within 1e15");
     return WS_OK;
 }
@@ -724,7 +724,7 @@ ws_status whitewater_step_check(ws_handle *h, const ws_whitewater_step_params *p
     if (!xyz || !vel || !life || m == 0u) return fail(h, WS_ERR_INVALID_ARG, "whitewater: no diffuse particles");
     if (m > (1u << 28)) return fail(h, WS_ERR_INVALID_ARG, "whitewater: more than 2^28 diffuse particles");
     for (size_t t = 0; t < (size_t)m * 3; t++)
-        if (!isfinite(xyz[t]) || fabsf(xyz[t]) > 1e15f || !isfinite(vel[t]) || fabsf(vel[t]) > 1e15f)
+        if (ws_bad_float(xyz[t]) || ws_bad_float(vel[t]))
             return fail(h, WS_ERR_INVALID_ARG, "whitewater: positions and velocities must be finite and within 1e15");
     for (size_t t = 0; t < m; t++)
         if (!isfinite(life[t])) return fail(h, WS_ERR_INVALID_ARG, "whitewater: lifetimes must be finite");
@@ -778,7 +778,7 @@ ws_status body_check(ws_handle *h, const ws_body_params *p, const float *xyz, co
         if (body_start[b] > body_start[b + 1]) return fail(h, WS_ERR_INVALID_ARG, "bodies: body_start must not decrease");
     auto in_range = [](const float *v, size_t k) {
         for (size_t t = 0; t < k; t++)
-            if (!isfinite(v[t]) || fabsf(v[t]) > 1e15f) return false;
+            if (ws_bad_float(v[t])) return false;
         return true;
     };
     if (!in_range(xyz, (size_t)m * 3) || !in_range(vel, (size_t)m * 3) || !in_range(vol, m) || !in_range(centre, (size_t)nb * 3))

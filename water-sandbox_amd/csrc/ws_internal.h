@@ -2,6 +2,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 
 #include <string>
@@ -176,6 +177,10 @@ struct WsEventPair {
     hipEvent_t a, b;
     bool counts = true;  // false: the second launch of a kernel id within one step (time is added, the launch count is per step)
 };
+
+// What every float of a caller's objects and query points is refused for: not finite, or so large that the kernels'
+// products and sums of a few of them could overflow.
+inline bool ws_bad_float(float x) { return !isfinite(x) || fabsf(x) > 1e15f; }
 
 // ---- who owns device memory ------------------------------------------------------------------------------------------
 // Every device allocation and every page-locked host allocation of a ws_handle / WsSlab has exactly ONE owner, of one of
@@ -535,30 +540,41 @@ void wsk_scatter(hipStream_t s, const uint32_t *keys, uint32_t *cursor, uint32_t
 void wsk_reorder(hipStream_t s, const WsDev &d, const uint32_t *slot_tmp, const uint32_t *cid_cur, const uint32_t *start, WsSoA cur,
                  WsSorted srt, uint32_t *cid_srt, WsXYZ sxyz, bool recompute_pred);
 void wsk_refresh_pred(hipStream_t s, const WsDev &d, WsSoA cur);
-// ws_apply_forces: the emitters as ONE by-value kernel argument (scalar loads, wave-uniform loop); affected = k device
-// words the kernel adds the per-emitter counts to, or nullptr.  The first form edits `cur` in place and re-bins it (what
-// bin_current leaves: cid, the record's cell id, count, rank); the second edits gathered {id, pos, vel, pred} records.
+// The between-step edits (ws_apply_forces, ws_collide_solids): what a call hands its kernel, ONE by-value kernel argument
+// whose objects the wave-uniform loop reads through scalar loads.  outputs(): whether the call wants the kernel's sums.
+// Forces: affected = k device words the kernel adds the per-emitter counts to, or nullptr.
+// Solids: each solid with its squared reach -- the squared distance from its centre beyond which no particle can be in
+// contact (solids_reach2 in ws_api.cpp; +inf = never skipped); sums = WS_MAX_SOLIDS x WS_SOLID_WORDS 64-bit device words
+// the kernel adds to ({contacts, 3 x impulse, 3 x angular impulse} in 2^-24 fixed point), or nullptr.
 struct WsForceSet {
     ws_force e[WS_MAX_FORCES];
 };
-void wsk_apply_forces(hipStream_t s, const WsDev &d, WsSoA cur, uint32_t *cid, uint32_t *count, const WsForceSet &fs, uint32_t k,
-                      float dt, uint32_t *affected);
-void wsk_apply_forces_records(hipStream_t s, uint32_t *all, const uint32_t *cnt, uint32_t world, uint32_t max_n,
-                              size_t stride_words, const WsForceSet &fs, uint32_t k, float dt, uint32_t *affected);
-// ws_collide_solids: the solids as ONE by-value kernel argument, each with its squared reach -- the squared distance from
-// its centre beyond which no particle can be in contact (solids_reach2 in ws_api.cpp; +inf = never skipped).  sums =
-// WS_MAX_SOLIDS x WS_SOLID_WORDS 64-bit device words the kernel adds to ({contacts, 3 x impulse, 3 x angular impulse} in
-// 2^-24 fixed point), or nullptr.  The first form edits `cur` in place and re-bins it, the second edits gathered
-// {id, pos, vel, pred} records (d: the container and its damping).
+struct WsForceArgs {
+    WsForceSet fs;
+    uint32_t k;
+    float dt;
+    uint32_t *affected;
+    bool outputs() const { return affected != nullptr; }
+};
 #define WS_SOLID_WORDS 7u
 struct WsSolidSet {
     ws_solid e[WS_MAX_SOLIDS];
     float reach2[WS_MAX_SOLIDS];
 };
-void wsk_collide_solids(hipStream_t s, const WsDev &d, WsSoA cur, uint32_t *cid, uint32_t *count, const WsSolidSet &ss, uint32_t k,
-                        unsigned long long *sums);
-void wsk_collide_solids_records(hipStream_t s, const WsDev &d, uint32_t *all, const uint32_t *cnt, uint32_t world, uint32_t max_n,
-                                size_t stride_words, const WsSolidSet &ss, uint32_t k, unsigned long long *sums);
+struct WsSolidArgs {
+    WsSolidSet ss;
+    uint32_t k;
+    unsigned long long *sums;
+    bool outputs() const { return sums != nullptr; }
+};
+// Args = WsForceArgs or WsSolidArgs.  The first edits `cur` in place and re-bins it (what bin_current leaves: cid, the
+// record's cell id, count, rank); the second edits the gathered {id, pos, vel, pred} records of slab handles (d: the global
+// grid, its container and damping).
+template <class Args>
+void wsk_edit_current(hipStream_t s, const WsDev &d, WsSoA cur, uint32_t *cid, uint32_t *count, const Args &a);
+template <class Args>
+void wsk_edit_records(hipStream_t s, const WsDev &d, uint32_t *all, const uint32_t *cnt, uint32_t world, uint32_t max_n,
+                      size_t stride_words, const Args &a);
 void wsk_density(hipStream_t s, const WsDev &d, const uint32_t *start, const uint32_t *cid_srt, WsSorted srt,
                  const uint8_t *mult, bool alias, int variant, bool ieee, uint32_t *stats, WsMask mask, WsXYZ sxyz,
                  const WsEventPair *ev = nullptr, WsSched sched = WsSched{});

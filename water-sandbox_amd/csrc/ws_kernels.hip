@@ -637,77 +637,6 @@ __device__ __forceinline__ bool forces_eval(const WsForceSet &fs, uint32_t k, fl
     return hit;
 }
 
-// Single-GPU handles: one lane per slot of `cur` in the order the last step left it (two 16-byte loads of consecutive
-// records), then what k_refresh_pred and k_bin would do in two more passes: the predicted position in registers, its
-// cell, cid[i] and the velocity record's w lane, the per-cell count and the particle's rank in it -- one atomic per run
-// of lanes that share a cell, as the force kernel's epilogue draws them.  The velocity record goes out as one 16-byte
-// store; cur.pred is not stored (k_reorder<true> and k_refresh_pred recompute it from the record).
-template <bool COUNTS>
-__global__ void __launch_bounds__(WS_BLOCK) k_apply_forces(WsDev d, WsSoA cur, uint32_t *__restrict__ cid,
-                                                           uint32_t *__restrict__ count, WsForceSet fs, uint32_t k, float dt,
-                                                           uint32_t *__restrict__ affected)
-{
-    const uint32_t i = blockIdx.x * WS_BLOCK + threadIdx.x;
-    const bool active = i < d.n;
-    float4 p = make_float4(0.f, 0.f, 0.f, 0.f), v = p;
-    if (active) {
-        p = cur.pos(i);
-        v = cur.vel(i);
-    }
-    forces_eval<COUNTS>(fs, k, dt, active, p, v, affected);
-    uint32_t c = 0;
-    if (active) {
-        c = grid_cell(d, p.x + v.x * WS_LOOKAHEAD, p.y + v.y * WS_LOOKAHEAD, p.z + v.z * WS_LOOKAHEAD);
-        cid[i] = c;
-        cur.vel(i) = make_float4(v.x, v.y, v.z, __uint_as_float(c));
-    }
-    const uint32_t r = wave_run_atomic_inc(count, c, active);
-    if (active && cur.rank) cur.rank[i] = r;
-}
-
-void wsk_apply_forces(hipStream_t s, const WsDev &d, WsSoA cur, uint32_t *cid, uint32_t *count, const WsForceSet &fs, uint32_t k,
-                      float dt, uint32_t *affected)
-{
-    if (!d.n) return;
-    const dim3 grid(cdiv(d.n, WS_BLOCK)), block(WS_BLOCK);
-    if (affected)
-        hipLaunchKernelGGL(k_apply_forces<true>, grid, block, 0, s, d, cur, cid, count, fs, k, dt, affected);
-    else
-        hipLaunchKernelGGL(k_apply_forces<false>, grid, block, 0, s, d, cur, cid, count, fs, k, dt, affected);
-}
-
-// Slab handles: the same definition on the gathered {id, pos, vel, pred} records of every rank (blockIdx.y = source rank,
-// the layout k_slab_select<2> reads), edited in place: velocity, and the predicted position by the library's own rule.
-template <bool COUNTS>
-__global__ void __launch_bounds__(WS_BLOCK) k_apply_forces_records(uint32_t *__restrict__ all, const uint32_t *__restrict__ cnt,
-                                                                   uint32_t max_n, size_t stride_words, WsForceSet fs, uint32_t k,
-                                                                   float dt, uint32_t *__restrict__ affected)
-{
-    const uint32_t t = blockIdx.x * WS_BLOCK + threadIdx.x, r = blockIdx.y;
-    const bool active = t < min(cnt[4 * r], max_n);
-    float *f = reinterpret_cast<float *>(all + (size_t)r * stride_words + (size_t)t * 10u + 1u);
-    float4 p = make_float4(0.f, 0.f, 0.f, 0.f), v = p;
-    if (active) {
-        p = make_float4(f[0], f[1], f[2], 0.f);
-        v = make_float4(f[3], f[4], f[5], 0.f);
-    }
-    forces_eval<COUNTS>(fs, k, dt, active, p, v, affected);
-    if (!active) return;
-    f[3] = v.x; f[4] = v.y; f[5] = v.z;
-    f[6] = p.x + v.x * WS_LOOKAHEAD; f[7] = p.y + v.y * WS_LOOKAHEAD; f[8] = p.z + v.z * WS_LOOKAHEAD;
-}
-
-void wsk_apply_forces_records(hipStream_t s, uint32_t *all, const uint32_t *cnt, uint32_t world, uint32_t max_n,
-                              size_t stride_words, const WsForceSet &fs, uint32_t k, float dt, uint32_t *affected)
-{
-    if (!max_n) return;
-    const dim3 grid(cdiv(max_n, WS_BLOCK), world), block(WS_BLOCK);
-    if (affected)
-        hipLaunchKernelGGL(k_apply_forces_records<true>, grid, block, 0, s, all, cnt, max_n, stride_words, fs, k, dt, affected);
-    else
-        hipLaunchKernelGGL(k_apply_forces_records<false>, grid, block, 0, s, all, cnt, max_n, stride_words, fs, k, dt, affected);
-}
-
 // ---------------------------------------------------------------------------------
 // ws_collide_solids: push the particles out of k solids, respond to the solids' motion, sum the reaction (never inside
 // ws_step)
@@ -859,19 +788,83 @@ __device__ __forceinline__ void solids_flush(const unsigned long long *acc, uint
     if (t < k * WS_SOLID_WORDS && acc[t - t % WS_SOLID_WORDS] != 0ull && acc[t] != 0ull) atomicAdd(&sums[t], acc[t]);
 }
 
-// Single-GPU handles: one lane per slot of `cur` (two 16-byte loads), then what k_apply_forces does after its edit: the
-// predicted position in registers, its cell, cid[i], the per-cell count and the rank -- and BOTH record halves go back as
-// 16-byte stores, {p, id} and {v, cell id}.  cur.pred is not stored (k_reorder<true> and k_refresh_pred recompute it).
+// ---------------------------------------------------------------------------------
+// the between-step edits (ws_apply_forces, ws_collide_solids, and whatever comes next): an edit is a TYPE, and two kernels
+// serve every edit -- k_edit_current on a single handle's `cur`, k_edit_records on the gathered records of slab handles
+//
+// An edit is a by-value kernel argument (its objects reach the wave-uniform loop through scalar loads) that declares
+//   moves      whether eval may change the position (else p comes back as it went in and is not stored);
+//   acc_words  the 64-bit LDS words a workgroup accumulates in, at most WS_BLOCK (0: none, and no barrier is taken);
+//   eval(d, active, p, v, acc)  the definition on one particle; true if it changed p or v.  EVERY lane of the workgroup
+//              calls it (it may ballot and shuffle), inactive lanes with active == false and zeros; d is the handle's
+//              grid, on slab handles the global one; acc is zeroed, and other waves add to it;
+//   flush(acc) the workgroup's words on their way to memory, called by every thread after a barrier.
+// Around it the kernels guarantee: the record read once and written once; an unchanged particle keeps its bits; the
+// predicted position is the library's own p + v * WS_LOOKAHEAD, never the edit's; and `cur` is left binned -- cid, the
+// record's cell id, the per-cell count and the rank, what bin_current leaves -- so that any number of edits may follow
+// one another between two steps.
+// ---------------------------------------------------------------------------------
+template <bool COUNTS>
+struct EditForces {
+    static constexpr bool moves = false;
+    static constexpr uint32_t acc_words = 0;
+    WsForceArgs a;
+    __device__ bool eval(const WsDev &, bool active, float4 &p, float4 &v, unsigned long long *) const
+    {
+        return forces_eval<COUNTS>(a.fs, a.k, a.dt, active, p, v, a.affected);
+    }
+    __device__ void flush(const unsigned long long *) const {}
+};
+
 template <bool REACT>
-__global__ void __launch_bounds__(WS_BLOCK) k_collide_solids(WsDev d, WsSoA cur, uint32_t *__restrict__ cid,
-                                                             uint32_t *__restrict__ count, WsSolidSet ss, uint32_t k,
-                                                             unsigned long long *__restrict__ sums)
+struct EditSolids {
+    static constexpr bool moves = true;
+    static constexpr uint32_t acc_words = REACT ? WS_MAX_SOLIDS * WS_SOLID_WORDS : 0u;
+    WsSolidArgs a;
+    __device__ bool eval(const WsDev &d, bool active, float4 &p, float4 &v, unsigned long long *acc) const
+    {
+        return solids_eval<REACT>(d, a.ss, a.k, active, p, v, acc);
+    }
+    __device__ void flush(const unsigned long long *acc) const { solids_flush(acc, a.k, a.sums); }
+};
+
+// what a launcher's argument struct becomes on the device: WITH = whether the call wants its outputs (COUNTS / REACT)
+template <class With>
+EditForces<With::value> edit_of(const WsForceArgs &a, With) { return {a}; }
+template <class With>
+EditSolids<With::value> edit_of(const WsSolidArgs &a, With) { return {a}; }
+
+template <class Edit>
+__device__ __forceinline__ void edit_begin(unsigned long long *acc)
 {
-    __shared__ unsigned long long acc[REACT ? WS_MAX_SOLIDS * WS_SOLID_WORDS : 1];
-    if constexpr (REACT) {
-        if (threadIdx.x < WS_MAX_SOLIDS * WS_SOLID_WORDS) acc[threadIdx.x] = 0ull;
+    static_assert(Edit::acc_words <= (uint32_t)WS_BLOCK, "one thread zeroes and flushes one accumulator word");
+    if constexpr (Edit::acc_words != 0u) {
+        if (threadIdx.x < Edit::acc_words) acc[threadIdx.x] = 0ull;
         __syncthreads();
     }
+}
+
+template <class Edit>
+__device__ __forceinline__ void edit_end(const Edit &edit, const unsigned long long *acc)
+{
+    if constexpr (Edit::acc_words != 0u) {
+        __syncthreads();
+        edit.flush(acc);
+    }
+}
+
+// Single-GPU handles: one lane per slot of `cur` in the order the last step left it (two 16-byte loads of consecutive
+// records), then what k_refresh_pred and k_bin would do in two more passes: the predicted position in registers, its
+// cell, cid[i] and the velocity record's w lane, the per-cell count and the particle's rank in it -- one atomic per run
+// of lanes that share a cell, as the force kernel's epilogue draws them.  The record halves go out as 16-byte stores,
+// {v, cell id} always and {p, id} for an edit that moves; cur.pred is not stored (k_reorder<true> and k_refresh_pred
+// recompute it from the record).
+template <class Edit>
+__global__ void __launch_bounds__(WS_BLOCK) k_edit_current(WsDev d, WsSoA cur, uint32_t *__restrict__ cid,
+                                                           uint32_t *__restrict__ count, Edit edit)
+{
+    __shared__ unsigned long long acc[Edit::acc_words ? Edit::acc_words : 1u];
+    edit_begin<Edit>(acc);
     const uint32_t i = blockIdx.x * WS_BLOCK + threadIdx.x;
     const bool active = i < d.n;
     float4 p = make_float4(0.f, 0.f, 0.f, 0.f), v = p;
@@ -879,78 +872,92 @@ __global__ void __launch_bounds__(WS_BLOCK) k_collide_solids(WsDev d, WsSoA cur,
         p = cur.pos(i);
         v = cur.vel(i);
     }
-    solids_eval<REACT>(d, ss, k, active, p, v, acc);
+    edit.eval(d, active, p, v, acc);
     uint32_t c = 0;
     if (active) {
         c = grid_cell(d, p.x + v.x * WS_LOOKAHEAD, p.y + v.y * WS_LOOKAHEAD, p.z + v.z * WS_LOOKAHEAD);
         cid[i] = c;
-        cur.pos(i) = p;
+        if constexpr (Edit::moves) cur.pos(i) = p;
         cur.vel(i) = make_float4(v.x, v.y, v.z, __uint_as_float(c));
     }
     const uint32_t r = wave_run_atomic_inc(count, c, active);
     if (active && cur.rank) cur.rank[i] = r;
-    if constexpr (REACT) {
-        __syncthreads();
-        solids_flush(acc, k, sums);
-    }
+    edit_end(edit, acc);
 }
 
-void wsk_collide_solids(hipStream_t s, const WsDev &d, WsSoA cur, uint32_t *cid, uint32_t *count, const WsSolidSet &ss, uint32_t k,
-                        unsigned long long *sums)
+// The gathered state of slab handles (WS_PACK_STATE_H, what k_slab_select<2> reads): per source rank r, stride_words
+// apart, min(cnt[4 r], max_n) records of 10 words: {id, pos[3], vel[3], pred[3]}.  The nine floats of record t of rank r:
+__device__ __forceinline__ float *state_record(uint32_t *all, size_t stride_words, uint32_t r, uint32_t t)
 {
-    if (!d.n) return;
-    const dim3 grid(cdiv(d.n, WS_BLOCK)), block(WS_BLOCK);
-    if (sums)
-        hipLaunchKernelGGL(k_collide_solids<true>, grid, block, 0, s, d, cur, cid, count, ss, k, sums);
-    else
-        hipLaunchKernelGGL(k_collide_solids<false>, grid, block, 0, s, d, cur, cid, count, ss, k, sums);
+    return reinterpret_cast<float *>(all + (size_t)r * stride_words + (size_t)t * 10u + 1u);
 }
 
-// Slab handles: the same definition on the gathered {id, pos, vel, pred} records of every rank (k_apply_forces_records'
-// layout), edited in place: position, velocity, and the predicted position by the library's own rule.  d: the GLOBAL
-// container and damping (the container rule).
-template <bool REACT>
-__global__ void __launch_bounds__(WS_BLOCK) k_collide_solids_records(WsDev d, uint32_t *__restrict__ all, const uint32_t *__restrict__ cnt,
-                                                                     uint32_t max_n, size_t stride_words, WsSolidSet ss, uint32_t k,
-                                                                     unsigned long long *__restrict__ sums)
+// Slab handles: the same definition on the gathered records of every rank (blockIdx.y = source rank), edited in place:
+// velocity, position for an edit that moves, and the predicted position by the library's own rule.  d: the GLOBAL grid.
+template <class Edit>
+__global__ void __launch_bounds__(WS_BLOCK) k_edit_records(WsDev d, uint32_t *__restrict__ all, const uint32_t *__restrict__ cnt,
+                                                           uint32_t max_n, size_t stride_words, Edit edit)
 {
-    __shared__ unsigned long long acc[REACT ? WS_MAX_SOLIDS * WS_SOLID_WORDS : 1];
-    if constexpr (REACT) {
-        if (threadIdx.x < WS_MAX_SOLIDS * WS_SOLID_WORDS) acc[threadIdx.x] = 0ull;
-        __syncthreads();
-    }
+    __shared__ unsigned long long acc[Edit::acc_words ? Edit::acc_words : 1u];
+    edit_begin<Edit>(acc);
     const uint32_t t = blockIdx.x * WS_BLOCK + threadIdx.x, r = blockIdx.y;
     const bool active = t < min(cnt[4 * r], max_n);
-    float *f = reinterpret_cast<float *>(all + (size_t)r * stride_words + (size_t)t * 10u + 1u);
+    float *f = state_record(all, stride_words, r, t);
     float4 p = make_float4(0.f, 0.f, 0.f, 0.f), v = p;
     if (active) {
         p = make_float4(f[0], f[1], f[2], 0.f);
         v = make_float4(f[3], f[4], f[5], 0.f);
     }
-    const bool touched = solids_eval<REACT>(d, ss, k, active, p, v, acc);
+    const bool changed = edit.eval(d, active, p, v, acc);
     if (active) {
-        if (touched) {
-            f[0] = p.x; f[1] = p.y; f[2] = p.z;
+        if (changed) {
+            if constexpr (Edit::moves) { f[0] = p.x; f[1] = p.y; f[2] = p.z; }
             f[3] = v.x; f[4] = v.y; f[5] = v.z;
         }
         f[6] = p.x + v.x * WS_LOOKAHEAD; f[7] = p.y + v.y * WS_LOOKAHEAD; f[8] = p.z + v.z * WS_LOOKAHEAD;
     }
-    if constexpr (REACT) {
-        __syncthreads();
-        solids_flush(acc, k, sums);
-    }
+    edit_end(edit, acc);
 }
 
-void wsk_collide_solids_records(hipStream_t s, const WsDev &d, uint32_t *all, const uint32_t *cnt, uint32_t world, uint32_t max_n,
-                                size_t stride_words, const WsSolidSet &ss, uint32_t k, unsigned long long *sums)
+// Run-time bools as template bools: f is called once, with a std::true_type or std::false_type for every bool given.
+template <class F>
+void ws_dispatch(F &&f)
+{
+    f();
+}
+template <class F, class... Bools>
+void ws_dispatch(F &&f, bool first, Bools... rest)
+{
+    if (first) ws_dispatch([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else ws_dispatch([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+
+
+template <class Args>
+void wsk_edit_current(hipStream_t s, const WsDev &d, WsSoA cur, uint32_t *cid, uint32_t *count, const Args &a)
+{
+    if (!d.n) return;
+    ws_dispatch([&](auto with) {
+        using Edit = decltype(edit_of(a, with));
+        hipLaunchKernelGGL(k_edit_current<Edit>, dim3(cdiv(d.n, WS_BLOCK)), dim3(WS_BLOCK), 0, s, d, cur, cid, count, edit_of(a, with));
+    }, a.outputs());
+}
+template void wsk_edit_current(hipStream_t, const WsDev &, WsSoA, uint32_t *, uint32_t *, const WsForceArgs &);
+template void wsk_edit_current(hipStream_t, const WsDev &, WsSoA, uint32_t *, uint32_t *, const WsSolidArgs &);
+
+template <class Args>
+void wsk_edit_records(hipStream_t s, const WsDev &d, uint32_t *all, const uint32_t *cnt, uint32_t world, uint32_t max_n,
+                      size_t stride_words, const Args &a)
 {
     if (!max_n) return;
-    const dim3 grid(cdiv(max_n, WS_BLOCK), world), block(WS_BLOCK);
-    if (sums)
-        hipLaunchKernelGGL(k_collide_solids_records<true>, grid, block, 0, s, d, all, cnt, max_n, stride_words, ss, k, sums);
-    else
-        hipLaunchKernelGGL(k_collide_solids_records<false>, grid, block, 0, s, d, all, cnt, max_n, stride_words, ss, k, sums);
+    ws_dispatch([&](auto with) {
+        using Edit = decltype(edit_of(a, with));
+        hipLaunchKernelGGL(k_edit_records<Edit>, dim3(cdiv(max_n, WS_BLOCK), world), dim3(WS_BLOCK), 0, s, d, all, cnt, max_n, stride_words,
+                           edit_of(a, with));
+    }, a.outputs());
 }
+template void wsk_edit_records(hipStream_t, const WsDev &, uint32_t *, const uint32_t *, uint32_t, uint32_t, size_t, const WsForceArgs &);
+template void wsk_edit_records(hipStream_t, const WsDev &, uint32_t *, const uint32_t *, uint32_t, uint32_t, size_t, const WsSolidArgs &);
 
 // ---------------------------------------------------------------------------------
 // smoothing kernels, assets/simulation.wgsl:93-117 (evaluation order as written)
@@ -3478,19 +3485,6 @@ __global__ void __launch_bounds__(64) k_field_bricks(WsDev d, const uint32_t *__
         }
     }
     if (valid) store.template put<GRAD>(a, at);
-}
-
-// Run-time bools as template bools: f is called once, with a std::true_type or std::false_type for every bool given.
-template <class F>
-void ws_dispatch(F &&f)
-{
-    f();
-}
-template <class F, class... Bools>
-void ws_dispatch(F &&f, bool first, Bools... rest)
-{
-    if (first) ws_dispatch([&](auto... c) { f(std::true_type{}, c...); }, rest...);
-    else ws_dispatch([&](auto... c) { f(std::false_type{}, c...); }, rest...);
 }
 
 // Whether the brick kernel can stage a source: the source declares its chunk.

@@ -1104,12 +1104,11 @@ ws_status slab_regrid(ws_handle *h, const ws_params *params, bool rebalance)
 // epilogue has already packed; the form that moves only the particles in reach is the scale-out follow-up: DESIGN.md 9.6.)
 // The call mutates state, so its verdict is made common before anything is touched: bit 0 of the agreed word = this rank
 // refuses, the rest = a hash of the arguments' bytes.
-// tag / things name the call and its objects in ws_last_error.  refuse() = the argument error or nullptr; prepare() = this
-// rank's output scratch, zeroed on the stream; mix(m) hashes the arguments with m(pointer, bytes) -- the objects' bytes
-// only if `valid`; edit(recs, max_n, stride) launches the kernel on the gathered records; fetch() copies the outputs.
-template <class Refuse, class Prepare, class Mix, class Edit, class Fetch>
-ws_status slab_edit_gathered(ws_handle *h, const char *tag, const char *things, Refuse refuse, Prepare prepare, Mix mix, Edit edit, Fetch fetch)
+// call: the description ws_api.cpp's edit_fluid documents (tag, things, refuse, prepare, mix, args, fetch).
+template <class Call>
+ws_status slab_edit_gathered(ws_handle *h, Call &call)
 {
+    const char *const tag = call.tag;
     WsSlab *S = h->slab;
     const uint32_t W = S->world;
     const std::string pre = std::string(tag) + ": ";
@@ -1118,10 +1117,10 @@ ws_status slab_edit_gathered(ws_handle *h, const char *tag, const char *things, 
     ws_status st = slab_gather(h, WS_PACK_STATE_H, &stride, &max_n);  // (also brings every rank's capacity: S->caps)
     if (st) return st;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    const char *why = refuse();
-    const ws_status st_cnt = !why ? prepare() : WS_OK;  // (this rank's alone: it refuses for all)
+    const char *why = call.refuse();
+    const ws_status st_cnt = !why ? call.prepare(h) : WS_OK;  // (this rank's alone: it refuses for all)
     uint32_t word = 2166136261u;  // FNV-1a
-    mix([&word](const void *p, size_t bytes) {
+    call.mix([&word](const void *p, size_t bytes) {
         for (size_t b = 0; b < bytes; b++) word = (word ^ static_cast<const uint8_t *>(p)[b]) * 16777619u;
     }, !why);
     word = (word << 1) | ((why || st_cnt) ? 1u : 0u);
@@ -1138,7 +1137,7 @@ ws_status slab_edit_gathered(ws_handle *h, const char *tag, const char *things, 
     if (why) return fail(h, WS_ERR_INVALID_ARG, why);
     if (st_cnt) return st_cnt;
     if (anybody) return fail(h, WS_ERR_INVALID_ARG, (pre + "another slab refused its arguments; nothing was changed").c_str());
-    if (differ) return fail(h, WS_ERR_INVALID_ARG, (pre + "the slabs were given different " + things + "; nothing was changed").c_str());
+    if (differ) return fail(h, WS_ERR_INVALID_ARG, (pre + "the slabs were given different " + call.things + "; nothing was changed").c_str());
     uint32_t *recs = const_cast<uint32_t *>(slab_gathered(S));  // (scratch of the gather: nothing the step reads)
     // the edit, and the x-layer histogram of the edited set: every slab's owned count under the cuts against every slab's
     // capacity, all alike, before the old state is given up (slab_regrid).  A failure in here is this rank's alone and is
@@ -1146,11 +1145,11 @@ ws_status slab_edit_gathered(ws_handle *h, const char *tag, const char *things, 
     const uint32_t nx = (uint32_t)h->dev.gdim_x;
     std::vector<uint32_t> hist(nx);
     {
-        edit(recs, max_n, stride);
+        wsk_edit_records(h->stream, h->dev, recs, S->cnt_all.p, W, max_n, stride, call.args);
         ws_status mine = slab_layer_hist(h, h->dev, recs, max_n, stride, &hist);
         if (!mine) {
             hipError_t e = hipGetLastError();
-            if (e == hipSuccess) e = fetch();
+            if (e == hipSuccess) e = call.fetch(h);
             if (e != hipSuccess) {
                 (void)hipGetLastError();
                 mine = fail(h, e == hipErrorOutOfMemory ? WS_ERR_OUT_OF_MEMORY : WS_ERR_HIP, "edit of the gathered state", e);
@@ -1190,46 +1189,6 @@ ws_status slab_edit_gathered(ws_handle *h, const char *tag, const char *things, 
         return st ? st : (st_agree ? st_agree : WS_ERR_OUT_OF_MEMORY);
     }
     return WS_OK;
-}
-
-ws_status slab_apply_forces(ws_handle *h, const ws_force *f, uint32_t k, float dt, uint32_t *out_affected)
-{
-    WsSlab *S = h->slab;
-    return slab_edit_gathered(
-        h, "forces", "emitters", [&] { return forces_refusal(f, k, dt); }, [&] { return out_affected ? forces_counters(h) : WS_OK; },
-        [&](auto m, bool valid) {
-            m(&k, 4);
-            m(&dt, 4);
-            if (valid) m(f, (size_t)k * sizeof(ws_force));
-        },
-        [&](uint32_t *recs, uint32_t max_n, size_t stride) {
-            WsForceSet fs{};
-            memcpy(fs.e, f, (size_t)k * sizeof(ws_force));
-            wsk_apply_forces_records(h->stream, recs, S->cnt_all.p, S->world, max_n, stride, fs, k, dt, out_affected ? h->force_cnt.p : nullptr);
-        },
-        [&] { return out_affected ? copy_now(h, out_affected, h->force_cnt.p, (size_t)k * 4, hipMemcpyDeviceToHost) : hipSuccess; });
-}
-
-// (the outputs reach the caller only after the edit has been agreed on: a refused call writes nothing)
-ws_status slab_collide_solids(ws_handle *h, const ws_solid *s, uint32_t k, uint32_t *out_contacts, double *out_impulse,
-                              double *out_angular)
-{
-    WsSlab *S = h->slab;
-    const bool react = out_contacts || out_impulse || out_angular;
-    unsigned long long sums[WS_MAX_SOLIDS * WS_SOLID_WORDS];
-    const ws_status st = slab_edit_gathered(
-        h, "solids", "solids", [&] { return solids_refusal(s, k); }, [&] { return react ? solids_sums(h) : WS_OK; },
-        [&](auto m, bool valid) {
-            m(&k, 4);
-            if (valid) m(s, (size_t)k * sizeof(ws_solid));
-        },
-        [&](uint32_t *recs, uint32_t max_n, size_t stride) {
-            wsk_collide_solids_records(h->stream, h->dev, recs, S->cnt_all.p, S->world, max_n, stride, solids_set(s, k), k,
-                                       react ? h->solid_sums.p : nullptr);
-        },
-        [&] { return react ? copy_now(h, sums, h->solid_sums.p, sizeof sums, hipMemcpyDeviceToHost) : hipSuccess; });
-    if (!st && react) solids_outputs(sums, k, out_contacts, out_impulse, out_angular);
-    return st;
 }
 
 // ws_sample_density_* on a slab handle (COLLECTIVE): every rank's current positions all-gathered by id into S->g_out
