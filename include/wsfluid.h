@@ -879,6 +879,77 @@ typedef struct ws_solid {      /* 112 bytes */
 ws_status ws_collide_solids(ws_handle *h, const ws_solid *s, uint32_t k, uint32_t *out_contacts, double *out_impulse,
                             double *out_angular);
 
+/* ---- solids given as signed-distance volumes: terrain, a hull, a bowl, whatever a mesh tool can voxelise (DESIGN.md 9.9;
+ *      no reference counterpart) ----------------------------------------------------------------------------------------
+ * A VOLUME is a regular grid of signed distances in the solid's local coordinates, negative inside the solid, that the host
+ * uploads once per shape into one of WS_MAX_VOLUMES slots of the handle.  ws_collide_volumes then is ws_collide_solids
+ * with the analytic shapes replaced by k POSES (instances) of resident volumes -- several poses may use one slot: the
+ * distance is the trilinear interpolant of the grid and the normal is that interpolant's own gradient.
+ *
+ * ws_volume_upload: node (i, j, k) lies at the local coordinates origin_a + (i, j, k)_a * spacing_a and holds
+ * sdf[(k * dims[1] + j) * dims[0] + i] -- x fastest, like ws_sample_density_grid.  The call first waits for the work enqueued
+ * so far (an enqueued edit may still be reading the old array), copies the array to the device and replaces whatever the
+ * slot held; sdf == NULL releases the slot, and the other arguments are then ignored.  On slab handles the call is LOCAL:
+ * no communication; every rank uploads its own copy.  A volume survives ws_reset, ws_write_particles, ws_set_params (a
+ * re-grid included) and ws_slab_rebalance; ws_destroy frees it.  A refused upload leaves the slot as it was.
+ * Errors: WS_ERR_INVALID_ARG (NULL handle; slot >= WS_MAX_VOLUMES; with a non-NULL sdf: NULL origin, spacing or dims; a dims
+ * entry outside 2 .. 1024; more than 2^26 nodes; a spacing that is not finite and > 0; an origin that is not finite; any
+ * origin, spacing or extent (dims_a - 1) * spacing_a above 1e15 in magnitude; any sdf value that is not finite or above 1e15
+ * in magnitude); WS_ERR_OUT_OF_MEMORY if the allocation fails (the handle stays usable and the slot is EMPTY);
+ * WS_ERR_UNSUPPORTED (WS_FLAG_REFERENCE_ORDER handles); WS_ERR_HIP on an unusable handle.
+ *
+ * ws_collide_volumes: fl(), dot, the cross product and x * y + z as the solids block defines them; arithmetic is IEEE
+ * whatever the handle's flags: every operation is rounded once, sqrt and division are correctly rounded, nothing is
+ * contracted.  Per particle, with a RUNNING (p, v), for the poses e = 0 .. k-1 in the order given, with c = centre, R_i =
+ * rot[3i .. 3i+2], V = velocity, W = angular_velocity and origin, spacing, dims, sdf those of the pose's slot:
+ *   1. q_a = p_a - c_a; l_i = dot(R_i, q).
+ *   2. grid coordinate g_a = (l_a - origin_a) / spacing_a.  The particle is IN THE DOMAIN iff 0 <= g_a <= (float)(dims_a - 1)
+ *      on all three axes.  Outside the domain the volume says nothing: on to the next pose (a host pads its volume with
+ *      positive distances).  Inside: cell i_a = min((uint32_t)g_a, dims_a - 2); fraction f_a = g_a - (float)i_a (exact; f_a
+ *      == 1 occurs only on the far face); the corners c_xyz = sdf at node (i_0 + x, i_1 + y, i_2 + z), x, y, z in {0, 1}.
+ *      Interpolate along x, then y, then z, keeping the differences:
+ *        d_yz = c_1yz - c_0yz,  cx_yz = c_0yz + f_0 * d_yz     (four each);
+ *        e_z  = cx_1z - cx_0z,  cy_z  = cx_0z + f_1 * e_z      (two each);
+ *        hh   = cy_1 - cy_0,    s     = cy_0 + f_2 * hh.
+ *      The gradient of that same interpolant, in local coordinates:
+ *        dz_z = d_0z + f_1 * (d_1z - d_0z);
+ *        G_0 = (dz_0 + f_2 * (dz_1 - dz_0)) / spacing_0;  G_1 = (e_0 + f_2 * (e_1 - e_0)) / spacing_1;  G_2 = hh / spacing_2.
+ *      gg = dot(G, G); m_a = G_a / sqrt(gg) if gg > 0, else m = (0, 1, 0): local up, the sphere's centre rule.
+ *      n_a = (m_0 * R_0,a + m_1 * R_1,a) + m_2 * R_2,a.
+ *   3. to 6. are ws_collide_solids' steps 3 to 6 unchanged: a contact exists iff s < margin; the push-out p_a = p_a +
+ *      (margin - s) * n_a; the response against V + W x r with restitution and friction; the 2^24 fixed-point 64-bit
+ *      reaction sums about `centre`, per POSE.
+ * After the loop, as there: the container rule for TOUCHED particles; an untouched particle keeps its bits; the predicted
+ * position of EVERY particle is recomputed and the state is binned again.  Outputs (k counts, k x 3 impulses, k x 3 angular
+ * impulses, each optional), waiting behaviour, WS_FLAG_GRAPH handles, the ws_read_positions_begin / _end window and
+ * ws_steps_done: all as ws_collide_solids.
+ * Slab handles: COLLECTIVE, by ws_collide_solids' route, the same bits as a single handle.  The verdict is common: if any
+ * rank refuses its arguments, or the ranks' poses differ, or the volumes in the slots the poses use differ between ranks
+ * (dims, origin, spacing or any byte of the array -- compared by a 64-bit hash taken at upload), ALL return
+ * WS_ERR_INVALID_ARG and nothing is changed.
+ * Errors: WS_ERR_INVALID_ARG (NULL handle or v; k outside 1 .. WS_MAX_VOLUME_POSES; slot >= WS_MAX_VOLUMES or an EMPTY slot;
+ * non-zero flags or reserved; any non-finite value or magnitude above 1e15; restitution or friction outside [0, 1]; margin
+ * < 0): nothing is touched and the handle steps on.  `rot` is the host's, as a solid's is.  WS_ERR_UNSUPPORTED
+ * (WS_FLAG_REFERENCE_ORDER handles); WS_ERR_HIP on an unusable handle. */
+#define WS_MAX_VOLUMES      4u    /* resident volumes (slots) per handle */
+#define WS_MAX_VOLUME_POSES 16u   /* instances per call; several may use one slot */
+typedef struct ws_volume_pose {   /* 96 bytes */
+    uint32_t slot;                /* offset 0: < WS_MAX_VOLUMES, holding a volume */
+    uint32_t flags;               /* offset 4: must be 0 */
+    float centre[3];              /* offset 8: world position of the volume's local (0, 0, 0); the centre of rotation */
+    float rot[9];                 /* offset 20: rows R_0 R_1 R_2 = the local axes in world coordinates, used as given */
+    float velocity[3];            /* offset 56: of the solid */
+    float angular_velocity[3];    /* offset 68: of the solid, about `centre` (radians per unit of time) */
+    float restitution;            /* offset 80: in [0, 1] */
+    float friction;               /* offset 84: in [0, 1] */
+    float margin;                 /* offset 88: >= 0 */
+    uint32_t reserved;            /* offset 92: must be 0 */
+} ws_volume_pose;
+ws_status ws_volume_upload(ws_handle *h, uint32_t slot, const float origin[3], const float spacing[3],
+                           const uint32_t dims[3], const float *sdf);
+ws_status ws_collide_volumes(ws_handle *h, const ws_volume_pose *v, uint32_t k, uint32_t *out_contacts,
+                             double *out_impulse, double *out_angular);
+
 /* ---- the fluid acting on things that float in it: buoyancy and drag on host-owned bodies (no reference
  *      counterpart) ----------------------------------------------------------------------------------------------------
  * One-way coupling, water to body.  The HOST owns the bodies, as it owns whitewater's diffuse particles: it describes each

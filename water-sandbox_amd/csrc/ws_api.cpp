@@ -697,6 +697,7 @@ void free_all(ws_handle *h)
     free_particle_arrays(h);
     release_all(h->fixed, h->stage_mem, h->force_cnt, h->solid_sums, h->v_keys, h->v_perm, h->v_tmp, h->v_count, h->v_cursor, h->v_start, h->v_bsum,
                 h->v_off);
+    for (auto &volume : h->volume) release_all(volume);
     free_field(h);
 #ifdef WS_WITH_REFCHECK
     ref_free(h);
@@ -1274,8 +1275,8 @@ ws_status ws_write_particles(ws_handle *h, const ws_particle80 *in)
 
 namespace {
 
-// ws_apply_forces and ws_collide_solids are one route around two descriptions.  A description (ForcesCall, SolidsCall)
-// carries
+// ws_apply_forces, ws_collide_solids and ws_collide_volumes are one route around three descriptions.  A description
+// (ForcesCall, SolidsCall, VolumesCall) carries
 //   tag, things     the call and its objects in ws_last_error;
 //   refuse()        the argument error, or nullptr; nothing is touched before it has passed;
 //   prepare(h)      after that: `args`, the kernel's argument, built once, and the output scratch it points to, grown
@@ -1400,6 +1401,41 @@ const char *solids_refusal(const ws_solid *s, uint32_t k)
     return nullptr;
 }
 
+// A lower bound of sigma_min(R)^2 that is safe to divide by, or a value that is not > 0 where R is too near singular for
+// one.  sigma_min(R)^2 = the smallest eigenvalue of the symmetric G = R R^T, from the characteristic cubic's trigonometric
+// solution (G is 3 x 3 positive semi-definite).
+double rot_sigma_min2(const float *rot)
+{
+    double G[3][3];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++)
+            G[i][j] = (double)rot[3 * i] * rot[3 * j] + (double)rot[3 * i + 1] * rot[3 * j + 1] + (double)rot[3 * i + 2] * rot[3 * j + 2];
+    const double tr = G[0][0] + G[1][1] + G[2][2], mean = tr / 3.0;
+    const double off = G[0][1] * G[0][1] + G[0][2] * G[0][2] + G[1][2] * G[1][2];
+    double dev = 2.0 * off;
+    for (int i = 0; i < 3; i++) dev += (G[i][i] - mean) * (G[i][i] - mean);
+    const double pp = sqrt(dev / 6.0);
+    double lam_min = mean;  // (a multiple of the identity)
+    if (pp > 0.0) {
+        double B[3][3];
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) B[i][j] = (G[i][j] - (i == j ? mean : 0.0)) / pp;
+        const double det = B[0][0] * (B[1][1] * B[2][2] - B[1][2] * B[2][1]) - B[0][1] * (B[1][0] * B[2][2] - B[1][2] * B[2][0]) +
+                           B[0][2] * (B[1][0] * B[2][1] - B[1][1] * B[2][0]);
+        const double phi = acos(std::min(1.0, std::max(-1.0, det / 2.0))) / 3.0;
+        lam_min = mean + 2.0 * pp * cos(phi + 2.0 * 3.14159265358979323846 / 3.0);
+    }
+    // (the eigenvalue carries an absolute error of a few 1e-16 tr: taken off, with the kernel's roundings, as 1e-3 tr)
+    return lam_min - 1e-3 * tr;
+}
+
+// a reach as the squared float the kernels compare |q|^2 with: (reach + 0.1 %)^2, rounded up; +inf where it has no float
+float reach2_of(double reach)
+{
+    const double r2 = reach * reach * 1.002001;
+    return r2 < 3e38 ? (float)r2 * 1.000001f : INFINITY;
+}
+
 // The squared distance from a solid's centre beyond which no particle can be in contact with it, whatever `rot` holds:
 // what lets a wave skip the solid without changing a bit.  A contact needs s < margin, and
 //   SPHERE:  s = fl(d - r) < margin                                   =>  d <= r + margin (up to roundings);
@@ -1419,35 +1455,12 @@ float solids_reach2(const ws_solid &o)
     } else if (o.kind == WS_SOLID_CAPSULE) {
         reach = o.size[0] + m + (double)o.size[1] * sqrt((double)o.rot[3] * o.rot[3] + (double)o.rot[4] * o.rot[4] + (double)o.rot[5] * o.rot[5]);
     } else {
-        // sigma_min(R)^2 = the smallest eigenvalue of the symmetric G = R R^T, from the characteristic cubic's trigonometric
-        // solution (G is 3 x 3 positive semi-definite)
-        double G[3][3];
-        for (int i = 0; i < 3; i++)
-            for (int j = 0; j < 3; j++)
-                G[i][j] = (double)o.rot[3 * i] * o.rot[3 * j] + (double)o.rot[3 * i + 1] * o.rot[3 * j + 1] + (double)o.rot[3 * i + 2] * o.rot[3 * j + 2];
-        const double tr = G[0][0] + G[1][1] + G[2][2], mean = tr / 3.0;
-        const double off = G[0][1] * G[0][1] + G[0][2] * G[0][2] + G[1][2] * G[1][2];
-        double dev = 2.0 * off;
-        for (int i = 0; i < 3; i++) dev += (G[i][i] - mean) * (G[i][i] - mean);
-        const double pp = sqrt(dev / 6.0);
-        double lam_min = mean;  // (a multiple of the identity)
-        if (pp > 0.0) {
-            double B[3][3];
-            for (int i = 0; i < 3; i++)
-                for (int j = 0; j < 3; j++) B[i][j] = (G[i][j] - (i == j ? mean : 0.0)) / pp;
-            const double det = B[0][0] * (B[1][1] * B[2][2] - B[1][2] * B[2][1]) - B[0][1] * (B[1][0] * B[2][2] - B[1][2] * B[2][0]) +
-                               B[0][2] * (B[1][0] * B[2][1] - B[1][1] * B[2][0]);
-            const double phi = acos(std::min(1.0, std::max(-1.0, det / 2.0))) / 3.0;
-            lam_min = mean + 2.0 * pp * cos(phi + 2.0 * 3.14159265358979323846 / 3.0);
-        }
-        // (the eigenvalue carries an absolute error of a few 1e-16 tr: taken off, with the kernel's roundings, as 1e-3 tr)
-        const double safe = lam_min - 1e-3 * tr;
+        const double safe = rot_sigma_min2(o.rot);
         if (!(safe > 0.0)) return INFINITY;
         const double b0 = o.size[0] + m, b1 = o.size[1] + m, b2 = o.size[2] + m;
         reach = sqrt((b0 * b0 + b1 * b1 + b2 * b2) / safe);
     }
-    const double r2 = reach * reach * 1.002001;  // (reach + 0.1 %)^2
-    return r2 < 3e38 ? (float)r2 * 1.000001f : INFINITY;
+    return reach2_of(reach);
 }
 
 struct SolidsCall {
@@ -1500,6 +1513,184 @@ ws_status ws_collide_solids(ws_handle *h, const ws_solid *s, uint32_t k, uint32_
                             double *out_angular)
 {
     SolidsCall call{s, k, out_contacts, out_impulse, out_angular};
+    const ws_status st = edit_fluid(h, call);
+    if (!st) call.outputs();
+    return st;
+}
+
+// ======================================================================================
+// solids given as signed-distance volumes
+// ======================================================================================
+}  // extern "C"
+
+namespace {
+
+// 64-bit FNV-1a over 32-bit words: what a slot remembers of its volume for the slabs' agreement
+uint64_t volume_mix(uint64_t hash, const void *p, size_t words)
+{
+    const uint32_t *w = static_cast<const uint32_t *>(p);
+    for (size_t t = 0; t < words; t++) hash = (hash ^ w[t]) * 1099511628211ull;
+    return hash;
+}
+
+// the argument errors of ws_volume_upload with an array (nullptr = acceptable)
+const char *volume_refusal(const float *origin, const float *spacing, const uint32_t *dims, const float *sdf)
+{
+    if (!origin || !spacing || !dims) return "volume: origin, spacing or dims is NULL";
+    uint64_t nodes = 1;
+    for (int c = 0; c < 3; c++) {
+        if (dims[c] < 2u || dims[c] > 1024u) return "volume: every dims entry must lie in 2 .. 1024";
+        nodes *= dims[c];
+        if (ws_bad_float(origin[c])) return "volume: origin must be finite and at most 1e15 in magnitude";
+        if (ws_bad_float(spacing[c]) || !(spacing[c] > 0.f)) return "volume: spacing must be finite, > 0 and at most 1e15";
+        if ((double)(dims[c] - 1u) * spacing[c] > 1e15) return "volume: an extent (dims - 1) * spacing is above 1e15";
+    }
+    if (nodes > (1ull << 26)) return "volume: more than 2^26 nodes";
+    for (uint64_t t = 0; t < nodes; t++)
+        if (ws_bad_float(sdf[t])) return "volume: every sdf value must be finite and at most 1e15 in magnitude";
+    return nullptr;
+}
+
+void volume_clear(ws_handle *h, uint32_t slot)
+{
+    h->volume[slot].release();
+    h->volume_desc[slot] = WsVolumeDesc{};
+    h->volume_hash[slot] = 0;
+}
+
+// the argument errors of ws_collide_volumes (nullptr = acceptable); nothing is touched before this has passed
+const char *volumes_refusal(const ws_handle *h, const ws_volume_pose *v, uint32_t k)
+{
+    if (!v) return "volumes: v is NULL";
+    if (k < 1u || k > WS_MAX_VOLUME_POSES) return "volumes: k outside 1 .. WS_MAX_VOLUME_POSES";
+    for (uint32_t e = 0; e < k; e++) {
+        const ws_volume_pose &o = v[e];
+        if (o.slot >= WS_MAX_VOLUMES) return "volumes: slot must be below WS_MAX_VOLUMES";
+        if (!h->volume[o.slot].p) return "volumes: the slot holds no volume (ws_volume_upload)";
+        if (o.flags) return "volumes: flags must be 0";
+        if (o.reserved) return "volumes: the reserved word must be 0";
+        for (int c = 0; c < 9; c++)
+            if (ws_bad_float(o.rot[c])) return "volumes: rot must be finite and at most 1e15 in magnitude";
+        for (int c = 0; c < 3; c++)
+            if (ws_bad_float(o.centre[c]) || ws_bad_float(o.velocity[c]) || ws_bad_float(o.angular_velocity[c]))
+                return "volumes: centre, velocity and angular_velocity must be finite and at most 1e15 in magnitude";
+        if (ws_bad_float(o.restitution) || ws_bad_float(o.friction) || ws_bad_float(o.margin)) return "volumes: restitution, friction and margin must be finite";
+        if (o.restitution < 0.f || o.restitution > 1.f || o.friction < 0.f || o.friction > 1.f) return "volumes: restitution and friction must lie in [0, 1]";
+        if (o.margin < 0.f) return "volumes: margin must be >= 0";
+    }
+    return nullptr;
+}
+
+// The squared distance from a pose's centre beyond which no particle can be in the volume's domain -- outside the domain
+// there is no contact, so the margin does not enter.  In the domain every l_a lies between origin_a and origin_a + (dims_a
+// - 1) spacing_a, so |l| is at most the largest |l| over the box's eight corners, and |q| <= |l| / sigma_min(R) (solids_reach2
+// has the roundings' allowance; a near-singular rot gives +inf: never skipped).
+float volumes_reach2(const ws_volume_pose &o, const WsVolumeDesc &D)
+{
+    const double safe = rot_sigma_min2(o.rot);
+    if (!(safe > 0.0)) return INFINITY;
+    double far2 = 0.0;
+    for (int c = 0; c < 3; c++) {
+        const double lo = D.origin[c], hi = lo + (double)(D.dims[c] - 1u) * D.spacing[c];
+        const double a = std::max(fabs(lo), fabs(hi));
+        far2 += a * a;
+    }
+    return reach2_of(sqrt(far2 / safe));
+}
+
+struct VolumesCall {
+    const ws_handle *owner;  // whose slots the poses name
+    const ws_volume_pose *v;
+    uint32_t k;
+    uint32_t *out_contacts;
+    double *out_impulse, *out_angular;
+    const char *tag = "volumes", *things = "poses or volumes";
+    WsVolumeArgs args{};
+    unsigned long long sums[WS_MAX_VOLUME_POSES * WS_SOLID_WORDS];  // fetch()'s copy of the accumulator words
+    bool react() const { return out_contacts || out_impulse || out_angular; }
+    const char *refuse() const { return volumes_refusal(owner, v, k); }
+    ws_status prepare(ws_handle *h)  // the slots as they are now, the poses' bytes as given, and each one's reach
+    {
+        memcpy(args.vs.vol, h->volume_desc, sizeof args.vs.vol);
+        memcpy(args.vs.e, v, (size_t)k * sizeof(ws_volume_pose));
+        for (uint32_t e = 0; e < k; e++) args.vs.reach2[e] = volumes_reach2(v[e], h->volume_desc[v[e].slot]);
+        args.k = k;
+        if (!react()) return WS_OK;
+        const ws_status st = scratch_zeroed(h, h->solid_sums, sizeof sums, "volume reaction sums");
+        args.sums = h->solid_sums.p;
+        return st;
+    }
+    // (valid: every slot the poses name is below WS_MAX_VOLUMES and holds a volume)
+    template <class M>
+    void mix(M m, bool valid) const
+    {
+        m(&k, 4);
+        if (!valid) return;
+        m(v, (size_t)k * sizeof(ws_volume_pose));
+        for (uint32_t s = 0; s < WS_MAX_VOLUMES; s++) {
+            bool used = false;
+            for (uint32_t e = 0; e < k; e++) used = used || v[e].slot == s;
+            if (used) m(&owner->volume_hash[s], 8);  // (covers dims, origin, spacing and the array: ws_volume_upload)
+        }
+    }
+    hipError_t fetch(ws_handle *h) { return react() ? copy_now(h, sums, h->solid_sums.p, sizeof sums, hipMemcpyDeviceToHost) : hipSuccess; }
+    void outputs() const  // (SolidsCall::outputs: only after the whole call has succeeded)
+    {
+        for (uint32_t e = 0; react() && e < k; e++) {
+            const unsigned long long *w = sums + (size_t)e * WS_SOLID_WORDS;
+            if (out_contacts) out_contacts[e] = (uint32_t)w[0];
+            for (int c = 0; c < 3; c++) {
+                if (out_impulse) out_impulse[3 * e + c] = (double)(long long)w[1 + c] * 0x1p-24;
+                if (out_angular) out_angular[3 * e + c] = (double)(long long)w[4 + c] * 0x1p-24;
+            }
+        }
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+ws_status ws_volume_upload(ws_handle *h, uint32_t slot, const float origin[3], const float spacing[3], const uint32_t dims[3],
+                           const float *sdf)
+{
+    if (!h) return WS_ERR_INVALID_ARG;
+    WS_DEAD_CHECK(h);
+    if (h->flags & WS_FLAG_REFERENCE_ORDER) return fail(h, WS_ERR_UNSUPPORTED, "volume: not in the reference-order validation mode");
+    if (slot >= WS_MAX_VOLUMES) return fail(h, WS_ERR_INVALID_ARG, "volume: slot must be below WS_MAX_VOLUMES");
+    if (sdf)
+        if (const char *why = volume_refusal(origin, spacing, dims, sdf)) return fail(h, WS_ERR_INVALID_ARG, why);
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));  // an enqueued edit may still be reading the old array
+    volume_clear(h, slot);
+    if (!sdf) return WS_OK;
+    const size_t nodes = (size_t)dims[0] * dims[1] * dims[2];
+    ws_status st = h->volume[slot].alloc(h, nodes * 4, "signed-distance volume");
+    if (st) return st;
+    const hipError_t e = copy_now(h, h->volume[slot].p, sdf, nodes * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        volume_clear(h, slot);
+        (void)hipGetLastError();
+        return fail(h, e == hipErrorOutOfMemory ? WS_ERR_OUT_OF_MEMORY : WS_ERR_HIP, "volume: the copy to the device", e);
+    }
+    WsVolumeDesc &D = h->volume_desc[slot];
+    D.sdf = h->volume[slot].p;
+    for (int c = 0; c < 3; c++) {
+        D.dims[c] = dims[c];
+        D.origin[c] = origin[c];
+        D.spacing[c] = spacing[c];
+    }
+    uint64_t hash = volume_mix(14695981039346656037ull, D.dims, 3);
+    hash = volume_mix(hash, D.origin, 3);
+    hash = volume_mix(hash, D.spacing, 3);
+    h->volume_hash[slot] = volume_mix(hash, sdf, nodes);
+    return WS_OK;
+}
+
+ws_status ws_collide_volumes(ws_handle *h, const ws_volume_pose *v, uint32_t k, uint32_t *out_contacts, double *out_impulse,
+                             double *out_angular)
+{
+    VolumesCall call{h, v, k, out_contacts, out_impulse, out_angular};
     const ws_status st = edit_fluid(h, call);
     if (!st) call.outputs();
     return st;

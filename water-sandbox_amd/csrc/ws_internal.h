@@ -330,6 +330,14 @@ struct WsField {
     WsScratch<float> rays, ray_t, ray_n;
 };
 
+// One resident signed-distance volume (ws_volume_upload) as ws_collide_volumes' kernel sees it
+struct WsVolumeDesc {
+    const float *sdf;  // dims[0] x dims[1] x dims[2] floats on the device, x fastest; nullptr: the slot is empty
+    uint32_t dims[3];
+    float origin[3];
+    float spacing[3];
+};
+
 struct ws_handle {
     int device = 0;
     uint32_t flags = 0;
@@ -361,7 +369,12 @@ struct ws_handle {
     uint32_t *stats = nullptr;    // device counters: [0] particle-steps with more candidates than the mask holds
     uint8_t *mult = nullptr;      // 27 stencil multiplicities (hash aliasing), device
     WsScratch<uint32_t> force_cnt;  // ws_apply_forces: WS_MAX_FORCES per-emitter counts (allocated by the first call that asks)
-    WsScratch<unsigned long long> solid_sums;  // ws_collide_solids: WS_MAX_SOLIDS x WS_SOLID_WORDS sums (allocated by the first call that asks)
+    WsScratch<unsigned long long> solid_sums;  // ws_collide_solids / _volumes: WS_MAX_SOLIDS x WS_SOLID_WORDS sums (allocated by the first call that asks)
+    // ws_volume_upload: the resident signed-distance volumes, one exact-size buffer per slot (p == nullptr: empty), what
+    // the kernel is told about each and a hash of {dims, origin, spacing, the array's bytes} for the slabs' agreement
+    WsScratch<float> volume[WS_MAX_VOLUMES];
+    WsVolumeDesc volume_desc[WS_MAX_VOLUMES] = {};
+    uint64_t volume_hash[WS_MAX_VOLUMES] = {};
     bool alias = false;
     size_t grid_alloc_cells = 0;  // cells that count / cursor hold
     // The owners of the arrays above, one per lifetime (ws_api.cpp):
@@ -567,7 +580,22 @@ struct WsSolidArgs {
     unsigned long long *sums;
     bool outputs() const { return sums != nullptr; }
 };
-// Args = WsForceArgs or WsSolidArgs.  The first edits `cur` in place and re-bins it (what bin_current leaves: cid, the
+// Volumes (ws_collide_volumes): the descriptors of the handle's WS_MAX_VOLUMES slots (sdf == nullptr: empty, used by no
+// pose that passed validation), the poses with their squared reach (volumes_reach2 in ws_api.cpp) and the solids' sums,
+// one row of WS_SOLID_WORDS per pose.  About 1.8 KB, like WsSolidSet.
+struct WsVolumeSet {
+    WsVolumeDesc vol[WS_MAX_VOLUMES];
+    ws_volume_pose e[WS_MAX_VOLUME_POSES];
+    float reach2[WS_MAX_VOLUME_POSES];
+};
+struct WsVolumeArgs {
+    WsVolumeSet vs;
+    uint32_t k;
+    unsigned long long *sums;
+    bool outputs() const { return sums != nullptr; }
+};
+static_assert(WS_MAX_VOLUME_POSES == WS_MAX_SOLIDS, "the poses' sums are the solids' accumulator rows");
+// Args = WsForceArgs, WsSolidArgs or WsVolumeArgs.  The first edits `cur` in place and re-bins it (what bin_current leaves: cid, the
 // record's cell id, count, rank); the second edits the gathered {id, pos, vel, pred} records of slab handles (d: the global
 // grid, its container and damping).
 template <class Args>

@@ -663,6 +663,76 @@ __device__ __forceinline__ long long wave_sum_i64(long long x)
     return x;
 }
 
+// Steps 3 to 6 of the definition, shared by every edit that collides (solids_eval, volumes_eval): given the signed distance
+// s and the outward unit normal n of one object at the running position -- `hit` = the particle is active and s < margin
+// -- the push-out, the response against the object's surface velocity and, with REACT, the object's contact count and six
+// fixed-point sums into its row `a` of the workgroup's accumulator.  Every lane of the wave must call.
+template <bool REACT>
+__device__ __forceinline__ bool contact_respond(bool hit, float s, float nx, float ny, float nz, float margin, const float *centre,
+                                                const float *V, const float *W, float restitution, float friction, float4 &p,
+                                                float4 &v, unsigned long long *a)
+{
+    bool kicked = false;
+    float dvx = 0.f, dvy = 0.f, dvz = 0.f, rx = 0.f, ry = 0.f, rz = 0.f;
+    if (hit) {
+        const float out = margin - s;
+        p.x = p.x + out * nx;
+        p.y = p.y + out * ny;
+        p.z = p.z + out * nz;
+        rx = p.x - centre[0]; ry = p.y - centre[1]; rz = p.z - centre[2];
+        const float ux = V[0] + (W[1] * rz - W[2] * ry);
+        const float uy = V[1] + (W[2] * rx - W[0] * rz);
+        const float uz = V[2] + (W[0] * ry - W[1] * rx);
+        const float relx = v.x - ux, rely = v.y - uy, relz = v.z - uz;
+        const float vn = relx * nx + rely * ny + relz * nz;
+        if (vn < 0.f) {
+            kicked = true;
+            const float j = (1.f + restitution) * (-vn);
+            const float tx = relx - vn * nx, ty = rely - vn * ny, tz = relz - vn * nz;
+            dvx = j * nx - friction * tx;
+            dvy = j * ny - friction * ty;
+            dvz = j * nz - friction * tz;
+            v.x = v.x + dvx;
+            v.y = v.y + dvy;
+            v.z = v.z + dvz;
+        }
+    }
+    if constexpr (REACT) {
+        const unsigned long long hits = __ballot(hit);
+        if (hits) {  // wave-uniform
+            const bool lead = (threadIdx.x & 63u) == 0u;
+            if (lead) atomicAdd(&a[0], (unsigned long long)__popcll(hits));
+            if (__ballot(kicked)) {
+                long long w[6] = {0, 0, 0, 0, 0, 0};
+                if (kicked) {
+                    const float ix = -dvx, iy = -dvy, iz = -dvz;
+                    w[0] = solids_fixed(ix);
+                    w[1] = solids_fixed(iy);
+                    w[2] = solids_fixed(iz);
+                    w[3] = solids_fixed(ry * iz - rz * iy);
+                    w[4] = solids_fixed(rz * ix - rx * iz);
+                    w[5] = solids_fixed(rx * iy - ry * ix);
+                }
+#pragma unroll
+                for (int c = 0; c < 6; c++) {
+                    const long long sum = wave_sum_i64(w[c]);
+                    if (lead && sum) atomicAdd(&a[1 + c], (unsigned long long)sum);
+                }
+            }
+        }
+    }
+    return hit;
+}
+
+// the step's own container rule (force_integrate_bin) on a particle some object touched
+__device__ __forceinline__ void contact_container(const WsDev &d, float4 &p, float4 &v)
+{
+    const float nd = -1.f * d.damping;
+    if (p.x < d.ext_min[0]) { v.x *= nd; p.x = d.ext_min[0]; } else if (p.x > d.ext_max[0]) { v.x *= nd; p.x = d.ext_max[0]; }
+    if (p.y < d.ext_min[1]) { v.y *= nd; p.y = d.ext_min[1]; } else if (p.y > d.ext_max[1]) { v.y *= nd; p.y = d.ext_max[1]; }
+    if (p.z < d.ext_min[2]) { v.z *= nd; p.z = d.ext_min[2]; } else if (p.z > d.ext_max[2]) { v.z *= nd; p.z = d.ext_max[2]; }
+}
+
 template <bool REACT>
 __device__ __forceinline__ bool solids_eval(const WsDev &d, const WsSolidSet &ss, uint32_t k, bool active, float4 &p, float4 &v,
                                             unsigned long long *acc)
@@ -717,66 +787,10 @@ __device__ __forceinline__ bool solids_eval(const WsDev &d, const WsSolidSet &ss
             s = -s;
             nx = -nx; ny = -ny; nz = -nz;
         }
-        const bool hit = active && s < S.margin;
-        bool kicked = false;
-        float dvx = 0.f, dvy = 0.f, dvz = 0.f, rx = 0.f, ry = 0.f, rz = 0.f;
-        if (hit) {
-            touched = true;
-            const float out = S.margin - s;
-            p.x = p.x + out * nx;
-            p.y = p.y + out * ny;
-            p.z = p.z + out * nz;
-            rx = p.x - S.centre[0]; ry = p.y - S.centre[1]; rz = p.z - S.centre[2];
-            const float *W = S.angular_velocity;
-            const float ux = S.velocity[0] + (W[1] * rz - W[2] * ry);
-            const float uy = S.velocity[1] + (W[2] * rx - W[0] * rz);
-            const float uz = S.velocity[2] + (W[0] * ry - W[1] * rx);
-            const float relx = v.x - ux, rely = v.y - uy, relz = v.z - uz;
-            const float vn = relx * nx + rely * ny + relz * nz;
-            if (vn < 0.f) {
-                kicked = true;
-                const float j = (1.f + S.restitution) * (-vn);
-                const float tx = relx - vn * nx, ty = rely - vn * ny, tz = relz - vn * nz;
-                dvx = j * nx - S.friction * tx;
-                dvy = j * ny - S.friction * ty;
-                dvz = j * nz - S.friction * tz;
-                v.x = v.x + dvx;
-                v.y = v.y + dvy;
-                v.z = v.z + dvz;
-            }
-        }
-        if constexpr (REACT) {
-            const unsigned long long hits = __ballot(hit);
-            if (hits) {  // wave-uniform
-                const bool lead = (threadIdx.x & 63u) == 0u;
-                unsigned long long *a = acc + e * WS_SOLID_WORDS;
-                if (lead) atomicAdd(&a[0], (unsigned long long)__popcll(hits));
-                if (__ballot(kicked)) {
-                    long long w[6] = {0, 0, 0, 0, 0, 0};
-                    if (kicked) {
-                        const float ix = -dvx, iy = -dvy, iz = -dvz;
-                        w[0] = solids_fixed(ix);
-                        w[1] = solids_fixed(iy);
-                        w[2] = solids_fixed(iz);
-                        w[3] = solids_fixed(ry * iz - rz * iy);
-                        w[4] = solids_fixed(rz * ix - rx * iz);
-                        w[5] = solids_fixed(rx * iy - ry * ix);
-                    }
-#pragma unroll
-                    for (int c = 0; c < 6; c++) {
-                        const long long sum = wave_sum_i64(w[c]);
-                        if (lead && sum) atomicAdd(&a[1 + c], (unsigned long long)sum);
-                    }
-                }
-            }
-        }
+        touched |= contact_respond<REACT>(active && s < S.margin, s, nx, ny, nz, S.margin, S.centre, S.velocity, S.angular_velocity,
+                                          S.restitution, S.friction, p, v, acc + e * WS_SOLID_WORDS);
     }
-    if (touched) {  // the step's own container rule (force_integrate_bin)
-        const float nd = -1.f * d.damping;
-        if (p.x < d.ext_min[0]) { v.x *= nd; p.x = d.ext_min[0]; } else if (p.x > d.ext_max[0]) { v.x *= nd; p.x = d.ext_max[0]; }
-        if (p.y < d.ext_min[1]) { v.y *= nd; p.y = d.ext_min[1]; } else if (p.y > d.ext_max[1]) { v.y *= nd; p.y = d.ext_max[1]; }
-        if (p.z < d.ext_min[2]) { v.z *= nd; p.z = d.ext_min[2]; } else if (p.z > d.ext_max[2]) { v.z *= nd; p.z = d.ext_max[2]; }
-    }
+    if (touched) contact_container(d, p, v);
     return touched;
 }
 
@@ -789,8 +803,76 @@ __device__ __forceinline__ void solids_flush(const unsigned long long *acc, uint
 }
 
 // ---------------------------------------------------------------------------------
-// the between-step edits (ws_apply_forces, ws_collide_solids, and whatever comes next): an edit is a TYPE, and two kernels
-// serve every edit -- k_edit_current on a single handle's `cur`, k_edit_records on the gathered records of slab handles
+// ws_collide_volumes: ws_collide_solids with the solid given as a signed-distance volume (never inside ws_step)
+//
+// include/wsfluid.h pins every operation; IEEE arithmetic whatever the handle's flags.  The slots' descriptors, the poses
+// and one squared reach per pose are a by-value kernel argument (WsVolumeSet), read through scalar loads in the wave-uniform
+// loop -- the pose's slot is wave-uniform too, so its descriptor is.  A wave none of whose lanes lies within the pose's
+// reach skips it with one ballot (reach2: volumes_reach2, a bound no point of the volume's domain lies beyond; outside the
+// domain there is no contact, so the skip changes no bit).
+// The eight corner values are the only gathers: every lane of a wave that goes on computes a CLAMPED cell -- a lane outside
+// the domain, or an inactive one, reads cell (0, 0, 0) -- so that the eight loads are issued together, before the first
+// use and under no divergent branch, through the read-only path.  The distance and the gradient are those of one
+// trilinear interpolant; steps 3 to 6 and the reaction are the solids' (contact_respond).  Every lane of the wave must call.
+// ---------------------------------------------------------------------------------
+template <bool REACT>
+__device__ __forceinline__ bool volumes_eval(const WsDev &d, const WsVolumeSet &vs, uint32_t k, bool active, float4 &p, float4 &v,
+                                             unsigned long long *acc)
+{
+    bool touched = false;
+    for (uint32_t e = 0; e < k; e++) {
+        const ws_volume_pose &P = vs.e[e];
+        const float qx = p.x - P.centre[0], qy = p.y - P.centre[1], qz = p.z - P.centre[2];
+        const float q2 = qx * qx + qy * qy + qz * qz;
+        if (!__ballot(active && q2 <= vs.reach2[e])) continue;  // wave-uniform: nobody can be in the domain
+        const WsVolumeDesc &D = vs.vol[P.slot & (WS_MAX_VOLUMES - 1u)];
+        const float *R = P.rot;
+        const float l0 = R[0] * qx + R[1] * qy + R[2] * qz;
+        const float l1 = R[3] * qx + R[4] * qy + R[5] * qz;
+        const float l2 = R[6] * qx + R[7] * qy + R[8] * qz;
+        const float g0 = (l0 - D.origin[0]) / D.spacing[0];
+        const float g1 = (l1 - D.origin[1]) / D.spacing[1];
+        const float g2 = (l2 - D.origin[2]) / D.spacing[2];
+        const uint32_t n0 = D.dims[0], n1 = D.dims[1], n2 = D.dims[2];
+        const bool in = active && g0 >= 0.f && g0 <= (float)(n0 - 1u) && g1 >= 0.f && g1 <= (float)(n1 - 1u) && g2 >= 0.f &&
+                        g2 <= (float)(n2 - 1u);
+        const float h0 = in ? g0 : 0.f, h1 = in ? g1 : 0.f, h2 = in ? g2 : 0.f;
+        const uint32_t i0 = min((uint32_t)h0, n0 - 2u), i1 = min((uint32_t)h1, n1 - 2u), i2 = min((uint32_t)h2, n2 - 2u);
+        const float f0 = h0 - (float)i0, f1 = h1 - (float)i1, f2 = h2 - (float)i2;
+        const float *__restrict__ c = D.sdf + ((i2 * n1 + i1) * n0 + i0);  // (at most 2^26 nodes)
+        const uint32_t sy = n0, sz = n0 * n1;
+        const float c000 = c[0], c100 = c[1], c010 = c[sy], c110 = c[sy + 1u];
+        const float c001 = c[sz], c101 = c[sz + 1u], c011 = c[sz + sy], c111 = c[sz + sy + 1u];
+        const float d00 = c100 - c000, d10 = c110 - c010, d01 = c101 - c001, d11 = c111 - c011;
+        const float cx00 = c000 + f0 * d00, cx10 = c010 + f0 * d10, cx01 = c001 + f0 * d01, cx11 = c011 + f0 * d11;
+        const float e0 = cx10 - cx00, e1 = cx11 - cx01;
+        const float cy0 = cx00 + f1 * e0, cy1 = cx01 + f1 * e1;
+        const float hh = cy1 - cy0;
+        const float s = cy0 + f2 * hh;
+        const float dz0 = d00 + f1 * (d10 - d00), dz1 = d01 + f1 * (d11 - d01);
+        const float G0 = (dz0 + f2 * (dz1 - dz0)) / D.spacing[0];
+        const float G1 = (e0 + f2 * (e1 - e0)) / D.spacing[1];
+        const float G2 = hh / D.spacing[2];
+        const float gg = G0 * G0 + G1 * G1 + G2 * G2;
+        float m0 = 0.f, m1 = 1.f, m2 = 0.f;
+        if (gg > 0.f) {
+            const float len = sqrtf(gg);
+            m0 = G0 / len; m1 = G1 / len; m2 = G2 / len;
+        }
+        const float nx = (m0 * R[0] + m1 * R[3]) + m2 * R[6];
+        const float ny = (m0 * R[1] + m1 * R[4]) + m2 * R[7];
+        const float nz = (m0 * R[2] + m1 * R[5]) + m2 * R[8];
+        touched |= contact_respond<REACT>(in && s < P.margin, s, nx, ny, nz, P.margin, P.centre, P.velocity, P.angular_velocity,
+                                          P.restitution, P.friction, p, v, acc + e * WS_SOLID_WORDS);
+    }
+    if (touched) contact_container(d, p, v);
+    return touched;
+}
+
+// ---------------------------------------------------------------------------------
+// the between-step edits (ws_apply_forces, ws_collide_solids, ws_collide_volumes, and whatever comes next): an edit is a
+// TYPE, and two kernels serve every edit -- k_edit_current on a single handle's `cur`, k_edit_records on the gathered
+// records of slab handles
 //
 // An edit is a by-value kernel argument (its objects reach the wave-uniform loop through scalar loads) that declares
 //   moves      whether eval may change the position (else p comes back as it went in and is not stored);
@@ -828,11 +910,25 @@ struct EditSolids {
     __device__ void flush(const unsigned long long *acc) const { solids_flush(acc, a.k, a.sums); }
 };
 
+template <bool REACT>
+struct EditVolumes {
+    static constexpr bool moves = true;
+    static constexpr uint32_t acc_words = REACT ? WS_MAX_VOLUME_POSES * WS_SOLID_WORDS : 0u;
+    WsVolumeArgs a;
+    __device__ bool eval(const WsDev &d, bool active, float4 &p, float4 &v, unsigned long long *acc) const
+    {
+        return volumes_eval<REACT>(d, a.vs, a.k, active, p, v, acc);
+    }
+    __device__ void flush(const unsigned long long *acc) const { solids_flush(acc, a.k, a.sums); }
+};
+
 // what a launcher's argument struct becomes on the device: WITH = whether the call wants its outputs (COUNTS / REACT)
 template <class With>
 EditForces<With::value> edit_of(const WsForceArgs &a, With) { return {a}; }
 template <class With>
 EditSolids<With::value> edit_of(const WsSolidArgs &a, With) { return {a}; }
+template <class With>
+EditVolumes<With::value> edit_of(const WsVolumeArgs &a, With) { return {a}; }
 
 template <class Edit>
 __device__ __forceinline__ void edit_begin(unsigned long long *acc)
@@ -944,6 +1040,7 @@ void wsk_edit_current(hipStream_t s, const WsDev &d, WsSoA cur, uint32_t *cid, u
 }
 template void wsk_edit_current(hipStream_t, const WsDev &, WsSoA, uint32_t *, uint32_t *, const WsForceArgs &);
 template void wsk_edit_current(hipStream_t, const WsDev &, WsSoA, uint32_t *, uint32_t *, const WsSolidArgs &);
+template void wsk_edit_current(hipStream_t, const WsDev &, WsSoA, uint32_t *, uint32_t *, const WsVolumeArgs &);
 
 template <class Args>
 void wsk_edit_records(hipStream_t s, const WsDev &d, uint32_t *all, const uint32_t *cnt, uint32_t world, uint32_t max_n,
@@ -958,6 +1055,7 @@ void wsk_edit_records(hipStream_t s, const WsDev &d, uint32_t *all, const uint32
 }
 template void wsk_edit_records(hipStream_t, const WsDev &, uint32_t *, const uint32_t *, uint32_t, uint32_t, size_t, const WsForceArgs &);
 template void wsk_edit_records(hipStream_t, const WsDev &, uint32_t *, const uint32_t *, uint32_t, uint32_t, size_t, const WsSolidArgs &);
+template void wsk_edit_records(hipStream_t, const WsDev &, uint32_t *, const uint32_t *, uint32_t, uint32_t, size_t, const WsVolumeArgs &);
 
 // ---------------------------------------------------------------------------------
 // smoothing kernels, assets/simulation.wgsl:93-117 (evaluation order as written)

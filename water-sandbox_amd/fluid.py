@@ -56,6 +56,7 @@ ABI_SYMBOLS = [
     "ws_read_velocities", "ws_sample_velocity_grid", "ws_sample_velocity_points", "ws_advect_points",
     "ws_default_whitewater_emit_params", "ws_default_whitewater_step_params", "ws_read_whitewater", "ws_emit_whitewater",
     "ws_step_whitewater", "ws_apply_forces", "ws_default_body_params", "ws_body_forces", "ws_collide_solids",
+    "ws_volume_upload", "ws_collide_volumes",
 ]
 
 
@@ -174,6 +175,27 @@ class WsSolid(C.Structure):
         ("friction", C.c_float),
         ("margin", C.c_float),
         ("reserved", C.c_uint32 * 2),
+    ]
+
+
+WS_MAX_VOLUMES = 4
+WS_MAX_VOLUME_POSES = 16
+
+
+class WsVolumePose(C.Structure):
+    """ws_volume_pose: one instance of a resident signed-distance volume in ws_collide_volumes (include/wsfluid.h)."""
+
+    _fields_ = [
+        ("slot", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("centre", C.c_float * 3),
+        ("rot", C.c_float * 9),
+        ("velocity", C.c_float * 3),
+        ("angular_velocity", C.c_float * 3),
+        ("restitution", C.c_float),
+        ("friction", C.c_float),
+        ("margin", C.c_float),
+        ("reserved", C.c_uint32),
     ]
 
 
@@ -309,6 +331,8 @@ def bind_library(path):
     L.ws_apply_forces.argtypes = [vp, vp, u32, C.c_float, vp]
     L.ws_default_body_params.argtypes = [vp]
     L.ws_collide_solids.argtypes = [vp, vp, u32, vp, vp, vp]
+    L.ws_volume_upload.argtypes = [vp, u32, vp, vp, vp, vp]
+    L.ws_collide_volumes.argtypes = [vp, vp, u32, vp, vp, vp]
     L.ws_body_forces.argtypes = [vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, vp]
     return L
 
@@ -606,6 +630,40 @@ def collide_solids(L, h, check, solids, reaction=True):
         return None
     contacts, impulse, angular = np.zeros(max(k, 1), np.uint32), np.zeros((max(k, 1), 3)), np.zeros((max(k, 1), 3))
     check(L.ws_collide_solids(h, C.byref(arr), k, contacts.ctypes.data, impulse.ctypes.data, angular.ctypes.data))
+    return contacts[:k], impulse[:k], angular[:k]
+
+
+def volume_pose(slot, centre=(0.0, 0.0, 0.0), rot=(1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0), velocity=(0.0, 0.0, 0.0),
+                angular_velocity=(0.0, 0.0, 0.0), restitution=0.0, friction=0.0, margin=0.0):
+    """One ws_volume_pose: an instance of the volume resident in `slot`; centre = where the volume's local origin lies,
+    rot = the nine floats of the rows R_0 R_1 R_2 (or a 3 x 3 nested sequence)."""
+    rot = [float(x) for x in np.asarray(rot, np.float64).reshape(-1)]
+    return WsVolumePose(slot, 0, (C.c_float * 3)(*centre), (C.c_float * 9)(*rot), (C.c_float * 3)(*velocity),
+                        (C.c_float * 3)(*angular_velocity), restitution, friction, margin, 0)
+
+
+def upload_volume(L, h, check, slot, origin, spacing, sdf):
+    """ws_volume_upload: sdf (nz, ny, nx) float32 -- x fastest in memory -- or None to release the slot."""
+    if sdf is None:
+        check(L.ws_volume_upload(h, slot, None, None, None, None))
+        return
+    sdf = np.ascontiguousarray(sdf, np.float32)
+    assert sdf.ndim == 3, "sdf has the shape (nz, ny, nx)"
+    dims = (C.c_uint32 * 3)(sdf.shape[2], sdf.shape[1], sdf.shape[0])
+    check(L.ws_volume_upload(h, slot, (C.c_float * 3)(*origin), (C.c_float * 3)(*spacing), dims, sdf.ctypes.data))
+
+
+def collide_volumes(L, h, check, poses, reaction=True):
+    """ws_collide_volumes: ws_collide_solids against poses of the resident signed-distance volumes (include/wsfluid.h has
+    the definition).  poses: a WsVolumePose or a sequence of them.  Returns what collide_solids returns, per pose."""
+    poses = [poses] if isinstance(poses, WsVolumePose) else list(poses)
+    k = len(poses)
+    arr = (WsVolumePose * max(k, 1))(*poses)
+    if not reaction:
+        check(L.ws_collide_volumes(h, C.byref(arr), k, None, None, None))
+        return None
+    contacts, impulse, angular = np.zeros(max(k, 1), np.uint32), np.zeros((max(k, 1), 3)), np.zeros((max(k, 1), 3))
+    check(L.ws_collide_volumes(h, C.byref(arr), k, contacts.ctypes.data, impulse.ctypes.data, angular.ctypes.data))
     return contacts[:k], impulse[:k], angular[:k]
 
 
@@ -970,6 +1028,16 @@ class FluidWorker:
         the contact count and the momentum the solid took per unit of particle mass, linear and about its centre -- or None
         with reaction=False (the call then only enqueues)."""
         return collide_solids(self._L, self._h, self._check, solids, reaction)
+
+    def upload_volume(self, slot, origin, spacing, sdf):
+        """Make a signed-distance volume resident in slot 0 .. 3: sdf of shape (nz, ny, nx), negative inside the solid,
+        node (i, j, k) at the local coordinates origin + (i, j, k) * spacing.  sdf=None releases the slot."""
+        upload_volume(self._L, self._h, self._check, slot, origin, spacing, sdf)
+
+    def collide_volumes(self, poses, reaction=True):
+        """Put resident volumes in the water between two steps: poses = volume_pose(...) or a list of up to 16.  What
+        collide_solids returns, per pose."""
+        return collide_volumes(self._L, self._h, self._check, poses, reaction)
 
     def body_forces(self, params, xyz, velocity, volume, body_start, centres, samples=False):
         """What the fluid does to things floating in it: buoyancy and drag on nb host-owned bodies, each a group of sample

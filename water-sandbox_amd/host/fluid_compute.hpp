@@ -400,6 +400,29 @@ class FluidWorker {
         return r;
     }
 
+    // Solids given as signed-distance volumes (include/wsfluid.h ws_volume_upload, ws_collide_volumes): a grid of
+    // distances per shape, uploaded once into one of WS_MAX_VOLUMES slots (sdf: nx * ny * nz floats, x fastest; empty =
+    // release the slot), then any number of poses of the resident volumes per call, with the solids' reaction.
+    void upload_volume(uint32_t slot, const float origin[3], const float spacing[3], const uint32_t dims[3],
+                       const std::vector<float> &sdf)
+    {
+        check(ws_volume_upload(h_, slot, origin, spacing, dims, sdf.empty() ? nullptr : sdf.data()));
+    }
+    SolidReaction collide_volumes(const std::vector<ws_volume_pose> &poses, bool react = true)
+    {
+        SolidReaction r;
+        if (poses.empty()) return r;
+        if (!react) {
+            check(ws_collide_volumes(h_, poses.data(), (uint32_t)poses.size(), nullptr, nullptr, nullptr));
+            return r;
+        }
+        r.contacts.resize(poses.size());
+        r.impulse.resize(3 * poses.size());
+        r.angular.resize(3 * poses.size());
+        check(ws_collide_volumes(h_, poses.data(), (uint32_t)poses.size(), r.contacts.data(), r.impulse.data(), r.angular.data()));
+        return r;
+    }
+
     std::vector<float> read_speeds()
     {
         std::vector<float> out(n_);

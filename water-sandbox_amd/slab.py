@@ -455,6 +455,15 @@ class SlabWorker:
         solids); the outputs are global.  reaction=False: this rank applies without asking for them (None)."""
         return fluid.collide_solids(self._L, self._h, self._check, solids, reaction)
 
+    def upload_volume(self, slot, origin, spacing, sdf):
+        """FluidWorker.upload_volume into THIS rank's slot (LOCAL: no communication; every rank uploads its own copy)."""
+        fluid.upload_volume(self._L, self._h, self._check, slot, origin, spacing, sdf)
+
+    def collide_volumes(self, poses, reaction=True):
+        """FluidWorker.collide_volumes on the GLOBAL particle set (COLLECTIVE: every rank makes the same call with the same
+        poses of the same volumes); the outputs are global.  reaction=False: this rank applies without asking (None)."""
+        return fluid.collide_volumes(self._L, self._h, self._check, poses, reaction)
+
     def body_forces(self, params, xyz, velocity, volume, body_start, centres, samples=False, want=True):
         """FluidWorker.body_forces over the GLOBAL particle set (COLLECTIVE); want=False: only contribute (None)."""
         return fluid.body_forces(self._L, self._h, self._check, params, xyz, velocity, volume, body_start, centres, samples, want)
