@@ -950,6 +950,75 @@ ws_status ws_volume_upload(ws_handle *h, uint32_t slot, const float origin[3], c
 ws_status ws_collide_volumes(ws_handle *h, const ws_volume_pose *v, uint32_t k, uint32_t *out_contacts,
                              double *out_impulse, double *out_angular);
 
+/* ---- the fluid holding together: surface tension and XSPH velocity smoothing (no reference counterpart) --
+ * The first edit that looks at a particle's neighbours.  The model is Akinci, Akinci and Teschner, "Versatile surface
+ * tension and adhesion for SPH fluids" (2013) -- a pairwise cohesion spline plus a normal-difference (curvature) term,
+ * with the symmetrising density factor -- and Monaghan's XSPH (1989).  ws_read_cohesion is the per-particle stage,
+ * read-only; ws_apply_cohesion adds the stage's dv to the velocities of the state the enqueued steps leave, by
+ * ws_apply_forces' route.  ws_step itself knows nothing of either.
+ * Below fl() is a rounding to float; arithmetic is IEEE whatever the handle's flags, as for the whitewater stage: every
+ * operation is rounded once, sqrt and division are correctly rounded, nothing is contracted, sums start at +0 and take
+ * their terms in the canonical order.  x, v are what ws_read_positions / ws_read_velocities return; h is the smoothing
+ * radius; rho_0 = rest_density, or the handle's target_density when rest_density == 0.
+ * Constants, as float operations in this order: h3 = (h*h)*h; h6 = h3*h3; h9 = h6*h3; kc = 32.0f / (3.14159274f * h9);
+ *   h664 = h6 * 0.015625f.
+ * Candidates of particle i: exactly the whitewater stage's -- those the density sampler's sweep visits around x_i and
+ *   accepts: the 27 cells of the clamped cell in increasing linear id, ids ascending inside a cell, e = x_j - x_i,
+ *   d2 = dot(e, e) (the whitewater block's dot), rejected iff d2 > d2_accept.  d = sqrt(d2).  A candidate at d == 0 (i
+ *   itself, a coincident particle) contributes nothing to pass B.
+ * Pass A, per particle: (rho_i, g_i) = the density and gradient ws_sample_density_points returns at x_i in its
+ *   WS_FLAG_IEEE_DIVISION form (rho_i includes i's own term, so rho_i > 0);  n_i,a = (h * g_i,a) / rho_i -- a
+ *   dimensionless normal that points into the fluid, about 1 at a free surface and about 0 in the bulk.
+ * Pass B, with A = X = (+0, +0, +0) and c_i = 0, per contributing candidate j (d > 0), in order:
+ *    1. xh_a = (-e_a) / d                                   (the unit vector from j to i)
+ *    2. q = 2.0f / (rho_i + rho_j)
+ *    3. K = rho_0 * q
+ *    4. t = h - d
+ *    5. t3 = (t*t)*t
+ *    6. d3 = (d*d)*d
+ *    7. pp = t3*d3
+ *    8. s = pp if 2.0f*d > h, else s = 2.0f*pp - h664
+ *    9. C = kc * s                                          (Akinci's spline: attraction beyond about h/3, repulsion closer)
+ *   10. fc = cohesion * C
+ *   11. T_a = fc * xh_a + curvature * (n_i,a - n_j,a)       (each product rounded, then the sum)
+ *   12. A_a = A_a - K * T_a
+ *   13. w = the density sampler's term at d, (h - d)^2 * pow2, the same bits
+ *   14. X_a = X_a + ((v_j,a - v_i,a) * w) * q
+ *   15. c_i += 1
+ * After the sweep: if c_i == 0 the particle is UNAFFECTED and dv = (+0, +0, +0); otherwise dv_a = dt * A_a + xsph * X_a
+ *   (each product rounded, then the sum).
+ * ws_read_cohesion: the stage, n entries in ORIGINAL-ID order, with every convention of ws_read_whitewater.  Outputs, any
+ *   of which may be NULL (all NULL: WS_ERR_INVALID_ARG on a single handle, contribute-only on a slab): out_normal n*3 (n_i),
+ *   out_density n (rho_i), out_dv n*3, out_neighbours n (c_i).  It waits for enqueued steps, writes nothing ws_step reads
+ *   and keeps its scratch in the sampler's.  Slab handles: COLLECTIVE on the gathered {position, velocity} set, the same
+ *   bits as a single handle; a rank that passes every output NULL only contributes; a rank validates its arguments after
+ *   the gather.
+ * ws_apply_cohesion: an affected particle (c_i > 0) gets v'_a = v_a + dv_a; an unaffected particle keeps its velocity bit
+ *   for bit (a -0 stays -0).  Positions do not change.  The predicted position of EVERY particle is recomputed by the
+ *   library's own rule and the state is binned again, as after ws_apply_forces.  out_affected, if not NULL, receives ONE
+ *   count: the particles with c_i > 0 (on slabs the global count).  Everything else is ws_apply_forces' contract:
+ *   ws_steps_done is unchanged; the 80-byte view keeps the last step's density, pressure and acceleration; a WS_FLAG_GRAPH
+ *   handle keeps replaying its captured step; the call may be made between ws_read_positions_begin and _end; slab handles
+ *   take the gather / common verdict / reload route, with p and dt in the agreement -- ranks whose arguments differ, or
+ *   any of which refuses, ALL return WS_ERR_INVALID_ARG and nothing is changed.
+ * Errors, with nothing touched: WS_ERR_INVALID_ARG (NULL handle or p; a non-zero reserved; any non-finite value or any
+ *   magnitude above 1e15; cohesion, curvature or rest_density < 0; xsph outside [0, 1]; dt not > 0; ws_read_cohesion:
+ *   every output NULL on a single handle); WS_ERR_UNSUPPORTED (WS_FLAG_REFERENCE_ORDER handles); WS_ERR_OUT_OF_MEMORY
+ *   (scratch cannot grow: the handle stays usable); WS_ERR_HIP on an unusable handle.  Whether a strength is stable at the
+ *   host's dt is the host's business, as a huge emitter strength is. */
+typedef struct ws_cohesion_params {   /* 20 bytes */
+    float cohesion;       /* offset 0:  gamma_c >= 0, the pairwise attraction                      */
+    float curvature;      /* offset 4:  gamma_n >= 0, the normal-difference (area-minimising) term */
+    float xsph;           /* offset 8:  epsilon in [0, 1]                                          */
+    float rest_density;   /* offset 12: rho_0; 0 = the handle's target_density (as ws_body_params) */
+    uint32_t reserved;    /* offset 16: must be 0                                                  */
+} ws_cohesion_params;
+/* Host-only (no device needed; WS_ERR_INVALID_ARG for NULL): 1, 1, 0.1, 0, 0. */
+ws_status ws_default_cohesion_params(ws_cohesion_params *out);
+ws_status ws_read_cohesion(ws_handle *h, const ws_cohesion_params *p, float dt, float *out_normal, float *out_density,
+                           float *out_dv, uint32_t *out_neighbours);
+ws_status ws_apply_cohesion(ws_handle *h, const ws_cohesion_params *p, float dt, uint32_t *out_affected);
+
 /* ---- the fluid acting on things that float in it: buoyancy and drag on host-owned bodies (no reference
  *      counterpart) ----------------------------------------------------------------------------------------------------
  * One-way coupling, water to body.  The HOST owns the bodies, as it owns whitewater's diffuse particles: it describes each

@@ -32,8 +32,11 @@ ws_status slab_regrid(ws_handle *h, const ws_params *params, bool rebalance);
 ws_status slab_field_positions(ws_handle *h, const float **xyz, WsDev *global, bool with_vel);
 template <class Call>
 ws_status slab_edit_gathered(ws_handle *h, Call &call);
+ws_status global_grid(const ws_params *params, uint32_t n_global, WsDev *out);
 // ws_field.inc
 void free_field(ws_handle *h);
+const char *cohesion_refusal(const ws_cohesion_params *p, float dt);
+ws_status cohesion_prepare(ws_handle *h, const WsGathered *g, const ws_cohesion_params *p, float dt, WsCohesionArgs *args);
 
 ws_status fail(ws_handle *h, ws_status st, const char *what, hipError_t e = hipSuccess)
 {
@@ -1279,8 +1282,9 @@ namespace {
 // (ForcesCall, SolidsCall, VolumesCall) carries
 //   tag, things     the call and its objects in ws_last_error;
 //   refuse()        the argument error, or nullptr; nothing is touched before it has passed;
-//   prepare(h)      after that: `args`, the kernel's argument, built once, and the output scratch it points to, grown
-//                   and zeroed on the handle's stream;
+//   prepare(h, g)   after that: `args`, the kernel's argument, built once, and the output scratch it points to, grown
+//                   and zeroed on the handle's stream; an edit that looks at neighbours (CohesionCall) runs its stage
+//                   here, on `cur` (g == nullptr) or on the state records a slab handle has gathered (g);
 //   mix(m, valid)   the arguments hashed with m(pointer, bytes) for the slabs' agreement -- the objects' bytes only if
 //                   `valid`;
 //   fetch(h)        the kernel's sums, complete on return.
@@ -1299,7 +1303,7 @@ ws_status edit_fluid(ws_handle *h, Call &call)
     HIP_TRY(h, hipSetDevice(h->device));
     if (h->slab) return slab_edit_gathered(h, call);  // collective: validated after the gather
     if (const char *why = call.refuse()) return fail(h, WS_ERR_INVALID_ARG, why);
-    const ws_status st = call.prepare(h);
+    const ws_status st = call.prepare(h, nullptr);
     if (st) return st;
     HIP_TRY(h, hipMemsetAsync(h->count, 0, (size_t)h->dev.ncells * 4, h->stream));
     wsk_edit_current(h->stream, h->dev, h->cur, h->cid_cur, h->count, call.args);
@@ -1335,7 +1339,7 @@ struct ForcesCall {
     const char *tag = "forces", *things = "emitters";
     WsForceArgs args{};
     const char *refuse() const { return forces_refusal(f, k, dt); }
-    ws_status prepare(ws_handle *h)  // (the k per-emitter counters only if the caller asks for them)
+    ws_status prepare(ws_handle *h, const WsGathered *)  // (the k per-emitter counters only if the caller asks for them)
     {
         memcpy(args.fs.e, f, (size_t)k * sizeof(ws_force));
         args.k = k;
@@ -1365,6 +1369,57 @@ extern "C" {
 ws_status ws_apply_forces(ws_handle *h, const ws_force *f, uint32_t k, float dt, uint32_t *out_affected)
 {
     ForcesCall call{f, k, dt, out_affected};
+    return edit_fluid(h, call);
+}
+
+// ======================================================================================
+// surface tension and XSPH: the edit that looks at neighbours (the stage: ws_field.inc)
+// ======================================================================================
+}  // extern "C"
+
+namespace {
+
+struct CohesionCall {
+    const ws_cohesion_params *p;
+    float dt;
+    uint32_t *out_affected;
+    const char *tag = "cohesion", *things = "parameters";
+    WsCohesionArgs args{};
+    const char *refuse() const { return cohesion_refusal(p, dt); }
+    uint32_t partial[WS_COHESION_SLOTS * WS_COHESION_SLOT_WORDS];
+    ws_status prepare(ws_handle *h, const WsGathered *g)  // the stage, then the partial counters if the caller asks for the count
+    {
+        ws_status st = cohesion_prepare(h, g, p, dt, &args);
+        if (st || !out_affected) return st;
+        st = scratch_zeroed(h, h->force_cnt, sizeof partial, "cohesion counters");  // (the emitters' scratch, grown)
+        args.affected = h->force_cnt.p;
+        return st;
+    }
+    template <class M>
+    void mix(M m, bool valid) const
+    {
+        m(&dt, 4);
+        if (valid) m(p, sizeof *p);
+    }
+    hipError_t fetch(ws_handle *h)
+    {
+        if (!out_affected) return hipSuccess;
+        const hipError_t e = copy_now(h, partial, h->force_cnt.p, sizeof partial, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return e;
+        uint32_t total = 0;
+        for (uint32_t s = 0; s < WS_COHESION_SLOTS; s++) total += partial[s * WS_COHESION_SLOT_WORDS];
+        *out_affected = total;
+        return hipSuccess;
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+ws_status ws_apply_cohesion(ws_handle *h, const ws_cohesion_params *p, float dt, uint32_t *out_affected)
+{
+    CohesionCall call{p, dt, out_affected};
     return edit_fluid(h, call);
 }
 
@@ -1473,7 +1528,7 @@ struct SolidsCall {
     unsigned long long sums[WS_MAX_SOLIDS * WS_SOLID_WORDS];  // fetch()'s copy of the accumulator words
     bool react() const { return out_contacts || out_impulse || out_angular; }
     const char *refuse() const { return solids_refusal(s, k); }
-    ws_status prepare(ws_handle *h)  // the solids' bytes as given, and each one's reach
+    ws_status prepare(ws_handle *h, const WsGathered *)  // the solids' bytes as given, and each one's reach
     {
         memcpy(args.ss.e, s, (size_t)k * sizeof(ws_solid));
         for (uint32_t e = 0; e < k; e++) args.ss.reach2[e] = solids_reach2(s[e]);
@@ -1609,7 +1664,7 @@ struct VolumesCall {
     unsigned long long sums[WS_MAX_VOLUME_POSES * WS_SOLID_WORDS];  // fetch()'s copy of the accumulator words
     bool react() const { return out_contacts || out_impulse || out_angular; }
     const char *refuse() const { return volumes_refusal(owner, v, k); }
-    ws_status prepare(ws_handle *h)  // the slots as they are now, the poses' bytes as given, and each one's reach
+    ws_status prepare(ws_handle *h, const WsGathered *)  // the slots as they are now, the poses' bytes as given, and each one's reach
     {
         memcpy(args.vs.vol, h->volume_desc, sizeof args.vs.vol);
         memcpy(args.vs.e, v, (size_t)k * sizeof(ws_volume_pose));

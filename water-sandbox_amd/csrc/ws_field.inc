@@ -26,7 +26,7 @@ void free_field_cells(ws_handle *h)
 void free_field(ws_handle *h)
 {
     auto &F = h->field;
-    release_all(F.body);
+    release_all(F.body, F.cnd, F.crec, F.cst, F.cnb);
     free_field_cells(h);
     release_all(F.xyz, F.keys, F.tmp, F.perm, F.spos, F.q, F.rho, F.grad, F.code, F.vbase, F.bcnt, F.bstart, F.bstate, F.tri,
                 F.mxyz, F.mnrm, F.vxyz, F.vpos, F.svel, F.wnrm, F.wst, F.wout, F.wpt, F.wnb, F.wcnt, F.woff, F.wstate, F.cxyz,
@@ -758,6 +758,93 @@ ws_status step_whitewater(ws_handle *h, const ws_whitewater_step_params *p, cons
     return field_finish(h, {{out_xyz, dp, M * 12}, {out_vel, dv, M * 12}, {out_life, dl, M * 4}, {out_class, dc, M}});
 }
 
+// ---- surface tension and XSPH (include/wsfluid.h defines the stage and the edit) ----------------------------------------
+// the argument errors of ws_read_cohesion / ws_apply_cohesion (nullptr = acceptable)
+const char *cohesion_refusal(const ws_cohesion_params *p, float dt)
+{
+    if (!p) return "cohesion: p is NULL";
+    if (p->reserved != 0u) return "cohesion: reserved must be 0";
+    if (ws_bad_float(p->cohesion) || ws_bad_float(p->curvature) || ws_bad_float(p->xsph) || ws_bad_float(p->rest_density))
+        return "cohesion: the parameters must be finite and at most 1e15 in magnitude";
+    if (p->cohesion < 0.f || p->curvature < 0.f || p->rest_density < 0.f) return "cohesion: cohesion, curvature and rest_density must be >= 0";
+    if (!(p->xsph >= 0.f && p->xsph <= 1.f)) return "cohesion: xsph must lie in [0, 1]";
+    if (ws_bad_float(dt) || !(dt > 0.f)) return "cohesion: dt must be finite, > 0 and at most 1e15";
+    return nullptr;
+}
+
+// The per-particle stage over the binned positions and velocities into F.crec, by id: {dv, count}, and with `outputs`
+// (ws_read_cohesion) {normal, density} behind them, split into F.cst (the normals, the densities, then dv: 3 n, n and 3 n
+// floats) and F.cnb.  The spline's constants are the header's float operations, in its order.
+ws_status cohesion_stage(ws_handle *h, const FieldCtx &c, const ws_cohesion_params *p, float dt, bool outputs)
+{
+    auto &F = h->field;
+    const size_t n = c.n;
+    ws_status st;
+    if ((st = F.cnd.grow(h, n * 16, kFieldScratch))) return st;
+    if ((st = F.crec.grow(h, n * (outputs ? 32 : 16), kFieldScratch))) return st;
+    if (outputs && (st = F.cst.grow(h, n * 28, kFieldScratch))) return st;
+    if (outputs && (st = F.cnb.grow(h, n * 4, kFieldScratch))) return st;
+    const float hh = c.d.h, h3 = (hh * hh) * hh, h6 = h3 * h3, h9 = h6 * h3;
+    const WsCohesion k = {p->cohesion, p->curvature, p->xsph, p->rest_density == 0.0f ? c.d.target_density : p->rest_density, dt,
+                          32.0f / (3.14159274f * h9), h6 * 0.015625f};
+    wsk_cohesion_stage(h->stream, c.d, F.start.p, F.spos.p, F.svel.p, F.cnd.p, k, F.crec.p, outputs ? F.crec.p + n : nullptr, (uint32_t)n);
+    if (outputs) wsk_cohesion_unpack(h->stream, F.crec.p, F.crec.p + n, F.cst.p, F.cst.p + 3 * n, F.cst.p + 4 * n, F.cnb.p, (uint32_t)n);
+    HIP_TRY(h, hipGetLastError());
+    return WS_OK;
+}
+
+ws_status read_cohesion(ws_handle *h, const ws_cohesion_params *p, float dt, float *out_nrm, float *out_rho, float *out_dv,
+                        uint32_t *out_nb)
+{
+    FieldCtx c;
+    c.want = out_nrm || out_rho || out_dv || out_nb;
+    ws_status st = field_enter(h, c, "cohesion", "cohesion: every output is NULL");
+    if (st) return st;
+    st = field_source(h, &c, FIELD_POSITIONS_AND_VELOCITIES, [&]() -> ws_status {
+        const char *why = cohesion_refusal(p, dt);
+        return why ? fail(h, WS_ERR_INVALID_ARG, why) : WS_OK;
+    });
+    if (st || c.contributed) return st;
+    if ((st = field_bin_particles(h, c))) return st;
+    if ((st = cohesion_stage(h, c, p, dt, true))) return st;
+    auto &F = h->field;
+    const size_t n = c.n;
+    return field_finish(h, {{out_nrm, F.cst.p, n * 12}, {out_rho, F.cst.p + 3 * n, n * 4}, {out_dv, F.cst.p + 4 * n, n * 12},
+                            {out_nb, F.cnb.p, n * 4}});
+}
+
+// ws_apply_cohesion's prepare(): the stage on the handle's stream, and what the edit kernel reads of it.  A single handle
+// (g == nullptr) takes positions and velocities from `cur`, as every field call; a slab handle takes them from the state
+// records its edit route has ALREADY gathered, unpacked by id on the global grid the slabs' field calls bin on -- no
+// further collective call.  The arguments have passed cohesion_refusal.
+ws_status cohesion_prepare(ws_handle *h, const WsGathered *g, const ws_cohesion_params *p, float dt, WsCohesionArgs *args)
+{
+    auto &F = h->field;
+    FieldCtx c;
+    c.want = true;
+    ws_status st;
+    if (!g) {
+        if ((st = field_source(h, &c, FIELD_POSITIONS_AND_VELOCITIES, []() { return WS_OK; }))) return st;
+    } else {
+        c.inputs = FIELD_POSITIONS_AND_VELOCITIES;
+        c.n = h->slab->n_global;
+        if ((st = global_grid(&h->params, c.n, &c.d))) return fail(h, st, g_create_error.c_str());
+        const size_t n = c.n;
+        if ((st = field_alloc(h, c.n, c.d.ncells))) return st;
+        if ((st = F.vxyz.grow(h, n * 12, kFieldScratch))) return st;
+        if ((st = F.svel.grow(h, n * 16, kFieldScratch))) return st;
+        if ((st = F.vpos.grow(h, n * 12, kFieldScratch))) return st;
+        wsk_state_split(h->stream, g->recs, g->cnt, g->world, g->max_n, g->stride_words, c.n, F.vpos.p, F.vxyz.p);
+        c.pos = F.vpos.p;
+    }
+    if ((st = field_bin_particles(h, c))) return st;
+    if ((st = cohesion_stage(h, c, p, dt, false))) return st;
+    args->dvc = F.crec.p;
+    args->affected = nullptr;
+    args->n = c.n;
+    return WS_OK;
+}
+
 // ---- bodies in the fluid (include/wsfluid.h defines a sample's terms and the order of a body's sums) -------------------
 ws_status body_check(ws_handle *h, const ws_body_params *p, const float *xyz, const float *vel, const float *vol, uint32_t m,
                      const uint32_t *body_start, const float *centre, uint32_t nb)
@@ -1011,6 +1098,27 @@ ws_status ws_step_whitewater(ws_handle *h, const ws_whitewater_step_params *p, c
 {
     if (!h) return WS_ERR_INVALID_ARG;
     return step_whitewater(h, p, xyz, velocity, life, m, out_xyz, out_velocity, out_life, out_class);
+}
+
+// ======================================================================================
+// surface tension and XSPH: the read-only stage (ws_apply_cohesion is an edit: ws_api.cpp)
+// ======================================================================================
+ws_status ws_default_cohesion_params(ws_cohesion_params *out)
+{
+    if (!out) return WS_ERR_INVALID_ARG;
+    out->cohesion = 1.0f;
+    out->curvature = 1.0f;
+    out->xsph = 0.1f;
+    out->rest_density = 0.0f;
+    out->reserved = 0u;
+    return WS_OK;
+}
+
+ws_status ws_read_cohesion(ws_handle *h, const ws_cohesion_params *p, float dt, float *out_normal, float *out_density,
+                           float *out_dv, uint32_t *out_neighbours)
+{
+    if (!h) return WS_ERR_INVALID_ARG;
+    return read_cohesion(h, p, dt, out_normal, out_density, out_dv, out_neighbours);
 }
 
 // ======================================================================================

@@ -316,6 +316,12 @@ struct WsField {
     WsScratch<float4> wnrm;
     WsScratch<float> wst, wout, wpt;
     WsScratch<uint32_t> wnb, wcnt, woff, wstate;
+    // surface tension and XSPH (ws_read_cohesion, ws_apply_cohesion): {normal, density} in spos' order; the stage by id
+    // as 16-byte records ({dv, count}, then for the read {normal, density}: n float4 each); the read's outputs (normal
+    // x 3, density, dv x 3 as one array of 7 n floats; the neighbour counts)
+    WsScratch<float4> cnd, crec;
+    WsScratch<float> cst;
+    WsScratch<uint32_t> cnb;
     // bodies (ws_body_forces), one array of words: the chunk table (4 per chunk) and the chunks' partial sums (8 per chunk),
     // the bodies' first chunks (nb + 1), the samples (xyz, velocity: 3 floats, volume: 1) and the centres (3 per body), the
     // per-sample results (force: 3, fraction: 1) and the per-body ones (force, torque: 3, volume, wet count: 1)
@@ -595,7 +601,26 @@ struct WsVolumeArgs {
     bool outputs() const { return sums != nullptr; }
 };
 static_assert(WS_MAX_VOLUME_POSES == WS_MAX_SOLIDS, "the poses' sums are the solids' accumulator rows");
-// Args = WsForceArgs, WsSolidArgs or WsVolumeArgs.  The first edits `cur` in place and re-bins it (what bin_current leaves: cid, the
+// Cohesion (ws_apply_cohesion): what the neighbour stage left by id -- {dv, the contributing-neighbour count (bits)}, one
+// float4 per particle of the n the stage saw (a record with an id beyond them is left alone) -- and the device words the
+// kernel adds the affected particles to, or nullptr: WS_COHESION_SLOTS partial counts, WS_COHESION_SLOT_WORDS words (one
+// cache line) apart, which the host sums.
+#define WS_COHESION_SLOTS 64u
+#define WS_COHESION_SLOT_WORDS 16u
+struct WsCohesionArgs {
+    const float4 *dvc;
+    uint32_t *affected;
+    uint32_t n;
+    bool outputs() const { return affected != nullptr; }
+};
+// The state records a slab handle's edit route has gathered ({id, pos, vel, pred}: 10 words each), as an edit's prepare()
+// sees them: rank r's min(cnt[4 r], max_n) records at recs + r * stride_words.
+struct WsGathered {
+    const uint32_t *recs, *cnt;
+    uint32_t world, max_n;
+    size_t stride_words;
+};
+// Args = WsForceArgs, WsSolidArgs, WsVolumeArgs or WsCohesionArgs.The first edits `cur` in place and re-bins it (what bin_current leaves: cid, the
 // record's cell id, count, rank); the second edits the gathered {id, pos, vel, pred} records of slab handles (d: the global
 // grid, its container and damping).
 template <class Args>
@@ -668,6 +693,20 @@ void wsk_whitewater_spawn(hipStream_t s, const WsWhiteEmit &e, const float *pxyz
                           const uint32_t *off, float *out_xyz, float *out_vel, float *out_life, uint32_t *out_src, uint32_t n);
 void wsk_whitewater_step(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, const float4 *svel, bool ieee,
                          const WsWhiteStep &sp, float *pts, float *vel, float *life, uint8_t *cls, uint32_t m);
+// surface tension and XSPH (ws_read_cohesion / ws_apply_cohesion) over the velocity field's binning: the call's strengths,
+// rho_0, dt and the two spline constants of the header (kc, h664), and the stage -- pass A into snd ({normal, density} in
+// spos' order), pass B by id into dvc ({dv, count}) and, unless nullptr, nrho ({normal, density}); wsk_cohesion_unpack:
+// the two as the four output arrays of ws_read_cohesion.  wsk_state_split: the gathered state records of slab handles as
+// positions and velocities by id.
+struct WsCohesion {
+    float cohesion, curvature, xsph, rho0, dt, kc, h664;
+};
+void wsk_cohesion_stage(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, const float4 *svel,
+                        float4 *snd, const WsCohesion &k, float4 *dvc, float4 *nrho, uint32_t n);
+void wsk_cohesion_unpack(hipStream_t s, const float4 *dvc, const float4 *nrho, float *normal, float *rho, float *dv, uint32_t *nb,
+                         uint32_t n);
+void wsk_state_split(hipStream_t s, const uint32_t *all, const uint32_t *cnt, uint32_t world, uint32_t max_n, size_t stride_words,
+                     uint32_t n_global, float *pos, float *vel);
 // bodies (ws_body_forces) over the velocity field's binning.  chunks: nchunks x {body, first sample, samples (1 .. the
 // workgroup size), 0}, a body's chunks consecutive and in order; cstart: the first chunk of every body, nb + 1 entries;
 // part: 8 words per chunk (written, then read by the finishing kernel).  One workgroup per chunk sweeps the field at the

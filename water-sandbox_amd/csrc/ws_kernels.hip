@@ -922,6 +922,39 @@ struct EditVolumes {
     __device__ void flush(const unsigned long long *acc) const { solids_flush(acc, a.k, a.sums); }
 };
 
+// ws_apply_cohesion: the neighbour stage (k_cohesion_normals / k_cohesion_stage, below the whitewater block) has left dv
+// and the contributing-neighbour count c BY ID, as one float4 each; the edit adds dv[id] where c[id] > 0 -- an unaffected particle keeps its
+// bits, a -0 included.  The id rides in the w lane of p (cur.pos(i).w; the record's id word).  COUNTS: one ballot per
+// wave and at most one atomic, as forces_eval<COUNTS>, into a.affected's slots.
+template <bool COUNTS>
+struct EditCohesion {
+    static constexpr bool moves = false;
+    static constexpr uint32_t acc_words = 0;
+    WsCohesionArgs a;
+    __device__ bool eval(const WsDev &, bool active, float4 &p, float4 &v, unsigned long long *) const
+    {
+        const uint32_t id = __float_as_uint(p.w);
+        float4 r = make_float4(0.f, 0.f, 0.f, 0.f);  // {dv, c (bits)}: one 16-byte gather per particle
+        if (active && id < a.n) r = a.dvc[id];
+        const bool hit = __float_as_uint(r.w) > 0u;
+        if constexpr (COUNTS) {
+            const uint32_t k = (uint32_t)__popcll(__ballot(hit));
+            // (nearly every wave has something to add: to one word that is 65 536 atomics in a row at 4 M particles --
+            // measured 757 us, ten times the rest of the pass -- so a wave adds to one of WS_COHESION_SLOTS words, a cache
+            // line apart, and the host sums them)
+            const uint32_t slot = ((blockIdx.x * WS_BLOCK + threadIdx.x) >> 6) % WS_COHESION_SLOTS;
+            if (k && (threadIdx.x & 63u) == 0u) atomicAdd(a.affected + slot * WS_COHESION_SLOT_WORDS, k);
+        }
+        if (hit) {
+            v.x = v.x + r.x;
+            v.y = v.y + r.y;
+            v.z = v.z + r.z;
+        }
+        return hit;
+    }
+    __device__ void flush(const unsigned long long *) const {}
+};
+
 // what a launcher's argument struct becomes on the device: WITH = whether the call wants its outputs (COUNTS / REACT)
 template <class With>
 EditForces<With::value> edit_of(const WsForceArgs &a, With) { return {a}; }
@@ -929,6 +962,8 @@ template <class With>
 EditSolids<With::value> edit_of(const WsSolidArgs &a, With) { return {a}; }
 template <class With>
 EditVolumes<With::value> edit_of(const WsVolumeArgs &a, With) { return {a}; }
+template <class With>
+EditCohesion<With::value> edit_of(const WsCohesionArgs &a, With) { return {a}; }
 
 template <class Edit>
 __device__ __forceinline__ void edit_begin(unsigned long long *acc)
@@ -1001,7 +1036,8 @@ __global__ void __launch_bounds__(WS_BLOCK) k_edit_records(WsDev d, uint32_t *__
     float *f = state_record(all, stride_words, r, t);
     float4 p = make_float4(0.f, 0.f, 0.f, 0.f), v = p;
     if (active) {
-        p = make_float4(f[0], f[1], f[2], 0.f);
+        // (w: the record's id word, where cur.pos(i) has it)
+        p = make_float4(f[0], f[1], f[2], __uint_as_float(reinterpret_cast<const uint32_t *>(f)[-1]));
         v = make_float4(f[3], f[4], f[5], 0.f);
     }
     const bool changed = edit.eval(d, active, p, v, acc);
@@ -1041,6 +1077,7 @@ void wsk_edit_current(hipStream_t s, const WsDev &d, WsSoA cur, uint32_t *cid, u
 template void wsk_edit_current(hipStream_t, const WsDev &, WsSoA, uint32_t *, uint32_t *, const WsForceArgs &);
 template void wsk_edit_current(hipStream_t, const WsDev &, WsSoA, uint32_t *, uint32_t *, const WsSolidArgs &);
 template void wsk_edit_current(hipStream_t, const WsDev &, WsSoA, uint32_t *, uint32_t *, const WsVolumeArgs &);
+template void wsk_edit_current(hipStream_t, const WsDev &, WsSoA, uint32_t *, uint32_t *, const WsCohesionArgs &);
 
 template <class Args>
 void wsk_edit_records(hipStream_t s, const WsDev &d, uint32_t *all, const uint32_t *cnt, uint32_t world, uint32_t max_n,
@@ -1056,6 +1093,7 @@ void wsk_edit_records(hipStream_t s, const WsDev &d, uint32_t *all, const uint32
 template void wsk_edit_records(hipStream_t, const WsDev &, uint32_t *, const uint32_t *, uint32_t, uint32_t, size_t, const WsForceArgs &);
 template void wsk_edit_records(hipStream_t, const WsDev &, uint32_t *, const uint32_t *, uint32_t, uint32_t, size_t, const WsSolidArgs &);
 template void wsk_edit_records(hipStream_t, const WsDev &, uint32_t *, const uint32_t *, uint32_t, uint32_t, size_t, const WsVolumeArgs &);
+template void wsk_edit_records(hipStream_t, const WsDev &, uint32_t *, const uint32_t *, uint32_t, uint32_t, size_t, const WsCohesionArgs &);
 
 // ---------------------------------------------------------------------------------
 // smoothing kernels, assets/simulation.wgsl:93-117 (evaluation order as written)
@@ -3768,6 +3806,138 @@ void wsk_whitewater_stage(hipStream_t s, const WsDev &d, const uint32_t *start, 
     hipLaunchKernelGGL(k_whitewater_normals, grid, block, 0, s, d, start, spos, snrm, n);
     hipLaunchKernelGGL(k_whitewater_stage, grid, block, 0, s, d, start, spos, svel, snrm, trapped, crest, align, energy, normal,
                        nb, n);
+}
+
+// ---------------------------------------------------------------------------------
+// surface tension and XSPH smoothing (ws_read_cohesion / ws_apply_cohesion; never inside ws_step)
+//
+// include/wsfluid.h pins every operation; IEEE arithmetic whatever the handle's flags.  The whitewater stage's shape: two
+// kernels, one lane per particle in the sampler's cell order, each one field_sweep.  k_cohesion_normals (pass A): the
+// density sampler's sums at x_i in their IEEE form, stored as ONE float4 {n_i = h g_i / rho_i, rho_i} beside spos, so that
+// pass B fetches a candidate's normal and density with one 16-byte load.  k_cohesion_stage (pass B): per contributing
+// candidate three 16-byte loads through the caches (position, velocity, {normal, density}), no LDS; the results scattered
+// by id as 16-byte records -- {dv, count} (what the edit gathers, EditCohesion above) and, for ws_read_cohesion only,
+// {normal, density} -- which k_cohesion_unpack, a streaming pass, splits into the call's four output arrays.
+// ---------------------------------------------------------------------------------
+__global__ void __launch_bounds__(WS_BLOCK) k_cohesion_normals(WsDev d, const uint32_t *__restrict__ start,
+                                                               const float4 *__restrict__ spos, float4 *__restrict__ snd,
+                                                               uint32_t n)
+{
+    const uint32_t i = blockIdx.x * WS_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const FieldAcc g = field_sweep<true, true>(d, start, FieldIso{spos}, spos[i]);
+    snd[i] = make_float4((d.h * g.gx) / g.rho, (d.h * g.gy) / g.rho, (d.h * g.gz) / g.rho, g.rho);  // (rho has i's own term: > 0)
+}
+
+// Pass B's accumulator and candidate source: positions, velocities and {normal, density} in cell order, the query
+// particle's own velocity and {normal, density}, and the call's constants.
+struct CohesionAcc {
+    float ax, ay, az, xx, xy, xz;
+    uint32_t c;
+};
+struct FieldCohesion {
+    const float4 *__restrict__ spos;
+    const float4 *__restrict__ svel;
+    const float4 *__restrict__ snd;
+    float4 vi, ni;
+    WsCohesion k;
+    __device__ __forceinline__ float4 at(uint32_t j) const { return spos[j]; }
+    template <bool IEEE, bool GRAD>
+    __device__ __forceinline__ void pair(const WsDev &d, uint32_t j, float ex, float ey, float ez, float d2, CohesionAcc &a) const
+    {
+        const float dst = sqrtf(d2);
+        if (!(dst > 0.f)) return;  // i itself, a coincident particle
+        const float xx = -ex / dst, xy = -ey / dst, xz = -ez / dst;
+        const float4 nj = snd[j], vj = svel[j];
+        const float q = 2.f / (ni.w + nj.w);
+        const float K = k.rho0 * q;
+        const float t = d.h - dst;
+        const float pp = ((t * t) * t) * ((dst * dst) * dst);
+        const float s = 2.f * dst > d.h ? pp : 2.f * pp - k.h664;
+        const float fc = k.cohesion * (k.kc * s);
+        a.ax = a.ax - K * (fc * xx + k.curvature * (ni.x - nj.x));
+        a.ay = a.ay - K * (fc * xy + k.curvature * (ni.y - nj.y));
+        a.az = a.az - K * (fc * xz + k.curvature * (ni.z - nj.z));
+        const float w = sk_density(d, dst);
+        a.xx = a.xx + ((vj.x - vi.x) * w) * q;
+        a.xy = a.xy + ((vj.y - vi.y) * w) * q;
+        a.xz = a.xz + ((vj.z - vi.z) * w) * q;
+        a.c++;
+    }
+};
+
+// by id: dvc[n] = {dv, c (bits)}, and if wanted nrho[n] = {n_i, rho_i}
+__global__ void __launch_bounds__(WS_BLOCK) k_cohesion_stage(WsDev d, const uint32_t *__restrict__ start,
+                                                             const float4 *__restrict__ spos, const float4 *__restrict__ svel,
+                                                             const float4 *__restrict__ snd, WsCohesion k,
+                                                             float4 *__restrict__ dvc, float4 *__restrict__ nrho, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * WS_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const float4 o = spos[i], v = svel[i], nd = snd[i];
+    const size_t id = __float_as_uint(o.w);
+    const FieldCohesion src = {spos, svel, snd, v, nd, k};
+    const CohesionAcc a = field_sweep<true, false, FieldCohesion, CohesionAcc>(d, start, src, o);
+    float4 out = make_float4(0.f, 0.f, 0.f, __uint_as_float(a.c));
+    if (a.c) {
+        out.x = k.dt * a.ax + k.xsph * a.xx;
+        out.y = k.dt * a.ay + k.xsph * a.xy;
+        out.z = k.dt * a.az + k.xsph * a.xz;
+    }
+    dvc[id] = out;
+    if (nrho) nrho[id] = nd;
+}
+
+void wsk_cohesion_stage(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, const float4 *svel,
+                        float4 *snd, const WsCohesion &k, float4 *dvc, float4 *nrho, uint32_t n)
+{
+    const dim3 grid(cdiv(n, WS_BLOCK)), block(WS_BLOCK);
+    hipLaunchKernelGGL(k_cohesion_normals, grid, block, 0, s, d, start, spos, snd, n);
+    hipLaunchKernelGGL(k_cohesion_stage, grid, block, 0, s, d, start, spos, svel, snd, k, dvc, nrho, n);
+}
+
+// ws_read_cohesion's outputs from the stage's records, by id: normal[3 n], rho[n], dv[3 n], nb[n]
+__global__ void __launch_bounds__(WS_BLOCK) k_cohesion_unpack(const float4 *__restrict__ dvc, const float4 *__restrict__ nrho,
+                                                              float *__restrict__ normal, float *__restrict__ rho,
+                                                              float *__restrict__ dv, uint32_t *__restrict__ nb, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * WS_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const float4 a = dvc[i], b = nrho[i];
+    field_store3(normal, i, b);
+    rho[i] = b.w;
+    field_store3(dv, i, a);
+    nb[i] = __float_as_uint(a.w);
+}
+
+void wsk_cohesion_unpack(hipStream_t s, const float4 *dvc, const float4 *nrho, float *normal, float *rho, float *dv, uint32_t *nb,
+                         uint32_t n)
+{
+    hipLaunchKernelGGL(k_cohesion_unpack, dim3(cdiv(n, WS_BLOCK)), dim3(WS_BLOCK), 0, s, dvc, nrho, normal, rho, dv, nb, n);
+}
+
+// The gathered state records of slab handles (state_record) as positions and velocities by id: what field_source leaves
+// on a single handle.  A record whose id is out of range is skipped.
+__global__ void __launch_bounds__(WS_BLOCK) k_state_split(const uint32_t *__restrict__ all, const uint32_t *__restrict__ cnt,
+                                                          uint32_t max_n, size_t stride_words, uint32_t n_global,
+                                                          float *__restrict__ pos, float *__restrict__ vel)
+{
+    const uint32_t t = blockIdx.x * WS_BLOCK + threadIdx.x, r = blockIdx.y;
+    if (t >= min(cnt[4 * r], max_n)) return;
+    const uint32_t *rec = all + (size_t)r * stride_words + (size_t)t * 10u;
+    const size_t id = rec[0];
+    if (id >= n_global) return;
+    const float *f = reinterpret_cast<const float *>(rec + 1);
+    field_store3(pos, id, make_float4(f[0], f[1], f[2], 0.f));
+    field_store3(vel, id, make_float4(f[3], f[4], f[5], 0.f));
+}
+
+void wsk_state_split(hipStream_t s, const uint32_t *all, const uint32_t *cnt, uint32_t world, uint32_t max_n, size_t stride_words,
+                     uint32_t n_global, float *pos, float *vel)
+{
+    if (!max_n) return;
+    hipLaunchKernelGGL(k_state_split, dim3(cdiv(max_n, WS_BLOCK), world), dim3(WS_BLOCK), 0, s, all, cnt, max_n, stride_words,
+                       n_global, pos, vel);
 }
 
 // the counter-based random numbers of the header: pure 32-bit integer arithmetic

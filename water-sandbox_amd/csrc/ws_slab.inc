@@ -1118,7 +1118,10 @@ ws_status slab_edit_gathered(ws_handle *h, Call &call)
     if (st) return st;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     const char *why = call.refuse();
-    const ws_status st_cnt = !why ? call.prepare(h) : WS_OK;  // (this rank's alone: it refuses for all)
+    // (this rank's alone: it refuses for all.  An edit that looks at neighbours runs its stage here, on the records just
+    // gathered and with no collective call of its own: a rank that refused skips it and keeps nobody waiting.)
+    const WsGathered gathered = {slab_gathered(S), S->cnt_all.p, W, max_n, stride};
+    const ws_status st_cnt = !why ? call.prepare(h, &gathered) : WS_OK;
     uint32_t word = 2166136261u;  // FNV-1a
     call.mix([&word](const void *p, size_t bytes) {
         for (size_t b = 0; b < bytes; b++) word = (word ^ static_cast<const uint8_t *>(p)[b]) * 16777619u;

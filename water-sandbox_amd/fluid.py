@@ -56,7 +56,7 @@ ABI_SYMBOLS = [
     "ws_read_velocities", "ws_sample_velocity_grid", "ws_sample_velocity_points", "ws_advect_points",
     "ws_default_whitewater_emit_params", "ws_default_whitewater_step_params", "ws_read_whitewater", "ws_emit_whitewater",
     "ws_step_whitewater", "ws_apply_forces", "ws_default_body_params", "ws_body_forces", "ws_collide_solids",
-    "ws_volume_upload", "ws_collide_volumes",
+    "ws_volume_upload", "ws_collide_volumes", "ws_default_cohesion_params", "ws_read_cohesion", "ws_apply_cohesion",
 ]
 
 
@@ -210,6 +210,18 @@ class WsBodyParams(C.Structure):
     ]
 
 
+class WsCohesionParams(C.Structure):
+    """ws_cohesion_params: the strengths of ws_read_cohesion / ws_apply_cohesion (include/wsfluid.h)."""
+
+    _fields_ = [
+        ("cohesion", C.c_float),
+        ("curvature", C.c_float),
+        ("xsph", C.c_float),
+        ("rest_density", C.c_float),
+        ("reserved", C.c_uint32),
+    ]
+
+
 class WsCamera(C.Structure):
     """ws_camera: pixel (i, j) looks along forward + u * right + w * up from eye (include/wsfluid.h)."""
 
@@ -329,6 +341,9 @@ def bind_library(path):
     L.ws_emit_whitewater.argtypes = [vp, vp, u32, vp, vp, vp, vp, vp]
     L.ws_step_whitewater.argtypes = [vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]
     L.ws_apply_forces.argtypes = [vp, vp, u32, C.c_float, vp]
+    L.ws_default_cohesion_params.argtypes = [vp]
+    L.ws_read_cohesion.argtypes = [vp, vp, C.c_float, vp, vp, vp, vp]
+    L.ws_apply_cohesion.argtypes = [vp, vp, C.c_float, vp]
     L.ws_default_body_params.argtypes = [vp]
     L.ws_collide_solids.argtypes = [vp, vp, u32, vp, vp, vp]
     L.ws_volume_upload.argtypes = [vp, u32, vp, vp, vp, vp]
@@ -603,6 +618,31 @@ def apply_forces(L, h, check, forces, dt, counts=True):
     out = np.zeros(max(len(forces), 1), np.uint32) if counts else None
     check(L.ws_apply_forces(h, C.byref(arr), len(forces), dt, out.ctypes.data if counts else None))
     return out[:len(forces)] if counts else None
+
+
+def cohesion_params(**fields):
+    """ws_default_cohesion_params with the given fields replaced (cohesion, curvature, xsph, rest_density)."""
+    return _whitewater_params(WsCohesionParams, load_library().ws_default_cohesion_params, fields)
+
+
+def read_cohesion(L, h, check, n, params, dt, want=True):
+    """ws_read_cohesion: a dict of the stage by id -- normal (n, 3) float32, density (n,), dv (n, 3), neighbours (n,)
+    uint32 (include/wsfluid.h has the definition).  want=False (slab handles): contribute, return None."""
+    if not want:
+        check(L.ws_read_cohesion(h, C.byref(params), dt, None, None, None, None))
+        return None
+    out = dict(normal=np.empty((n, 3), np.float32), density=np.empty(n, np.float32), dv=np.empty((n, 3), np.float32),
+               neighbours=np.empty(n, np.uint32))
+    check(L.ws_read_cohesion(h, C.byref(params), dt, *(out[k].ctypes.data for k in ("normal", "density", "dv", "neighbours"))))
+    return out
+
+
+def apply_cohesion(L, h, check, params, dt, count=True):
+    """ws_apply_cohesion: v += dv of the stage on every particle that has a contributing neighbour.  Returns how many
+    particles were affected, or None with count=False (a single handle then only enqueues)."""
+    out = C.c_uint32(0)
+    check(L.ws_apply_cohesion(h, C.byref(params), dt, C.byref(out) if count else None))
+    return int(out.value) if count else None
 
 
 def solid(kind, centre, size, rot=(1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0), hollow=False, velocity=(0.0, 0.0, 0.0),
@@ -1021,6 +1061,17 @@ class FluidWorker:
         to the velocities as one Euler step of dt.  The per-emitter counts of affected particles, or None with
         counts=False (the call then only enqueues)."""
         return apply_forces(self._L, self._h, self._check, forces, dt, counts)
+
+    def read_cohesion(self, params, dt):
+        """The surface-tension and XSPH stage of every fluid particle, by id, read-only: params = cohesion_params(...).
+        A dict of normal (n, 3), density (n,), dv (n, 3) -- what apply_cohesion would add -- and neighbours (n,)."""
+        return read_cohesion(self._L, self._h, self._check, self.n, params, dt)
+
+    def apply_cohesion(self, params, dt, count=True):
+        """Surface tension (Akinci et al. 2013) and XSPH velocity smoothing between two steps: params =
+        cohesion_params(...), applied to the velocities as one explicit step of dt.  The number of affected particles,
+        or None with count=False (the call then only enqueues)."""
+        return apply_cohesion(self._L, self._h, self._check, params, dt, count)
 
     def collide_solids(self, solids, reaction=True):
         """Put solid things in the water between two steps: solids = solid(...) or a list of up to 16.  Particles nearer

@@ -423,6 +423,15 @@ class FluidWorker {
         return r;
     }
 
+    // Surface tension and XSPH velocity smoothing between two steps (include/wsfluid.h ws_apply_cohesion): one explicit
+    // step of dt on the velocities.  Returns the number of particles that had a contributing neighbour.
+    uint32_t apply_cohesion(const ws_cohesion_params &p, float dt)
+    {
+        uint32_t affected = 0;
+        check(ws_apply_cohesion(h_, &p, dt, &affected));
+        return affected;
+    }
+
     std::vector<float> read_speeds()
     {
         std::vector<float> out(n_);

@@ -450,6 +450,15 @@ class SlabWorker:
         emitters); the counts are global.  counts=False: this rank applies without asking for them (None)."""
         return fluid.apply_forces(self._L, self._h, self._check, forces, dt, counts)
 
+    def read_cohesion(self, params, dt, want=True):
+        """FluidWorker.read_cohesion of the GLOBAL particle set (COLLECTIVE); want=False: only contribute (None)."""
+        return fluid.read_cohesion(self._L, self._h, self._check, self.n_global, params, dt, want)
+
+    def apply_cohesion(self, params, dt, count=True):
+        """FluidWorker.apply_cohesion on the GLOBAL particle set (COLLECTIVE: every rank makes the same call with the same
+        parameters); the count is global.  count=False: this rank applies without asking for it (None)."""
+        return fluid.apply_cohesion(self._L, self._h, self._check, params, dt, count)
+
     def collide_solids(self, solids, reaction=True):
         """FluidWorker.collide_solids on the GLOBAL particle set (COLLECTIVE: every rank makes the same call with the same
         solids); the outputs are global.  reaction=False: this rank applies without asking for them (None)."""
