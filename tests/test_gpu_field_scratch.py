@@ -18,7 +18,7 @@ STEPS = 20
 SIZES = (65, 4097, 1)  # one per pass: grow, grow again, reuse while larger than needed
 KINDS = ("density_grid", "density_points", "aniso_grid", "aniso_points", "anisotropy", "surface", "aniso_surface", "cast_rays",
          "cast_camera", "velocity_grid", "velocity_points", "advect_points", "read_whitewater", "emit_whitewater",
-         "step_whitewater", "read_velocities")
+         "step_whitewater", "read_velocities", "read_cohesion", "body_forces")
 ORDER = tuple(KINDS[i] for i in np.random.default_rng(16).permutation(len(KINDS)))
 # the passes of the mixed run: the shuffled list, the same list reversed, the shuffled list again
 PASSES = tuple((kind, size) for order, size in zip((ORDER, ORDER[::-1], ORDER), SIZES) for kind in order)
@@ -122,8 +122,16 @@ class _Scene:
             return flat(out)
         if kind == "step_whitewater":
             return flat(x.step_whitewater(ws.fluid.whitewater_step_params(), q["pts"], q["vel"], q["life"], **kw))
-        assert kind == "read_velocities"
-        return flat(x.read_velocities(**kw))
+        if kind == "read_velocities":
+            return flat(x.read_velocities(**kw))
+        if kind == "read_cohesion":
+            return flat(x.read_cohesion(ws.fluid.cohesion_params(), F32(1.0 / 60.0), **kw))
+        assert kind == "body_forces"
+        # the m samples as three bodies, each about the mean of its samples (an empty body about the origin)
+        start = np.array([0, m // 3, 2 * m // 3, m], np.uint32)
+        centres = np.array([q["pts"][a:b].mean(0) if b > a else np.zeros(3) for a, b in zip(start[:-1], start[1:])], F32)
+        return flat(x.body_forces(ws.fluid.body_params(), q["pts"], q["vel"], F32(0.001) + np.abs(q["life"]), start, centres,
+                                  samples=True, **kw))
 
     def expected(self, ieee, regridded, kind, m):
         key = (ieee, regridded, kind, m)
@@ -144,7 +152,7 @@ def scene(ws):
 
 def test_the_scene_exercises_every_call(ws, scene):
     """What the mixed runs rely on: meshes, hits and misses, spawns, a moving fluid."""
-    assert len(set(KINDS)) == len(KINDS) == 16 and set(ORDER) == set(KINDS) and ORDER != KINDS
+    assert len(set(KINDS)) == len(KINDS) == 18 and set(ORDER) == set(KINDS) and ORDER != KINDS
     assert np.abs(scene.pos - scene.start).max() > 0.1 and scene.vel.any()
     for kind in ("surface", "aniso_surface"):
         xyz, nrm, tri = scene.expected(False, False, kind, 4097)
