@@ -1544,19 +1544,39 @@ __device__ __forceinline__ void run_bounds(const uint32_t *__restrict__ start, i
     e = v[3];
 }
 
+// The lane masks K4's walk votes with.  The ballot is taken of the compare itself, where it is made: v_cmp into an SGPR
+// pair, then s_and / s_cmp and a scalar branch.  (A bool that reaches __ballot from another block -- `more` carried
+// round the loop -- comes back through a VGPR: v_cndmask + v_cmp_ne per vote.)
+__device__ __forceinline__ uint64_t nd_lanes_lt(uint32_t a, uint32_t b) { return __ballot(a < b); }
+__device__ __forceinline__ uint64_t nd_lanes_ge(uint32_t a, uint32_t b) { return __ballot(a >= b); }
+
+// Candidate U of a trip, d2 away: every lane stores d2 at its list's write position `at` (an LDS address: list +
+// slot * 4 * ND_P + 4 * lane); the lanes that accept it move `at` one slot on and set bit U.  Branch-free.
+// TEST: the candidate belongs to the run only where more than 4 U bytes of it are left.
+// (Store, advance and bit under the accept mask instead: tools/ab/patches/k4_masked_push.patch, HISTORY.md round 7.)
+template <int U, bool TEST>
+__device__ __forceinline__ void nd_mark(float d2, float d2_accept, uint32_t left, uint32_t &at, uint32_t &bits)
+{
+    const bool acc = (!(TEST && U > 0) || left > 4u * U) && !(d2 > d2_accept);
+    *reinterpret_cast<__attribute__((address_space(3))) float *>(at) = d2;
+    at += acc ? 4u * ND_P : 0u;
+    bits = (U ? bits : 0u) | (acc ? 1u : 0u) << U;
+}
+
 // K4's phase 1 over one run on the planar arrays: 4 candidates per trip from three 16-B loads, the
 // squared distances in scalar f32 arithmetic (same IEEE operations per candidate, same order).
 // Lanes past their run's end keep loading in-bounds slots (the planes are padded) and are masked
 // out of the accept test.  note(nvalid, bits): the trip tested nvalid candidates, bit u = candidate u accepted.
-template <class Push, class Phase2, class Note>
-__device__ __forceinline__ void nd_run_planar(const WsDev &d, float4 o, uint32_t j, uint32_t e, uint32_t &cnt,
-                                              WsXYZ p, Push &&push, Phase2 &&phase2, Note &&note)
+// at: the lane's list write position (nd_mark), at0 the empty list's; the fill level is (at - at0) >> 8.
+template <class Phase2, class Note>
+__device__ __forceinline__ void nd_run_planar(const WsDev &d, float4 o, uint32_t j, uint32_t e, uint32_t &at, const uint32_t at0,
+                                              WsXYZ p, Phase2 &&phase2, Note &&note)
 {
-    // the walk keeps two numbers per lane: the byte offset of the next candidate in the planes (32-bit, from the three
-    // uniform plane bases: no 64-bit address arithmetic) and how many candidates of the run remain
+    static_assert(4u * ND_P == 256u, "the fill level is read as (at - at0) >> 8");
+    // the walk keeps one number per lane: the byte offset of the next candidate in the planes (32-bit, from the three
+    // uniform plane bases: no 64-bit address arithmetic); the run's candidates are left while it is below `end`
     uint32_t off = j * 4u;
-    int32_t rem = (int32_t)(e - j);
-    bool more = rem > 0;
+    const uint32_t end = e > j ? e * 4u : off;
     auto trip = [&]() {
         const nd_f4 X = *reinterpret_cast<const nd_f4u *>(reinterpret_cast<const char *>(p.x) + off);
         const nd_f4 Y = *reinterpret_cast<const nd_f4u *>(reinterpret_cast<const char *>(p.y) + off);
@@ -1570,36 +1590,38 @@ __device__ __forceinline__ void nd_run_planar(const WsDev &d, float4 o, uint32_t
             const float ex = X[u] - o.x, ey = Y[u] - o.y, ez = Z[u] - o.z;
             d2[u] = ex * ex + ey * ey + ez * ez;
         }
-        uint32_t bits = 0;
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const bool acc = (u < rem) && !(d2[u] > d.d2_accept);  // (u < rem: the candidate belongs to the run)
-            push(cnt, d2[u]);  // branch-free: store always, advance the slot on accept
-            cnt += acc ? 1u : 0u;
-            bits |= (acc ? 1u : 0u) << u;
-        }
-        note((uint32_t)min(4, rem), bits);
+        const uint32_t left = end - off;  // bytes of the run from here (> 0)
+        uint32_t bits;
+        nd_mark<0, true>(d2[0], d.d2_accept, left, at, bits);
+        nd_mark<1, true>(d2[1], d.d2_accept, left, at, bits);
+        nd_mark<2, true>(d2[2], d.d2_accept, left, at, bits);
+        nd_mark<3, true>(d2[3], d.d2_accept, left, at, bits);
+        note(min(4u, left >> 2), bits);
         off += 16u;
-        more = rem > 4;
-        rem -= 4;
     };
-    if (!__ballot(more && cnt + (uint32_t)rem > (uint32_t)ND_K)) {
+    if (!(nd_lanes_lt(off, end) & nd_lanes_lt((uint32_t)ND_K, ((at - at0) >> 8) + ((end - off) >> 2)))) {
         // no list of the wave can fill up in this run, even if every remaining candidate is accepted (the sparse
         // state, and short runs anywhere): the plain walk, each lane to the end of its run
-        while (more) trip();
+        while (off < end) trip();
         return;
     }
     // Some list may fill up.  Wave-uniform walk: the moment a lane with candidates left has no room, EVERY lane
     // empties its list (phase 2) and all go on together.  (A lane that waited for the others to finish the run would
     // walk the rest of it alone afterwards -- whole trips of the wave for one lane: 101 instead of 83 trips per wave
     // in the settled C3 cloud.)  The order of the terms is the visit order whenever the lists are emptied.
+    const uint32_t full = at0 + 4u * ND_P * ND_K;  // `at` of a list that takes no further trip
     for (;;) {
-        if (__ballot(more && cnt >= (uint32_t)ND_K)) {
-            phase2(cnt);
-            cnt = 0;
+        const uint64_t more = nd_lanes_lt(off, end);
+        if (more & nd_lanes_ge(at, full)) {
+            phase2((at - at0) >> 8);
+            at = at0;
         }
-        if (!__ballot(more)) break;
-        if (more) trip();
+        if (!more) break;
+        // trips in a row, a loop of their own: each lane until its run ends, all of them until one fills its list
+        if (off < end) {
+            do trip();
+            while (off < end && !nd_lanes_ge(at, full));
+        }
     }
 }
 
@@ -1619,12 +1641,12 @@ __device__ __forceinline__ void nd_tile(const WsDev &d, const uint32_t *__restri
     // accumulator; when a trip crosses into the next word the full word goes out (coalesced across lanes) and the
     // bits that spilled over start the next one -- the crossing is the rare path, one trip in eight.
     uint32_t acc32 = 0;
-    uint32_t pos = 0, word = 0;  // candidates seen so far = 32 * word + pos
+    uint32_t posb = 0u - 32u, word = 0;  // candidates seen so far = 32 * word + pos, and posb = pos - 32 (mod 2^32):
+                                         // a trip's add carries out exactly when it crosses into the next word
     // the row of mask word `word` for this particle: a running pointer, one stride further at each crossing (the word
     // index only ever goes up by one; the product word * stride was a quarter-rate 64-bit multiply that some lane of
     // the wave took on every trip).  It stops at row ND_MASK_WORDS, where nothing is stored any more.
     uint32_t *mrow = mask.words + (iv - d.base);
-    auto push = [&](uint32_t slot, float d2) { list[slot * ND_P + tid] = d2; };
     auto phase2 = [&](uint32_t cnt) {
         uint32_t k = 0;
         for (; k + 2u <= cnt; k += 2u) {  // two list entries per pass: their LDS reads and square roots overlap
@@ -1635,19 +1657,22 @@ __device__ __forceinline__ void nd_tile(const WsDev &d, const uint32_t *__restri
         if (k < cnt) density_pair<IEEE>(d, list[k * ND_P + tid], density, near_density, 1u);
     };
     auto note = [&](uint32_t nvalid, uint32_t bits) {
-        acc32 |= bits << pos;
-        pos += nvalid;
-        if (pos >= 32u) {  // pos was >= 28, so the shift below is by 1..4
+        acc32 |= bits << (posb & 31u);
+        uint32_t over;  // = pos + nvalid - 32 where the trip crosses: 0..3 bits spill over, the trip's last ones
+        if (__builtin_expect(__builtin_add_overflow(posb, nvalid, &over), 0)) {
             if (word < ND_MASK_WORDS) {
                 *mrow = acc32;
                 mrow += mask.stride;
             }
-            pos -= 32u;
-            acc32 = bits >> (nvalid - pos);  // the bits that spilled over: the trip's last `pos` ones
+            acc32 = bits >> (nvalid - over);  // (a shift by 1..4)
             word++;
+            over -= 32u;
         }
+        posb = over;
     };
-    uint32_t cnt = 0;
+    // list write position (nd_mark): slot 0
+    const uint32_t at0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) float *)list + 4u * tid;
+    uint32_t at = at0;
     for (int p = 0; p < 3; p++) {  // dx = -1, 0, +1
         const int cc = d.guard + c + (p - 1) * rowy;
         // unconditional (iv is always a real particle), so the six loads go out together
@@ -1663,12 +1688,13 @@ __device__ __forceinline__ void nd_tile(const WsDev &d, const uint32_t *__restri
             e1 = b1;
             e2 = b2;
         }
-        nd_run_planar(d, o, b0, e0, cnt, sxyz, push, phase2, note);
-        nd_run_planar(d, o, b1, e1, cnt, sxyz, push, phase2, note);
-        nd_run_planar(d, o, b2, e2, cnt, sxyz, push, phase2, note);
+        nd_run_planar(d, o, b0, e0, at, at0, sxyz, phase2, note);
+        nd_run_planar(d, o, b1, e1, at, at0, sxyz, phase2, note);
+        nd_run_planar(d, o, b2, e2, at, at0, sxyz, phase2, note);
     }
-    phase2(cnt);
+    phase2((at - at0) >> 8);
     if (valid) {
+        const uint32_t pos = posb + 32u;
         if (pos && word < ND_MASK_WORDS) *mrow = acc32;
         if (32u * word + pos > 32u * ND_MASK_WORDS) atomicAdd(&stats[0], 1u);  // rare by construction: one counter is enough
         density_store(density, near_density, i, srt);
