@@ -30,6 +30,8 @@ def test_product_sources_have_no_experiment_switches():
 DEV_HOOKS = ("WS_VARIANT", "WS_CELL_BUDGET", "WS_COPY_STREAM_PRIORITY", "WS_RCCL_LIBRARY", "WS_RCCL_SINGLE_COMM",
              "WS_SLAB_EXACT_ONE_RANK", "WS_SLAB_FLOOR_MIGRATION", "WS_SLAB_FLOOR_FAR", "WS_SLAB_FLOOR_HALO", "WS_SLAB_COMM_PRIORITY",
              "WS_TILE_SCHEDULE", "WS_SCHED_CLASSES", "WS_SCHED_GROUP", "WS_FAIL_REGRID")
+# ... and every entry point that exists in such a build alone (csrc/ws_api.cpp, under the same define)
+DEV_ENTRY_POINTS = ("ws_dev_schedule", "ws_dev_plant_schedule", "ws_dev_read_tile_costs")
 
 
 def test_product_sources_read_the_environment_through_the_dev_hook_macro_only():
@@ -63,6 +65,12 @@ def test_product_binary_contains_no_environment_hook():
     assert b"getenv" not in blob
     dev = open(b.build_dev_library(), "rb").read()  # ... and the developer build does (the test means something)
     assert all(name.encode() in dev for name in DEV_HOOKS) and b"getenv" in dev
+    # the same for the developer build's entry points (planted tile costs: tests/schedule_dev.py): not in the product,
+    # not in its header
+    header = open(os.path.join(ROOT, "include", "wsfluid.h")).read()
+    for name in DEV_ENTRY_POINTS:
+        assert name.encode() not in blob and name.encode() in dev and name not in header, name
+    assert b"ws_dev_" not in blob and "ws_dev_" not in header
 
 
 def test_product_build_defines_nothing():

@@ -1880,5 +1880,134 @@ ws_status ws_grid_dims(ws_handle *h, uint32_t dims[3])
 
 }  // extern "C"
 
+#ifdef WS_DEV_HOOKS
+// ======================================================================================
+// developer build only: k_schedule on tile costs the CALLER chooses (tests/test_gpu_schedule_kernel.py).  In a step the
+// costs are whatever the clock measured; these three calls let a test hand the kernel the arrays its arithmetic is
+// delicate at, and see which tiles the scheduled K4 / K5 then ran.  Not declared in include/wsfluid.h.
+// ======================================================================================
+namespace {
+
+// the arrays of one call, released before it returns (hipFree waits for the device: these calls are not on a hot path)
+struct DevSchedArrays {
+    WsScratch<uint32_t> cost4, cost5, split4, split5, perm4, perm5;
+    void release() { release_all(cost4, cost5, split4, split5, perm4, perm5); }
+};
+
+ws_status dev_upload_costs(ws_handle *h, WsScratch<uint32_t> &buf, const uint32_t *cost, uint32_t nt)
+{
+    const ws_status st = buf.alloc(h, (size_t)nt * 4, "planted tile costs");
+    if (st) return st;
+    if (nt) HIP_TRY(h, hipMemcpyAsync(buf.p, cost, (size_t)nt * 4, hipMemcpyHostToDevice, h->stream));
+    return WS_OK;
+}
+
+// split (16 words, as alloc_schedule makes it) and perm of one kernel, all bits set: what k_schedule leaves unwritten shows
+ws_status dev_schedule_outputs(ws_handle *h, WsScratch<uint32_t> &split, WsScratch<uint32_t> &perm, uint32_t nt)
+{
+    ws_status st = split.alloc(h, 16 * 4, "tile schedule");
+    if (!st) st = perm.alloc(h, (size_t)nt * 4, "tile schedule");
+    if (st) return st;
+    HIP_TRY(h, hipMemsetAsync(split.p, 0xFF, 16 * 4, h->stream));
+    if (nt) HIP_TRY(h, hipMemsetAsync(perm.p, 0xFF, (size_t)nt * 4, h->stream));
+    return WS_OK;
+}
+
+ws_status dev_drain(ws_handle *h)
+{
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (h->sched_stream) HIP_TRY(h, hipStreamSynchronize(h->sched_stream));
+    return WS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// k_schedule once, on cost arrays of the caller's: nt4 / nt5 tiles (any counts, whatever the handle's n; 0 = that half
+// of the launch returns at once and its outputs stay all-ones), group_particles / tile5 as wsk_schedule takes them
+// (K4's groups are group_particles / 64 tiles, K5's group_particles / tile5).  Waits; split4 / split5: 9 words each.
+ws_status ws_dev_schedule(ws_handle *h, const uint32_t *cost4, uint32_t nt4, const uint32_t *cost5, uint32_t nt5, uint32_t nclasses,
+                          uint32_t group_particles, uint32_t tile5, uint32_t *split4, uint32_t *perm4, uint32_t *split5, uint32_t *perm5)
+{
+    if (!h || !split4 || !split5 || (nt4 && (!cost4 || !perm4)) || (nt5 && (!cost5 || !perm5)) || !tile5) return WS_ERR_INVALID_ARG;
+    WS_DEAD_CHECK(h);
+    HIP_TRY(h, hipSetDevice(h->device));
+    DevSchedArrays a;
+    const ws_status st = [&]() -> ws_status {
+        ws_status s = dev_upload_costs(h, a.cost4, cost4, nt4);
+        if (!s) s = dev_upload_costs(h, a.cost5, cost5, nt5);
+        if (!s) s = dev_schedule_outputs(h, a.split4, a.perm4, nt4);
+        if (!s) s = dev_schedule_outputs(h, a.split5, a.perm5, nt5);
+        if (s) return s;
+        WsSched s4, s5;
+        s4.split = a.split4.p, s4.perm = a.perm4.p, s4.cost = a.cost4.p;
+        s5.split = a.split5.p, s5.perm = a.perm5.p, s5.cost = a.cost5.p;
+        wsk_schedule(h->stream, s4, nt4, s5, s5, nt5, nclasses, group_particles, tile5);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(split4, a.split4.p, 9 * 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(split5, a.split5.p, 9 * 4, hipMemcpyDeviceToHost, h->stream));
+        if (nt4) HIP_TRY(h, hipMemcpyAsync(perm4, a.perm4.p, (size_t)nt4 * 4, hipMemcpyDeviceToHost, h->stream));
+        if (nt5) HIP_TRY(h, hipMemcpyAsync(perm5, a.perm5.p, (size_t)nt5 * 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        return WS_OK;
+    }();
+    (void)hipStreamSynchronize(h->stream);  // (a failure half way: nothing of `a` is still in flight when it is freed)
+    a.release();
+    return st;
+}
+
+// A handle whose schedule is on: the NEXT ws_step's K4 and K5 run the split / perm k_schedule makes of cost4
+// [sched_tiles4] and cost5 [sched_tiles5], and the cost arrays those two kernels write start at zero, so that
+// ws_dev_read_tile_costs shows afterwards which tiles ran.  The step after that is scheduled from measured costs again.
+ws_status ws_dev_plant_schedule(ws_handle *h, const uint32_t *cost4, const uint32_t *cost5)
+{
+    if (!h || !cost4 || !cost5) return WS_ERR_INVALID_ARG;
+    WS_DEAD_CHECK(h);
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (!h->sched_on) return fail(h, WS_ERR_INVALID_ARG, "ws_dev_plant_schedule: the handle has no tile schedule");
+    DevSchedArrays a;
+    const ws_status st = [&]() -> ws_status {
+        ws_status s = dev_drain(h);
+        if (!s) s = dev_upload_costs(h, a.cost4, cost4, h->sched_tiles4);
+        if (!s) s = dev_upload_costs(h, a.cost5, cost5, h->sched_tiles5);
+        if (s) return s;
+        const uint32_t par = h->sched_parity;  // the set the next step's kernels read
+        WsSched s4 = h->sched4[par], from5;
+        s4.cost = a.cost4.p;
+        from5.cost = a.cost5.p;
+        wsk_schedule(h->stream, s4, h->sched_tiles4, h->sched5[par], from5, h->sched_tiles5, h->sched_classes, h->sched_group,
+                     wsk_force_tile(h->n));
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemsetAsync(h->sched4[par].cost, 0, (size_t)h->sched_tiles4 * 4, h->stream));
+        HIP_TRY(h, hipMemsetAsync(h->sched5[par].cost, 0, (size_t)h->sched_tiles5 * 4, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        return WS_OK;
+    }();
+    (void)hipStreamSynchronize(h->stream);
+    a.release();
+    return st;
+}
+
+// The costs K4 and K5 of the last step wrote (cost4 [sched_tiles4], cost5 [sched_tiles5]; either may be NULL), and the
+// two tile counts (ntiles[2]; may be NULL).
+ws_status ws_dev_read_tile_costs(ws_handle *h, uint32_t *cost4, uint32_t *cost5, uint32_t *ntiles)
+{
+    if (!h) return WS_ERR_INVALID_ARG;
+    WS_DEAD_CHECK(h);
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (!h->sched_on) return fail(h, WS_ERR_INVALID_ARG, "ws_dev_read_tile_costs: the handle has no tile schedule");
+    const ws_status st = dev_drain(h);
+    if (st) return st;
+    if (ntiles) ntiles[0] = h->sched_tiles4, ntiles[1] = h->sched_tiles5;
+    const uint32_t ran = h->sched_parity ^ 1u;  // the set the last step's kernels read, and whose costs its K5 wrote
+    if (cost4) HIP_TRY(h, copy_now(h, cost4, h->sched4[ran].cost, (size_t)h->sched_tiles4 * 4, hipMemcpyDeviceToHost));
+    if (cost5) HIP_TRY(h, copy_now(h, cost5, h->sched5[ran].cost, (size_t)h->sched_tiles5 * 4, hipMemcpyDeviceToHost));
+    return WS_OK;
+}
+
+}  // extern "C"
+#endif  // WS_DEV_HOOKS
+
 #include "ws_field.inc"
 #include "ws_slab.inc"
