@@ -104,7 +104,8 @@ def test_set_params_gravity_and_radius_change(oracle, ws):
 def test_record_view_reports_the_last_steps_acceleration_whatever_happens_after_it(ws):
     """The step does not store accelerations; ws_read_particles computes them on demand from the state the last step
     left behind.  They must be the ones that step USED: reading twice gives the same bits, and a parameter change
-    (viscosity, pressure; a new radius that throws the grid away) between the step and the read does not leak in."""
+    (viscosity, pressure; a new radius that throws the grid away) between the step and the read does not leak in.  Nor
+    does it into the pressure, which the view computes from the stored density: with the parameters of that step."""
     pos = ws.workloads.uniform_cloud(20000, 3, [-2.9, -1.9, -1.9], [2.9, 1.9, 1.9])
     params = ws.make_params(container_size=(6.0, 4.0, 4.0))
 
@@ -126,7 +127,7 @@ def test_record_view_reports_the_last_steps_acceleration_whatever_happens_after_
                    ws.make_params(container_size=(6.0, 4.0, 4.0), smoothing_radius=0.35),
                    ws.make_params(container_size=(6.0, 4.0, 4.0), gravity=(1.0, 2.0, 3.0, 0.0))):
         got = after(change)
-        for f in ("acceleration", "position", "velocity", "predicted_position"):
+        for f in ("acceleration", "position", "velocity", "predicted_position", "density", "pressure"):
             assert np.array_equal(got[f].view(np.uint32), want[f].view(np.uint32)), f
 
 

@@ -37,6 +37,7 @@ def gpu_step_check(ws, pos, params, ieee, what, warm=0, state=None, queries=None
     q = queries(state) if callable(queries) else queries
     worst = F.check_step(state, got, params, ws.get_smoothing_kernel(params), what, _arith(ieee), queries=q, check_sort=sort)
     worst["stats"] = stats
+    worst["got"] = got
     return worst
 
 

@@ -568,6 +568,13 @@ void enqueue_step(ws_handle *h)
     h->accel_stale = true;  // ... and no accelerations (refresh_accel)
 }
 
+// The record views report pressure = f(density) (simulation.wgsl:192-193) without storing it: what f was when the step
+// about to be enqueued computes its densities.  ws_set_params between that step and a read must not leak into the view.
+void note_step_params(ws_handle *h)
+{
+    h->last_pressure = {h->dev.pressure_scalar, h->dev.target_density, h->dev.near_pressure_scalar};
+}
+
 // cur.pred is not maintained by the step loop (k_reorder recomputes it): bring it up to date for a reader off the loop
 void refresh_pred(ws_handle *h, const WsDev &d)
 {
@@ -640,6 +647,7 @@ ws_status upload_positions(ws_handle *h, const float *pos_xyz)
     // the caller's buffer must not be referenced after return
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->steps = 0;
+    h->last_pressure = {};
     return WS_OK;
 }
 
@@ -906,6 +914,7 @@ ws_status ws_step(ws_handle *h)
     if (h->dead) return fail(h, WS_ERR_HIP, h->err.c_str());
     hipStream_t s = h->stream;
     bound_pending(h);
+    note_step_params(h);
     // WS_FLAG_GRAPH: the five launches as one captured graph (the reference replays its pass graph the same way,
     // src/fluid_compute.rs:309-363,:396).  Off by default: measured no faster than the direct launches, which already
     // pipeline on the stream (round 1: C1 0.061 vs 0.055 ms/step, C2 0.107 vs 0.100, C3 equal; round 3: DESIGN.md).
@@ -1231,7 +1240,7 @@ ws_status ws_read_particles(ws_handle *h, ws_particle80 *out)
     refresh_pred(h, h->dev);
     st = refresh_accel(h);
     if (st) return st;
-    wsk_gather_particles(h->stream, h->dev, h->cur, h->srt, h->accel, h->steps > 0, (ws_particle80 *)h->stage, h->n);
+    wsk_gather_particles(h->stream, h->cur, h->srt, h->accel, h->steps > 0, h->last_pressure, (ws_particle80 *)h->stage, h->n);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipMemcpyAsync(out, h->stage, bytes, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -1268,6 +1277,7 @@ ws_status ws_write_particles(ws_handle *h, const ws_particle80 *in)
     if (st) return st;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->steps = 0;
+    h->last_pressure = {};
     return WS_OK;
 }
 

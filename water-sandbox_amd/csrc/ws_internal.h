@@ -344,6 +344,12 @@ struct WsVolumeDesc {
     float spacing[3];
 };
 
+// What a record view's pressures are computed from: the density -> pressure parameters of the step that computed the
+// densities, not the handle's current ones (ws_set_params may have come in between).
+struct WsPressureParams {
+    float pressure_scalar, target_density, near_pressure_scalar;
+};
+
 struct ws_handle {
     int device = 0;
     uint32_t flags = 0;
@@ -353,6 +359,7 @@ struct ws_handle {
     ws_params params{};
     ws_smoothing_kernel sk{};
     WsDev dev{};
+    WsPressureParams last_pressure{};  // of the last step enqueued (ws_step records them; zero again wherever steps returns to 0)
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;
     bool done_recorded = false;
@@ -644,8 +651,8 @@ void wsk_force(hipStream_t s, const WsDev &d, const uint32_t *start, const uint3
 void wsk_gather_positions(hipStream_t s, WsSoA cur, float *out_xyz, uint32_t n);
 void wsk_gather_speeds(hipStream_t s, WsSoA cur, float *out, uint32_t n);
 void wsk_gather_velocities(hipStream_t s, WsSoA cur, float *out_xyz, uint32_t n);
-void wsk_gather_particles(hipStream_t s, const WsDev &d, WsSoA cur, WsSorted srt, const float4 *accel, bool have_step,
-                          ws_particle80 *out, uint32_t n);
+void wsk_gather_particles(hipStream_t s, WsSoA cur, WsSorted srt, const float4 *accel, bool have_step,
+                          const WsPressureParams &pp, ws_particle80 *out, uint32_t n);
 // reference-layout view
 void wsk_view_keys(hipStream_t s, const WsDev &d, WsSorted srt, uint32_t *keys_by_id, uint32_t *count);
 void wsk_view_count(hipStream_t s, const uint32_t *keys, uint32_t *count, uint32_t n);
@@ -761,13 +768,13 @@ void wsk_halo_pack(hipStream_t s, const WsDev &d, const uint32_t *start, WsSorte
 void wsk_halo_unpack(hipStream_t s, const WsDev &d, uint32_t *start, WsSorted srt, WsXYZ sxyz, uint32_t *dyn, uint32_t rowy,
                      uint32_t nxl, uint32_t ghost_cap, const uint32_t *recvL, const uint32_t *recvR, bool densities);
 void wsk_gather_slab(hipStream_t s, const WsDev &d, WsSoA cur, WsSorted srt, const float4 *accel, bool have_step,
-                     ws_particle80 *out, uint32_t *ids);
+                     const WsPressureParams &pp, ws_particle80 *out, uint32_t *ids);
 void wsk_upload_positions_ids(hipStream_t s, const float *xyz_dev, const uint32_t *ids_dev, WsSoA cur, uint32_t n);
 // id-ordered global views / loads of slab handles (ws_kernels.hip "slab handles: the id-ordered GLOBAL views")
 enum { WS_PACK_POS_H = 0, WS_PACK_SPEED_H = 1, WS_PACK_RECORD_H = 2, WS_PACK_STATE_H = 3, WS_PACK_KEY_H = 4, WS_PACK_POSVEL_H = 5 };
 uint32_t wsk_pack_words(int kind);  // payload words per record (the record carries one more: the particle id)
 void wsk_slab_pack(hipStream_t s, const WsDev &d, int kind, WsSoA cur, WsSorted srt, const float4 *accel, bool have_step,
-                   uint32_t *out);
+                   const WsPressureParams &pp, uint32_t *out);
 void wsk_slab_unpack_by_id(hipStream_t s, const uint32_t *all, const uint32_t *cnt, uint32_t world, uint32_t max_n,
                            size_t stride_words, uint32_t pw, uint32_t n_global, uint32_t *out);
 void wsk_slab_layer_hist(hipStream_t s, const WsDev &d, const uint32_t *all, const uint32_t *cnt, uint32_t world, uint32_t max_n,

@@ -2275,8 +2275,8 @@ void wsk_gather_velocities(hipStream_t s, WsSoA cur, float *out_xyz, uint32_t n)
     hipLaunchKernelGGL(k_gather_velocities, dim3(cdiv(n, WS_BLOCK)), dim3(WS_BLOCK), 0, s, cur, out_xyz, n);
 }
 
-__global__ void __launch_bounds__(WS_BLOCK) k_gather_particles(WsDev d, WsSoA cur, WsSorted srt,
-                                                               const float4 *__restrict__ accel, int have_step,
+__global__ void __launch_bounds__(WS_BLOCK) k_gather_particles(WsSoA cur, WsSorted srt, const float4 *__restrict__ accel,
+                                                               int have_step, WsPressureParams pp,
                                                                ws_particle80 *__restrict__ out, uint32_t n)
 {
     const uint32_t i = blockIdx.x * WS_BLOCK + threadIdx.x;
@@ -2287,8 +2287,9 @@ __global__ void __launch_bounds__(WS_BLOCK) k_gather_particles(WsDev d, WsSoA cu
     if (have_step) {
         dp.x = srt.pred(i).w;  // density / near density ride in the sorted copy's w lanes
         dp.y = srt.vel(i).w;
-        dp.z = d.pressure_scalar * (dp.x - d.target_density);  // simulation.wgsl:192-193
-        dp.w = d.near_pressure_scalar * dp.y;
+        // simulation.wgsl:192-193, with the parameters of the step that computed the densities (ws_handle::last_pressure)
+        dp.z = pp.pressure_scalar * (dp.x - pp.target_density);
+        dp.w = pp.near_pressure_scalar * dp.y;
         a = accel[i];
     }
     float4 *rec = reinterpret_cast<float4 *>(out + id);
@@ -2299,11 +2300,11 @@ __global__ void __launch_bounds__(WS_BLOCK) k_gather_particles(WsDev d, WsSoA cu
     rec[4] = make_float4(q.x, q.y, q.z, 0.f);
 }
 
-void wsk_gather_particles(hipStream_t s, const WsDev &d, WsSoA cur, WsSorted srt, const float4 *accel, bool have_step,
-                          ws_particle80 *out, uint32_t n)
+void wsk_gather_particles(hipStream_t s, WsSoA cur, WsSorted srt, const float4 *accel, bool have_step,
+                          const WsPressureParams &pp, ws_particle80 *out, uint32_t n)
 {
-    hipLaunchKernelGGL(k_gather_particles, dim3(cdiv(n, WS_BLOCK)), dim3(WS_BLOCK), 0, s, d, cur, srt, accel,
-                       have_step ? 1 : 0, out, n);
+    hipLaunchKernelGGL(k_gather_particles, dim3(cdiv(n, WS_BLOCK)), dim3(WS_BLOCK), 0, s, cur, srt, accel,
+                       have_step ? 1 : 0, pp, out, n);
 }
 
 // ---------------------------------------------------------------------------------
@@ -2945,8 +2946,8 @@ void wsk_halo_unpack(hipStream_t s, const WsDev &d, uint32_t *start, WsSorted sr
 
 // Slab readback: owned particles (state of the last step, sorted order) with their ids.
 __global__ void __launch_bounds__(WS_BLOCK) k_gather_slab(WsDev d, WsSoA cur, WsSorted srt, const float4 *__restrict__ accel,
-                                                          int have_step, ws_particle80 *__restrict__ out,
-                                                          uint32_t *__restrict__ ids)
+                                                          int have_step, WsPressureParams pp,
+                                                          ws_particle80 *__restrict__ out, uint32_t *__restrict__ ids)
 {
     const uint32_t k = blockIdx.x * WS_BLOCK + threadIdx.x;
     if (k >= ws_n(d)) return;
@@ -2956,8 +2957,8 @@ __global__ void __launch_bounds__(WS_BLOCK) k_gather_slab(WsDev d, WsSoA cur, Ws
     if (have_step) {
         dp.x = srt.pred(i).w;
         dp.y = srt.vel(i).w;
-        dp.z = d.pressure_scalar * (dp.x - d.target_density);
-        dp.w = d.near_pressure_scalar * dp.y;
+        dp.z = pp.pressure_scalar * (dp.x - pp.target_density);  // (the last step's: k_gather_particles)
+        dp.w = pp.near_pressure_scalar * dp.y;
         a = accel[i];
     }
     float4 *rec = reinterpret_cast<float4 *>(out + k);
@@ -2970,11 +2971,11 @@ __global__ void __launch_bounds__(WS_BLOCK) k_gather_slab(WsDev d, WsSoA cur, Ws
 }
 
 void wsk_gather_slab(hipStream_t s, const WsDev &d, WsSoA cur, WsSorted srt, const float4 *accel, bool have_step,
-                     ws_particle80 *out, uint32_t *ids)
+                     const WsPressureParams &pp, ws_particle80 *out, uint32_t *ids)
 {
     if (d.n == 0) return;
     hipLaunchKernelGGL(k_gather_slab, dim3(cdiv(d.n, WS_BLOCK)), dim3(WS_BLOCK), 0, s, d, cur, srt, accel,
-                       have_step ? 1 : 0, out, ids);
+                       have_step ? 1 : 0, pp, out, ids);
 }
 
 // upload of a slab's initial particles: ids are given explicitly
@@ -3021,7 +3022,7 @@ uint32_t wsk_pack_words(int kind) { return ws_pack_words(kind); }
 
 template <int KIND>
 __global__ void __launch_bounds__(WS_BLOCK) k_slab_pack(WsDev d, WsSoA cur, WsSorted srt, const float4 *__restrict__ accel,
-                                                        int have_step, uint32_t *__restrict__ out)
+                                                        int have_step, WsPressureParams pp, uint32_t *__restrict__ out)
 {
     const uint32_t k = blockIdx.x * WS_BLOCK + threadIdx.x;
     if (k >= d.n) return;
@@ -3058,8 +3059,8 @@ __global__ void __launch_bounds__(WS_BLOCK) k_slab_pack(WsDev d, WsSoA cur, WsSo
         if (have_step) {
             dp.x = srt.pred(i).w;
             dp.y = srt.vel(i).w;
-            dp.z = d.pressure_scalar * (dp.x - d.target_density);
-            dp.w = d.near_pressure_scalar * dp.y;
+            dp.z = pp.pressure_scalar * (dp.x - pp.target_density);
+            dp.w = pp.near_pressure_scalar * dp.y;
             a = accel[i];
         }
         f[0] = p.x; f[1] = p.y; f[2] = p.z; f[3] = 0.f;
@@ -3071,18 +3072,18 @@ __global__ void __launch_bounds__(WS_BLOCK) k_slab_pack(WsDev d, WsSoA cur, WsSo
 }
 
 void wsk_slab_pack(hipStream_t s, const WsDev &d, int kind, WsSoA cur, WsSorted srt, const float4 *accel, bool have_step,
-                   uint32_t *out)
+                   const WsPressureParams &pp, uint32_t *out)
 {
     if (!d.n) return;
     const dim3 g(cdiv(d.n, WS_BLOCK)), b(WS_BLOCK);
     const int hs = have_step ? 1 : 0;
     switch (kind) {
-        case WS_PACK_POS: hipLaunchKernelGGL(k_slab_pack<WS_PACK_POS>, g, b, 0, s, d, cur, srt, accel, hs, out); break;
-        case WS_PACK_SPEED: hipLaunchKernelGGL(k_slab_pack<WS_PACK_SPEED>, g, b, 0, s, d, cur, srt, accel, hs, out); break;
-        case WS_PACK_RECORD: hipLaunchKernelGGL(k_slab_pack<WS_PACK_RECORD>, g, b, 0, s, d, cur, srt, accel, hs, out); break;
-        case WS_PACK_STATE: hipLaunchKernelGGL(k_slab_pack<WS_PACK_STATE>, g, b, 0, s, d, cur, srt, accel, hs, out); break;
-        case WS_PACK_POSVEL: hipLaunchKernelGGL(k_slab_pack<WS_PACK_POSVEL>, g, b, 0, s, d, cur, srt, accel, hs, out); break;
-        default: hipLaunchKernelGGL(k_slab_pack<WS_PACK_KEY>, g, b, 0, s, d, cur, srt, accel, hs, out); break;
+        case WS_PACK_POS: hipLaunchKernelGGL(k_slab_pack<WS_PACK_POS>, g, b, 0, s, d, cur, srt, accel, hs, pp, out); break;
+        case WS_PACK_SPEED: hipLaunchKernelGGL(k_slab_pack<WS_PACK_SPEED>, g, b, 0, s, d, cur, srt, accel, hs, pp, out); break;
+        case WS_PACK_RECORD: hipLaunchKernelGGL(k_slab_pack<WS_PACK_RECORD>, g, b, 0, s, d, cur, srt, accel, hs, pp, out); break;
+        case WS_PACK_STATE: hipLaunchKernelGGL(k_slab_pack<WS_PACK_STATE>, g, b, 0, s, d, cur, srt, accel, hs, pp, out); break;
+        case WS_PACK_POSVEL: hipLaunchKernelGGL(k_slab_pack<WS_PACK_POSVEL>, g, b, 0, s, d, cur, srt, accel, hs, pp, out); break;
+        default: hipLaunchKernelGGL(k_slab_pack<WS_PACK_KEY>, g, b, 0, s, d, cur, srt, accel, hs, pp, out); break;
     }
 }
 

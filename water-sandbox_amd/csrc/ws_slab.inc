@@ -432,6 +432,7 @@ ws_status slab_step(ws_handle *h)
     if (S->comm_failed) return fail(h, WS_ERR_COMM, "an earlier transport call failed; the slab handle is unusable");
     if (S->failed) return fail(h, dyn_error_status(S->failed), dyn_error_text(S->failed));
     bound_pending(h);
+    note_step_params(h);
     const uint64_t t = h->steps;
     if (t >= S->t0 + kStatusLag) {  // (tables of steps before the last load describe another particle set)
         const ws_status st = slab_consume_status(h, t - kStatusLag);
@@ -819,6 +820,7 @@ ws_status slab_reset(ws_handle *h, const float *pos_xyz)
     ws_status st = slab_quiesce(h);
     if (st) return st;
     h->steps = 0;
+    h->last_pressure = {};
     return slab_load_global(h, 0, pos_xyz, 12);
 }
 
@@ -827,6 +829,7 @@ ws_status slab_write_particles(ws_handle *h, const ws_particle80 *in)
     ws_status st = slab_quiesce(h);
     if (st) return st;
     h->steps = 0;
+    h->last_pressure = {};
     return slab_load_global(h, 1, in, sizeof(ws_particle80));
 }
 
@@ -893,7 +896,7 @@ ws_status slab_gather(ws_handle *h, int kind, size_t *stride_words_out, uint32_t
         st = refresh_accel(h);
         if (st) return st;
     }
-    wsk_slab_pack(h->stream, d, kind, h->cur, h->srt, h->accel, h->steps > S->t0, S->g_send.p);
+    wsk_slab_pack(h->stream, d, kind, h->cur, h->srt, h->accel, h->steps > S->t0, h->last_pressure, S->g_send.p);
     HIP_TRY(h, hipGetLastError());
     if (W > 1) {
         const int rc = S->tr.allgather_dev(S->tr.ctx, S->g_send.p, S->g_all.p, each, h->stream);
@@ -1397,7 +1400,7 @@ ws_status ws_slab_read_particles(ws_handle *h, ws_particle80 *out, uint32_t *out
     refresh_pred(h, d);
     st = refresh_accel(h);
     if (st) return st;
-    wsk_gather_slab(h->stream, d, h->cur, h->srt, h->accel, h->steps > h->slab->t0, (ws_particle80 *)h->stage,
+    wsk_gather_slab(h->stream, d, h->cur, h->srt, h->accel, h->steps > h->slab->t0, h->last_pressure, (ws_particle80 *)h->stage,
                     (uint32_t *)((char *)h->stage + pb));
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipMemcpyAsync(out, h->stage, pb, hipMemcpyDeviceToHost, h->stream));
