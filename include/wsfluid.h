@@ -1081,7 +1081,7 @@ uint64_t ws_steps_done(ws_handle *h);
 
 /* Kernel ids for ws_profile_read (stable; names via ws_kernel_name). */
 enum {
-    WS_K_SCAN = 0,     /* cell-count exclusive scan (3 launches)                */
+    WS_K_SCAN = 0,     /* cell-count exclusive scan (one launch per step)       */
     WS_K_SCATTER = 1,  /* slot assignment inside each cell                      */
     WS_K_REORDER = 2,  /* stable in-cell order + physical SoA reorder           */
     WS_K_DENSITY = 3,  /* K4 update_density                                     */
@@ -1092,7 +1092,13 @@ enum {
 const char *ws_kernel_name(uint32_t kernel_id);
 /* With WS_FLAG_PROFILE: total milliseconds and launch count per kernel id since the
  * last ws_profile_reset, measured with HIP events on the handle's own stream.  Waits
- * for enqueued steps. */
+ * for enqueued steps.  Scan, scatter, reorder and bin are timed by an event pair recorded
+ * around the launch, K4 and K5 by events the launch itself carries.  A step counts one
+ * launch per kernel id: a slab step that runs K4 and K5 as an early and a late range
+ * contributes ONE launch and the SUM of its two ranges' times.  WS_K_BIN counts the
+ * stand-alone binning of ws_create, ws_reset, ws_write_particles and a ws_set_params that
+ * re-grids on a single-GPU handle.  A WS_FLAG_GRAPH handle records nothing: all zeros.
+ * Either output pointer may be NULL; kernel_id >= WS_K_COUNT is WS_ERR_INVALID_ARG. */
 ws_status ws_profile_read(ws_handle *h, uint32_t kernel_id, double *total_ms, uint64_t *launches);
 ws_status ws_profile_reset(ws_handle *h);
 /* Restrict WS_FLAG_PROFILE's events to the kernel ids whose bit is set in mask (default: all),

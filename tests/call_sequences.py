@@ -206,7 +206,7 @@ def _read(w, op, kit, cur, **kw):
     return flat(w.sort_view())
 
 
-Record = collections.namedtuple("Record", "states outs reads splits final counts graph_steps")
+Record = collections.namedtuple("Record", "states outs reads splits final counts graph_steps profile")
 
 
 def run(noisy, quiet, fresh, seq, check=None, *, kit):
@@ -227,8 +227,9 @@ def run(noisy, quiet, fresh, seq, check=None, *, kit):
     check(index, op, ref, before, after, out) is called after every edit with the verified (pos, vel) around it and
     the quiet handle's outputs.  A difference raises SequenceMismatch at the first op where it shows.  Returns a Record
     of what was verified: states[i] = (pos, vel) after op i (-1: at the start), outs[i], reads[i], splits[i], final,
-    the number of ops per class, graph_steps[i] = noisy.stats()["graph_steps"] after step op i."""
-    rec = Record({}, {}, {}, {}, [], collections.Counter(), {})
+    the number of ops per class, graph_steps[i] = noisy.stats()["graph_steps"] after step op i, and -- where the noisy
+    handle offers profile() -- profile[i] = noisy.profile() after EVERY op i (-1: at the start; check_profile_counts)."""
+    rec = Record({}, {}, {}, {}, [], collections.Counter(), {}, {})
     cur = dict(small=False, gx=0, volumes={})
 
     def state(i, op):
@@ -242,7 +243,12 @@ def run(noisy, quiet, fresh, seq, check=None, *, kit):
         rec.states[i] = tuple(want)
         return want
 
+    def note_profile(i):
+        if hasattr(noisy, "profile"):
+            rec.profile[i] = noisy.profile()
+
     pos, vel = state(-1, None)
+    note_profile(-1)
     split = None
 
     def end_split():
@@ -263,6 +269,7 @@ def run(noisy, quiet, fresh, seq, check=None, *, kit):
             buf = np.empty((len(pos), 3), F32)
             noisy.read_positions_begin(buf)
             split = (i, buf, pos)
+            note_profile(i)
             continue
         if op.cls == "read":
             got = _read(noisy, op, kit, cur)
@@ -279,6 +286,7 @@ def run(noisy, quiet, fresh, seq, check=None, *, kit):
             if bad:
                 raise SequenceMismatch(i, op, "outputs %s differ from %s" % (bad, against), seq)
             rec.reads[i] = want
+            note_profile(i)
             continue
         call, ref = _arguments(op, kit, cur, pos, vel)
         out_n, out_q = flat(call(noisy)), flat(call(quiet))
@@ -298,6 +306,7 @@ def run(noisy, quiet, fresh, seq, check=None, *, kit):
                 raise SequenceMismatch(i, op, "the restatement: %s" % (e,), seq) from e
         if op.cls == "step" and hasattr(noisy, "stats"):
             rec.graph_steps[i] = noisy.stats()["graph_steps"]
+        note_profile(i)
     end_split()
     a, b = noisy.read_vec("particles"), quiet.read_vec("particles")
     bad = record_fields(a, b)
@@ -305,6 +314,45 @@ def run(noisy, quiet, fresh, seq, check=None, *, kit):
         raise SequenceMismatch(len(seq), None, "the records at the end differ in %s" % bad, seq)
     rec.final.append(b)
     return rec
+
+
+STEP_KERNELS = ("cell_scan", "cell_scatter", "reorder", "density", "force_integrate_bin")  # one launch each per step
+
+
+def expected_launches(seq, steps_before, bins_before=1):
+    """The cumulative launch counts a profiled single handle must report after every op, from the op list ALONE:
+    [{kernel: launches}] for index -1 (the start: `bins_before` stand-alone binnings -- the handle's creation -- and
+    `steps_before` steps) and then one per op.  A step op of variant v adds v to each of STEP_KERNELS; a write, a
+    reset and a re-grid bin the particles once more ("bin"); edits, uploads, other parameter pushes and reads add
+    nothing."""
+    now = dict({k: steps_before for k in STEP_KERNELS}, bin=bins_before)
+    out = [dict(now)]
+    for op in seq:
+        if op.cls == "step":
+            for k in STEP_KERNELS:
+                now[k] += op.variant
+        elif op.name in ("write", "reset") or regrids(op):
+            now["bin"] += 1
+        out.append(dict(now))
+    return out
+
+
+def check_profile_counts(seq, rec, steps_before, bins_before=1):
+    """rec.profile (what run() recorded of noisy.profile() after every op) against expected_launches, at EVERY op: the
+    first op whose counts differ raises SequenceMismatch there.  A counted kernel must also carry time, an uncounted
+    one none."""
+    want = expected_launches(seq, steps_before, bins_before)
+    if sorted(rec.profile) != list(range(-1, len(seq))):
+        raise SequenceMismatch(-1, None, "the profile was recorded at ops %s" % sorted(rec.profile), seq)
+    for i in range(-1, len(seq)):
+        got = {k: n for k, (_, n) in rec.profile[i].items()}
+        op = seq[i] if i >= 0 else None
+        if got != want[i + 1]:
+            bad = {k: (got.get(k), want[i + 1].get(k)) for k in set(got) | set(want[i + 1]) if got.get(k) != want[i + 1].get(k)}
+            raise SequenceMismatch(i, op, "launch counts (reported, asked for) differ: %s" % bad, seq)
+        timeless = [k for k, (ms, n) in rec.profile[i].items() if (ms > 0.0) != (n > 0)]
+        if timeless:
+            raise SequenceMismatch(i, op, "kernels counted without time, or timed without a count: %s" % timeless, seq)
 
 
 STEP_FIELDS = ("density", "pressure", "acceleration")  # of the 80-byte record: what only a step computes

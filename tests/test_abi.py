@@ -71,6 +71,15 @@ def test_status_strings_and_kernel_names(ws):
     assert lib.ws_kernel_name(4) == b"force_integrate_bin"
 
 
+def test_kernel_names_are_the_inverse_of_the_binding_ids(ws):
+    """ws_kernel_name(k) for every id below WS_K_COUNT against fluid.KERNEL_IDS, which profile() reads by."""
+    lib = ws.load_library()
+    by_id = {k: name for name, k in ws.fluid.KERNEL_IDS.items()}
+    assert sorted(by_id) == list(range(6)) and len(ws.fluid.KERNEL_IDS) == 6
+    for k in range(6):
+        assert lib.ws_kernel_name(k) == by_id[k].encode(), k
+
+
 def test_create_rejects_bad_arguments_without_touching_a_device(ws):
     lib = ws.load_library()
     h = C.c_void_p()

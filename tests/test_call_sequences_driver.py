@@ -369,6 +369,81 @@ def test_a_split_read_must_hold_the_positions_of_its_begin():
     Q.run(*handles(None), seq, kit=KIT)
 
 
+class Profiled(Toy):
+    """A stand-in that counts its launches as a profiled handle does: one of each step kernel per step, one "bin" per
+    creation, write, reset and re-grid.  miscount = an op name: a read of that name loses the event pair of one density
+    launch (a pair dropped unread); "split": the step after a re-grid counts its density launch twice (an early and a
+    late range both counted)."""
+
+    def __init__(self, pos, params, miscount=None):
+        super().__init__(pos, params)
+        self.miscount, self.counts, self.regridded = miscount, dict({k: 0 for k in Q.STEP_KERNELS}, bin=1), False
+
+    def profile(self):
+        return {k: (0.01 * n, n) for k, n in self.counts.items()}
+
+    def run(self, steps=1):
+        super().run(steps)
+        for k in Q.STEP_KERNELS:
+            self.counts[k] += steps
+        if self.miscount == "split" and self.regridded:
+            self.counts["density"] += 1
+        self.regridded = False
+
+    def write_slice(self, name, rec):
+        super().write_slice(name, rec)
+        self.counts["bin"] += 1
+
+    def reset(self, pos):
+        super().reset(pos)
+        self.counts["bin"] += 1
+
+    def set_params(self, p):
+        if p["h"] != self.p["h"]:
+            self.counts["bin"] += 1
+            self.regridded = True
+        super().set_params(p)
+
+    def read_speeds(self):
+        if self.miscount == "read_speeds":
+            self.counts["density"] -= 1
+        return super().read_speeds()
+
+
+SPEEDS = Op("read", "read_speeds", None, None)
+MISCOUNTS = {
+    # planted miscount, sequence, the op at which the counts first differ
+    "a read drops a pair": ("read_speeds", [STEP, FORCES, SPEEDS, STEP], 2),
+    "the step after a re-grid counts twice": ("split", [STEP, REGRID, FIELD(), Op("step", "run", 3, None), STEP], 3),
+    "faithful": (None, [STEP, REGRID, SPEEDS, Op("host", "reset", None, None), Op("step", "run", 3, None), BACK, Op("host", "write", None, 7)], None),
+}
+
+
+@pytest.mark.parametrize("case", list(MISCOUNTS))
+def test_a_planted_miscount_is_reported_at_the_op_where_it_happens(case):
+    miscount, seq, index = MISCOUNTS[case]
+    _, quiet, fresh = handles(None)
+    noisy = Profiled(KIT.start, quiet.p, miscount)
+    noisy.run(5)
+    rec = Q.run(noisy, quiet, fresh, seq, kit=KIT)  # (the state is right: only the counts are not)
+    assert sorted(rec.profile) == list(range(-1, len(seq)))
+    if index is None:
+        Q.check_profile_counts(seq, rec, 5)
+        assert Q.expected_launches(seq, 5)[-1] == dict({k: 5 + 1 + 3 for k in Q.STEP_KERNELS}, bin=1 + 4)
+        return
+    with pytest.raises(Q.SequenceMismatch) as e:
+        Q.check_profile_counts(seq, rec, 5)
+    assert e.value.index == index and e.value.op == seq[index] and "density" in e.value.what, e.value
+    with pytest.raises(Q.SequenceMismatch) as e:  # ... and a wrong claim about the start is refused at the start
+        Q.check_profile_counts(seq, rec, 4)
+    assert e.value.index == -1
+
+
+def test_a_handle_without_a_profile_records_none():
+    noisy, quiet, fresh = handles(None)
+    assert Q.run(noisy, quiet, fresh, [STEP, SPEEDS], kit=KIT).profile == {}
+
+
 def test_returned_counts_are_compared():
     class Miscount(Toy):
         def apply_forces(self, forces, dt, counts=True):

@@ -1,7 +1,7 @@
 """Seeded sequences of every single-handle call against a quiet shadow handle (tests/call_sequences.py has the generator,
 the driver and the property): the noisy handle executes every op, the quiet one only the ops that change the state, and
-every read on the noisy handle must give a fresh handle's bits.  The noisy handle is plain, captured (WS_FLAG_GRAPH), in
-IEEE division, on the cost-guided tile schedule, or on merged cells; the quiet one is always direct and unscheduled, in
+every read on the noisy handle must give a fresh handle's bits.  The noisy handle is plain, captured (WS_FLAG_GRAPH),
+profiled (WS_FLAG_PROFILE: its launch counts are checked at every op too), in IEEE division, on the cost-guided tile schedule, or on merged cells; the quiet one is always direct and unscheduled, in
 the same arithmetic (and on the same grid: the summation order follows it).  Each sequence is also replayed on two
 loopback slabs against what its plain run recorded.
 
@@ -215,6 +215,23 @@ def test_captured_steps(ws, kit, seed):
             stale = True
     assert stats["graph_steps"] == before > g0
     print("CALLSEQ " + json.dumps(dict(configuration="graph", seed=seed, fully_replayed_step_ops=dict(replays))))
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_profiled(ws, kit, seed):
+    """profile=True on the noisy handle: its steps carry event brackets and K4 / K5 go through the launch that takes a
+    start / stop event pair (csrc/ws_kernels.hip WS_LAUNCH); the quiet and the fresh handles are unprofiled.  Same bits
+    at every op, and the launch counts after EVERY op are the ones the op list asks for (Q.expected_launches: nothing is
+    read back from the library to make the expectation): the handle's creation binned once and the 20 steps before the
+    first op ran each step kernel 20 times; a step op of variant v adds v to each, a write, a reset and a re-grid one
+    `bin`, edits and reads nothing -- not the unprofiled force pass of ws_read_particles, not the field calls that
+    drain the pending pairs."""
+    seq, rec, stats, _ = _sequence_run(ws, kit, seed, "profiled", lambda *a, **kw: ws.FluidWorker(*a, profile=True, **kw))
+    assert stats["graph_steps"] == 0 and not stats["tile_schedule"]
+    Q.check_profile_counts(seq, rec, STEPS)
+    last = {k: n for k, (_, n) in rec.profile[len(seq) - 1].items()}
+    assert last["density"] == STEPS + sum(op.variant for op in seq if op.cls == "step") > STEPS
+    assert last["bin"] == 1 + sum(op.name in ("write", "reset") or Q.regrids(op) for op in seq) > 1
 
 
 @pytest.mark.parametrize("seed", SEEDS)
