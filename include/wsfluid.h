@@ -1019,6 +1019,98 @@ ws_status ws_read_cohesion(ws_handle *h, const ws_cohesion_params *p, float dt, 
                            float *out_dv, uint32_t *out_neighbours);
 ws_status ws_apply_cohesion(ws_handle *h, const ws_cohesion_params *p, float dt, uint32_t *out_affected);
 
+/* ---- what the fluid carries: per-particle attributes -- paint, mix and sample them (no reference
+ *      counterpart) ----------------------------------------------------------------------------------------------------
+ * Every particle carries one ATTRIBUTE A = (A_0, A_1, A_2, A_3), four floats whose meaning is the host's (RGB dye plus a
+ * temperature, four dyes, ...).  The handle keeps them on the device in ORIGINAL-ID order; nothing of a particle's physics
+ * reads them.  The array is allocated by the first attribute call, all +0, and freed by ws_destroy.  ws_reset returns it
+ * to +0; ws_write_particles, ws_set_params (a re-grid included), ws_slab_rebalance and every step leave it alone.
+ * Below fl() is a rounding to float; arithmetic is IEEE whatever the handle's flags, except where the field says
+ * otherwise: every operation is rounded once, sqrt and division are correctly rounded, nothing is contracted, sums start
+ * at +0 and take their terms in the canonical order; dot is the whitewater block's; x is what ws_read_positions returns.
+ * ws_write_attributes: n*4 floats by id, used as given (a NaN spreads as it would in the host's own arithmetic); NULL =
+ *   all +0.  ws_read_attributes: n*4 floats by id; a handle that never made an attribute call reads all +0.
+ * ws_paint_attributes, per particle, for the brushes e = 0 .. k-1 in the order given, on the RUNNING value of A:
+ *    1. q_a = x_a - c_a; d = sqrt(dot(q, q)).  If !(d < R) go on to the next brush; otherwise the particle is PAINTED by e
+ *       and n_e += 1.
+ *    2. t = d / R; w = 1 - falloff * t; s = strength * w.
+ *    3. For every channel c in `channels`:
+ *         MIX: A_c = fl(fl(1 - s) * A_c) + fl(s * value_c)    (strength 1, falloff 0: a finite A_c becomes value_c exactly)
+ *         ADD: A_c = A_c + fl(s * value_c)
+ *   A particle no brush reaches keeps its four floats bit for bit; channels outside the mask keep theirs.  out_painted,
+ *   if not NULL, receives the k counts n_e.
+ * ws_diffuse_attributes: a kernel-weighted exchange between neighbours -- XSPH's form (Monaghan 1989) applied to A, NOT a
+ *   Laplacian with a physical diffusivity: the spiky kernel's W'(d)/d is unbounded for close pairs, so an explicit
+ *   Laplacian step would not be stable at the host's dt.  r_c = fl(rate_c * dt).
+ *   Candidates of particle i: exactly the cohesion stage's -- the 27 cells of the clamped cell in increasing linear id,
+ *   ids ascending inside a cell, e = x_j - x_i, d2 = dot(e, e), rejected iff d2 > d2_accept.  d = sqrt(d2).  A candidate
+ *   at d == 0 (i itself, a coincident particle) contributes nothing.
+ *   Pass A, once per call: rho_i = the density ws_sample_density_points returns at x_i in its WS_FLAG_IEEE_DIVISION form
+ *   -- the cohesion pass A's rho_i, the same bits.
+ *   Pass B, run `iterations` times, every particle reading the A of the previous iteration.  With S = (+0, +0, +0, +0) and
+ *   c_i = 0, per contributing candidate j (d > 0), in order:
+ *    1. q = 2.0f / (rho_i + rho_j)
+ *    2. w = the density sampler's term at d, (h - d)^2 * pow2, the same bits
+ *    3. g = w * q
+ *    4. S_c = S_c + (A_j,c - A_i,c) * g
+ *    5. c_i += 1
+ *   After the sweep: if c_i == 0 the particle is UNAFFECTED and keeps its bits; otherwise A'_c = A_c + r_c * S_c (the
+ *   product rounded, then the sum) for every channel with rate_c != 0, and a channel with rate_c == 0 keeps its bits.
+ *   out_affected, if not NULL, receives ONE count: the particles with c_i > 0.  A call with iterations = k equals k calls
+ *   with iterations = 1 bit for bit; it bins and runs pass A once.
+ *   Two properties follow.  g_ij and g_ji are the same bits and the differences are exact negatives, so sum_i A_i changes
+ *   only by the rounding of the particles' own sums.  And sum_{j != i} g_ij < 2, because q < 2 / rho_i and sum w <= rho_i:
+ *   with r_c <= 0.5 every A'_i,c is a convex combination of values in i's neighbourhood in exact arithmetic, which is why
+ *   r_c > 0.5 is refused.
+ * ws_sample_attribute_grid / _points: at a node or point exactly ws_sample_velocity_grid / _points with A_j (four
+ *   channels) in place of v_j: per accepted candidate w = the density sampler's term, rho += w, M_c += fl(w * A_j,c);
+ *   value_c = M_c / rho, correctly rounded, where rho > 0, +0 elsewhere.  Only the sqrt inside w follows
+ *   WS_FLAG_IEEE_DIVISION.  out_value: 4 floats per node (nodes x fastest) or point; out_density is bit-identical to
+ *   ws_sample_density_* for the same query; grid and points calls return the same bits at the same place.  Either output
+ *   may be NULL, not both on a single handle.  The typical use: sample at the out_xyz of ws_extract_surface to colour the
+ *   mesh.
+ * Every call waits for enqueued steps, writes nothing ws_step reads and leaves ws_steps_done unchanged; it may be made
+ * between ws_read_positions_begin and _end; a WS_FLAG_GRAPH handle keeps replaying its captured step.  The binning is
+ * recomputed from the current positions on every call that needs neighbours; scratch lives in the sampler's (grow-only).
+ * Slab handles: every call is COLLECTIVE, with the same arguments on every rank.  The attribute array is replicated --
+ *   n_global * 16 bytes on every rank, by global id -- positions come from the gather the field calls make, and every rank
+ *   computes the definition on the global set, so the bits are a single handle's.  A rank that passes every output NULL
+ *   only contributes (and still keeps its replica current).  The verdict of the calls that change A is common: arguments
+ *   are validated after the gather and compared across ranks (ws_write_attributes: a hash of the array); if ranks differ,
+ *   or any rank refuses, ALL return WS_ERR_INVALID_ARG and nothing changes.
+ * Errors, with nothing touched: WS_ERR_INVALID_ARG (a NULL handle, b or p; k outside 1 .. WS_MAX_BRUSHES; a kind above 1;
+ *   channels 0 or above 15; a non-finite value or a magnitude above 1e15 in a brush or in p; radius not > 0; falloff
+ *   outside [0, 1]; a MIX strength outside [0, 1]; a rate below 0; dt not finite or not > 0; any r_c > 0.5; iterations
+ *   outside 1 .. 64; a non-zero reserved; NULL out of ws_read_attributes on a single handle; the density sampler's query
+ *   errors for the two field calls); WS_ERR_UNSUPPORTED (WS_FLAG_REFERENCE_ORDER handles); WS_ERR_OUT_OF_MEMORY (the
+ *   handle stays usable); WS_ERR_HIP on an unusable handle. */
+#define WS_MAX_BRUSHES 16u
+#define WS_BRUSH_MIX 0u
+#define WS_BRUSH_ADD 1u
+typedef struct ws_brush {        /* 48 bytes */
+    uint32_t kind;               /* offset 0:  WS_BRUSH_MIX or WS_BRUSH_ADD */
+    float centre[3];             /* 4  */
+    float radius;                /* 16: R > 0; a particle is in reach iff d < R */
+    float falloff;               /* 20: in [0, 1]: 0 = hard edge, 1 = linear to zero at the rim */
+    float strength;              /* 24: MIX: in [0, 1]; ADD: any finite */
+    uint32_t channels;           /* 28: bit c set = channel c is painted; 1 .. 15 */
+    float value[4];              /* 32 */
+} ws_brush;
+typedef struct ws_diffuse_params {   /* 24 bytes */
+    float rate[4];               /* offset 0: per channel, 1 / time, >= 0; 0 = the channel keeps its bits */
+    uint32_t iterations;         /* 16: 1 .. 64 */
+    uint32_t reserved;           /* 20: must be 0 */
+} ws_diffuse_params;
+/* Host-only (no device needed; WS_ERR_INVALID_ARG for NULL): rate 1, 1, 1, 1; iterations 1; reserved 0. */
+ws_status ws_default_diffuse_params(ws_diffuse_params *out);
+ws_status ws_write_attributes(ws_handle *h, const float *in);
+ws_status ws_read_attributes(ws_handle *h, float *out);
+ws_status ws_paint_attributes(ws_handle *h, const ws_brush *b, uint32_t k, uint32_t *out_painted);
+ws_status ws_diffuse_attributes(ws_handle *h, const ws_diffuse_params *p, float dt, uint32_t *out_affected);
+ws_status ws_sample_attribute_grid(ws_handle *h, const float origin[3], const float spacing[3], const uint32_t dims[3],
+                                   float *out_value, float *out_density);
+ws_status ws_sample_attribute_points(ws_handle *h, const float *xyz, uint32_t m, float *out_value, float *out_density);
+
 /* ---- the fluid acting on things that float in it: buoyancy and drag on host-owned bodies (no reference
  *      counterpart) ----------------------------------------------------------------------------------------------------
  * One-way coupling, water to body.  The HOST owns the bodies, as it owns whitewater's diffuse particles: it describes each

@@ -30,6 +30,7 @@ ws_status slab_reset(ws_handle *h, const float *pos_xyz);
 ws_status slab_write_particles(ws_handle *h, const ws_particle80 *in);
 ws_status slab_regrid(ws_handle *h, const ws_params *params, bool rebalance);
 ws_status slab_field_positions(ws_handle *h, const float **xyz, WsDev *global, bool with_vel);
+ws_status slab_agree_words(ws_handle *h, uint32_t mine, std::vector<uint32_t> *table);
 template <class Call>
 ws_status slab_edit_gathered(ws_handle *h, Call &call);
 ws_status global_grid(const ws_params *params, uint32_t n_global, WsDev *out);
@@ -709,6 +710,7 @@ void free_all(ws_handle *h)
     release_all(h->fixed, h->stage_mem, h->force_cnt, h->solid_sums, h->v_keys, h->v_perm, h->v_tmp, h->v_count, h->v_cursor, h->v_start, h->v_bsum,
                 h->v_off);
     for (auto &volume : h->volume) release_all(volume);
+    release_all(h->attr);
     free_field(h);
 #ifdef WS_WITH_REFCHECK
     ref_free(h);
@@ -1253,6 +1255,8 @@ ws_status ws_reset(ws_handle *h, const float *pos_xyz)
     if (!h || !pos_xyz) return WS_ERR_INVALID_ARG;
     WS_DEAD_CHECK(h);
     HIP_TRY(h, hipSetDevice(h->device));
+    // the attributes return to +0 (include/wsfluid.h; an array that was never allocated is all +0 already)
+    if (h->attr.p) HIP_TRY(h, hipMemsetAsync(h->attr.p, 0, h->attr.bytes, h->stream));
     if (h->slab) return slab_reset(h, pos_xyz);  // pos_xyz: ALL n_global positions, on every rank
     WS_REF_DISPATCH(h, ref_upload_positions(h, pos_xyz));
     return upload_positions(h, pos_xyz);

@@ -26,6 +26,7 @@ void free_field_cells(ws_handle *h)
 void free_field(ws_handle *h)
 {
     auto &F = h->field;
+    release_all(F.sattr[0], F.sattr[1], F.srho, F.aval);
     release_all(F.body, F.cnd, F.crec, F.cst, F.cnb);
     free_field_cells(h);
     release_all(F.xyz, F.keys, F.tmp, F.perm, F.spos, F.q, F.rho, F.grad, F.code, F.vbase, F.bcnt, F.bstart, F.bstate, F.tri,
@@ -934,6 +935,259 @@ ws_status body_forces(ws_handle *h, const ws_body_params *p, const float *xyz, c
                             {out_wet, d_wet, NB * 4}, {out_sforce, d_sforce, M * 12}, {out_sfrac, d_sfrac, M * 4}});
 }
 
+// ---- per-particle attributes (include/wsfluid.h defines paint, diffusion and the field) ---------------------------------
+// The array lives in ws_handle::attr, by id: n float4, on slab handles n_global (replicated).
+uint32_t attr_count(const ws_handle *h) { return h->slab ? h->slab->n_global : h->n; }
+
+// the array, all +0, on the first call that needs it
+ws_status attr_ensure(ws_handle *h)
+{
+    if (h->attr.p) return WS_OK;
+    const size_t bytes = (size_t)attr_count(h) * 16;
+    const ws_status st = h->attr.alloc(h, bytes, "attribute array");
+    if (st) return st;
+    if (hipMemsetAsync(h->attr.p, 0, bytes, h->stream) != hipSuccess) {
+        (void)hipGetLastError();
+        h->attr.release();
+        return fail(h, WS_ERR_HIP, "attribute array");
+    }
+    return WS_OK;
+}
+
+// the preamble of the attribute calls: a dead handle, the reference-order validation mode
+ws_status attr_enter(ws_handle *h)
+{
+    FieldCtx c;
+    c.want = true;
+    return field_enter(h, c, "attributes", nullptr);
+}
+
+// FNV-1a over bytes: a call's arguments in the slabs' agreement (slab_edit_gathered's word)
+struct AttrHash {
+    uint32_t word = 2166136261u;
+    void mix(const void *p, size_t bytes)
+    {
+        for (size_t b = 0; b < bytes; b++) word = (word ^ static_cast<const uint8_t *>(p)[b]) * 16777619u;
+    }
+};
+
+// The verdict of a call that changes the attributes, before it has changed anything.  why: the argument error, or
+// nullptr; mine: a failure of this rank's own (an allocation), with its text in h->err.  A single handle answers for
+// itself.  Slab handles make the verdict common: bit 0 of the agreed word = this rank refuses, the rest = the hash of its
+// arguments; ranks that differ, or any of which refuses, ALL return WS_ERR_INVALID_ARG.
+ws_status attr_verdict(ws_handle *h, const char *why, ws_status mine, uint32_t hash)
+{
+    if (h->slab && h->slab->world > 1) {
+        const std::string mine_text = h->err;
+        const uint32_t word = (hash << 1) | ((why || mine) ? 1u : 0u);
+        std::vector<uint32_t> tab;
+        const ws_status st = slab_agree_words(h, word, &tab);
+        if (st) return st;
+        bool anybody = false, differ = false;
+        for (uint32_t r = 0; r < h->slab->world; r++) {
+            anybody = anybody || (tab[4 * r] & 1u);
+            differ = differ || (tab[4 * r] >> 1) != (word >> 1);
+        }
+        if (why) return fail(h, WS_ERR_INVALID_ARG, why);
+        if (mine) return fail(h, mine, mine_text.c_str());
+        if (anybody) return fail(h, WS_ERR_INVALID_ARG, "attributes: another slab refused its arguments; nothing was changed");
+        if (differ) return fail(h, WS_ERR_INVALID_ARG, "attributes: the slabs were given different arguments; nothing was changed");
+        return WS_OK;
+    }
+    if (why) return fail(h, WS_ERR_INVALID_ARG, why);
+    return mine;
+}
+
+// field_source for the calls that change the attributes: the positions by id and the grid they are binned on.  What a
+// slab's peers take part in (the gather) fails through the return value; what is this rank's alone (the scratch) comes
+// back in *mine and goes into the common verdict, so that no peer waits there for a rank that has left.
+ws_status attr_positions(ws_handle *h, FieldCtx *c, ws_status *mine)
+{
+    *mine = WS_OK;
+    c->want = true;
+    c->inputs = FIELD_POSITIONS;
+    c->contributed = false;
+    HIP_TRY(h, hipSetDevice(h->device));
+    c->d = h->dev;
+    c->n = h->n;
+    if (h->slab) {
+        const ws_status st = slab_field_positions(h, &c->pos, &c->d, false);
+        if (st) return st;
+        c->n = h->slab->n_global;
+    }
+    *mine = field_alloc(h, c->n, c->d.ncells);
+    if (!*mine && !h->slab) {
+        wsk_gather_positions(h->stream, h->cur, h->field.xyz.p, c->n);
+        c->pos = h->field.xyz.p;
+    }
+    return WS_OK;
+}
+
+ws_status write_attributes(ws_handle *h, const float *in)
+{
+    ws_status st = attr_enter(h);
+    if (st) return st;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const ws_status mine = attr_ensure(h);
+    const size_t n = attr_count(h);
+    uint64_t hash = 14695981039346656037ull;  // (volume_hash's form, folded to the agreement's word)
+    if (in && h->slab) hash = volume_mix(hash, in, n * 4);
+    const uint32_t given = in ? 1u : 0u;
+    if ((st = attr_verdict(h, nullptr, mine, ((uint32_t)(hash ^ (hash >> 32)) << 1) | given))) return st;
+    if (in) HIP_TRY(h, hipMemcpyAsync(h->attr.p, in, n * 16, hipMemcpyHostToDevice, h->stream));
+    else HIP_TRY(h, hipMemsetAsync(h->attr.p, 0, n * 16, h->stream));
+    return field_finish(h, {});
+}
+
+ws_status read_attributes(ws_handle *h, float *out)
+{
+    ws_status st = attr_enter(h);
+    if (st) return st;
+    if (!out) return h->slab ? WS_OK : fail(h, WS_ERR_INVALID_ARG, "attributes: out is NULL");
+    HIP_TRY(h, hipSetDevice(h->device));
+    if ((st = attr_ensure(h))) return st;
+    return field_finish(h, {{out, h->attr.p, (size_t)attr_count(h) * 16}});
+}
+
+// the argument errors of ws_paint_attributes (nullptr = acceptable)
+const char *brush_refusal(const ws_brush *b, uint32_t k)
+{
+    if (!b) return "attributes: b is NULL";
+    if (k < 1u || k > WS_MAX_BRUSHES) return "attributes: k outside 1 .. WS_MAX_BRUSHES";
+    for (uint32_t e = 0; e < k; e++) {
+        if (b[e].kind > WS_BRUSH_ADD) return "attributes: unknown brush kind";
+        if (b[e].channels < 1u || b[e].channels > 15u) return "attributes: channels must lie in 1 .. 15";
+        for (int c = 0; c < 3; c++)
+            if (ws_bad_float(b[e].centre[c])) return "attributes: a brush must be finite and at most 1e15 in magnitude";
+        for (int c = 0; c < 4; c++)
+            if (ws_bad_float(b[e].value[c])) return "attributes: a brush must be finite and at most 1e15 in magnitude";
+        if (ws_bad_float(b[e].radius) || ws_bad_float(b[e].falloff) || ws_bad_float(b[e].strength))
+            return "attributes: a brush must be finite and at most 1e15 in magnitude";
+        if (!(b[e].radius > 0.f)) return "attributes: radius must be > 0";
+        if (!(b[e].falloff >= 0.f && b[e].falloff <= 1.f)) return "attributes: falloff must lie in [0, 1]";
+        if (b[e].kind == WS_BRUSH_MIX && !(b[e].strength >= 0.f && b[e].strength <= 1.f))
+            return "attributes: a MIX strength must lie in [0, 1]";
+    }
+    return nullptr;
+}
+
+// ws_paint_attributes: the positions by id, one streaming pass over the array; the per-brush counts through the emitters'
+// counters (ws_handle::force_cnt).
+ws_status paint_attributes(ws_handle *h, const ws_brush *b, uint32_t k, uint32_t *out_painted)
+{
+    ws_status st = attr_enter(h);
+    if (st) return st;
+    const char *why = brush_refusal(b, k);
+    if (why && !h->slab) return fail(h, WS_ERR_INVALID_ARG, why);
+    FieldCtx c;
+    ws_status mine = WS_OK;
+    if ((st = attr_positions(h, &c, &mine))) return st;
+    if (!mine) mine = attr_ensure(h);
+    WsBrushArgs args{};
+    AttrHash hash;
+    hash.mix(&k, 4);
+    if (!why) {
+        memcpy(args.bs.e, b, (size_t)k * sizeof(ws_brush));
+        args.k = k;
+        hash.mix(b, (size_t)k * sizeof(ws_brush));
+        if (!mine && out_painted) {
+            mine = scratch_zeroed(h, h->force_cnt, WS_MAX_BRUSHES * 4, "brush counters");
+            args.painted = h->force_cnt.p;
+        }
+    }
+    if ((st = attr_verdict(h, why, mine, hash.word))) return st;
+    wsk_attr_paint(h->stream, args, c.pos, h->attr.p, c.n);
+    HIP_TRY(h, hipGetLastError());
+    return field_finish(h, {{out_painted, h->force_cnt.p, (size_t)k * 4}});
+}
+
+// the argument errors of ws_diffuse_attributes (nullptr = acceptable); r = fl(rate * dt) per channel
+const char *diffuse_refusal(const ws_diffuse_params *p, float dt, float r[4])
+{
+    if (!p) return "attributes: p is NULL";
+    if (p->reserved != 0u) return "attributes: reserved must be 0";
+    if (p->iterations < 1u || p->iterations > 64u) return "attributes: iterations must lie in 1 .. 64";
+    if (!isfinite(dt) || !(dt > 0.f)) return "attributes: dt must be finite and > 0";
+    for (int c = 0; c < 4; c++) {
+        if (ws_bad_float(p->rate[c])) return "attributes: the rates must be finite and at most 1e15 in magnitude";
+        if (p->rate[c] < 0.f) return "attributes: the rates must be >= 0";
+        r[c] = p->rate[c] * dt;
+        if (!(r[c] <= 0.5f)) return "attributes: rate * dt must be at most 0.5";
+    }
+    return nullptr;
+}
+
+// ws_diffuse_attributes: the binning, the attributes gathered into cell order and pass A once; pass B `iterations` times
+// between the two cell-ordered arrays; one scatter back by id.  The count goes through the cohesion edit's partial counters.
+ws_status diffuse_attributes(ws_handle *h, const ws_diffuse_params *p, float dt, uint32_t *out_affected)
+{
+    ws_status st = attr_enter(h);
+    if (st) return st;
+    float r[4] = {0.f, 0.f, 0.f, 0.f};
+    const char *why = diffuse_refusal(p, dt, r);
+    if (why && !h->slab) return fail(h, WS_ERR_INVALID_ARG, why);
+    FieldCtx c;
+    ws_status mine = WS_OK;
+    if ((st = attr_positions(h, &c, &mine))) return st;
+    auto &F = h->field;
+    const size_t n = c.n;
+    uint32_t partial[WS_COHESION_SLOTS * WS_COHESION_SLOT_WORDS];
+    if (!mine) mine = attr_ensure(h);
+    if (!mine) mine = F.sattr[0].grow(h, n * 16, kFieldScratch);
+    if (!mine) mine = F.sattr[1].grow(h, n * 16, kFieldScratch);
+    if (!mine) mine = F.srho.grow(h, n * 4, kFieldScratch);
+    if (!mine && out_affected) mine = scratch_zeroed(h, h->force_cnt, sizeof partial, "diffusion counters");
+    AttrHash hash;
+    hash.mix(&dt, 4);
+    if (!why) hash.mix(p, sizeof *p);
+    if ((st = attr_verdict(h, why, mine, hash.word))) return st;
+    if ((st = field_bin_particles(h, c))) return st;
+    hipStream_t s = h->stream;
+    wsk_attr_gather(s, F.spos.p, h->attr.p, F.sattr[0].p, c.n);
+    wsk_attr_density(s, c.d, F.start.p, F.spos.p, F.srho.p, c.n);
+    for (uint32_t it = 0; it < p->iterations; it++)
+        wsk_attr_diffuse(s, c.d, F.start.p, F.spos.p, F.srho.p, F.sattr[it & 1u].p, r, F.sattr[(it + 1u) & 1u].p,
+                         it == 0u && out_affected ? h->force_cnt.p : nullptr, c.n);
+    wsk_attr_scatter(s, F.spos.p, F.sattr[p->iterations & 1u].p, h->attr.p, c.n);
+    HIP_TRY(h, hipGetLastError());
+    if ((st = field_finish(h, {{out_affected ? partial : nullptr, h->force_cnt.p, sizeof partial}}))) return st;
+    if (out_affected) {
+        uint32_t total = 0;
+        for (uint32_t t = 0; t < WS_COHESION_SLOTS; t++) total += partial[t * WS_COHESION_SLOT_WORDS];
+        *out_affected = total;
+    }
+    return WS_OK;
+}
+
+// ws_sample_attribute_grid / _points: sample_velocity with the attributes gathered into cell order in place of the
+// velocities.  The query is the density sampler's, errors included.
+ws_status sample_attributes(ws_handle *h, const FieldQuery &q, float *out_val, float *out_rho)
+{
+    FieldCtx c;
+    c.want = out_val || out_rho;
+    if (q.grid && !q.given && (c.want || !h->slab))
+        return fail(h, WS_ERR_INVALID_ARG, "attribute field: origin, spacing and dims are required");
+    ws_status st = field_enter(h, c, "attribute field", "attribute field: both outputs are NULL");
+    if (st) return st;
+    st = field_source(h, &c, FIELD_POSITIONS, [&]() { return field_check(h, q); });
+    if (st || c.contributed) return st;
+    if ((st = field_bin_particles(h, c))) return st;
+    auto &F = h->field;
+    const size_t nq = (size_t)q.count();
+    if (!q.grid && (st = field_upload(h, q))) return st;
+    if (out_rho && (st = F.rho.grow(h, nq * 4, kFieldScratch))) return st;
+    if (out_val) {
+        if ((st = attr_ensure(h))) return st;
+        if ((st = F.sattr[0].grow(h, (size_t)c.n * 16, kFieldScratch))) return st;
+        if ((st = F.aval.grow(h, nq * 16, kFieldScratch))) return st;
+        wsk_attr_gather(h->stream, F.spos.p, h->attr.p, F.sattr[0].p, c.n);
+    }
+    wsk_attr_sample(h->stream, c.d, F.start.p, F.spos.p, F.sattr[0].p, h->ieee, F.q.p, (uint32_t)nq, q.grid6(), q.dims3(),
+                    q.bricks(c.d), out_val ? F.aval.p : nullptr, out_rho ? F.rho.p : nullptr);
+    HIP_TRY(h, hipGetLastError());
+    return field_finish(h, {{out_rho, F.rho.p, nq * 4}, {out_val, F.aval.p, nq * 16}});
+}
+
 }  // namespace
 
 extern "C" {
@@ -1119,6 +1373,55 @@ ws_status ws_read_cohesion(ws_handle *h, const ws_cohesion_params *p, float dt, 
 {
     if (!h) return WS_ERR_INVALID_ARG;
     return read_cohesion(h, p, dt, out_normal, out_density, out_dv, out_neighbours);
+}
+
+// ======================================================================================
+// per-particle attributes: paint, mix and sample them (include/wsfluid.h defines every operation)
+// ======================================================================================
+ws_status ws_default_diffuse_params(ws_diffuse_params *out)
+{
+    if (!out) return WS_ERR_INVALID_ARG;
+    for (float &rate : out->rate) rate = 1.0f;
+    out->iterations = 1u;
+    out->reserved = 0u;
+    return WS_OK;
+}
+
+ws_status ws_write_attributes(ws_handle *h, const float *in)
+{
+    if (!h) return WS_ERR_INVALID_ARG;
+    return write_attributes(h, in);
+}
+
+ws_status ws_read_attributes(ws_handle *h, float *out)
+{
+    if (!h) return WS_ERR_INVALID_ARG;
+    return read_attributes(h, out);
+}
+
+ws_status ws_paint_attributes(ws_handle *h, const ws_brush *b, uint32_t k, uint32_t *out_painted)
+{
+    if (!h) return WS_ERR_INVALID_ARG;
+    return paint_attributes(h, b, k, out_painted);
+}
+
+ws_status ws_diffuse_attributes(ws_handle *h, const ws_diffuse_params *p, float dt, uint32_t *out_affected)
+{
+    if (!h) return WS_ERR_INVALID_ARG;
+    return diffuse_attributes(h, p, dt, out_affected);
+}
+
+ws_status ws_sample_attribute_grid(ws_handle *h, const float origin[3], const float spacing[3], const uint32_t dims[3],
+                                   float *out_value, float *out_density)
+{
+    if (!h) return WS_ERR_INVALID_ARG;
+    return sample_attributes(h, FieldQuery::of_grid(origin, spacing, dims, 1u), out_value, out_density);
+}
+
+ws_status ws_sample_attribute_points(ws_handle *h, const float *xyz, uint32_t m, float *out_value, float *out_density)
+{
+    if (!h) return WS_ERR_INVALID_ARG;
+    return sample_attributes(h, FieldQuery::of_points(xyz, m), out_value, out_density);
 }
 
 // ======================================================================================

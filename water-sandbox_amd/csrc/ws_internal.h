@@ -322,6 +322,11 @@ struct WsField {
     WsScratch<float4> cnd, crec;
     WsScratch<float> cst;
     WsScratch<uint32_t> cnb;
+    // attributes (ws_diffuse_attributes, ws_sample_attribute_*): the attributes in spos' order, twice (the iterations
+    // ping-pong; the field reads the first), the IEEE densities in spos' order, a field call's values (4 per query)
+    WsScratch<float4> sattr[2];
+    WsScratch<float> srho;
+    WsScratch<float4> aval;
     // bodies (ws_body_forces), one array of words: the chunk table (4 per chunk) and the chunks' partial sums (8 per chunk),
     // the bodies' first chunks (nb + 1), the samples (xyz, velocity: 3 floats, volume: 1) and the centres (3 per body), the
     // per-sample results (force: 3, fraction: 1) and the per-body ones (force, torque: 3, volume, wet count: 1)
@@ -388,6 +393,9 @@ struct ws_handle {
     WsScratch<float> volume[WS_MAX_VOLUMES];
     WsVolumeDesc volume_desc[WS_MAX_VOLUMES] = {};
     uint64_t volume_hash[WS_MAX_VOLUMES] = {};
+    // the per-particle attributes: one float4 per particle BY ID (n; on slab handles n_global, replicated on every rank),
+    // allocated all +0 by the first attribute call (p == nullptr: every attribute is +0), zeroed by ws_reset
+    WsScratch<float4> attr;
     bool alias = false;
     size_t grid_alloc_cells = 0;  // cells that count / cursor hold
     // The owners of the arrays above, one per lifetime (ws_api.cpp):
@@ -714,6 +722,29 @@ void wsk_cohesion_unpack(hipStream_t s, const float4 *dvc, const float4 *nrho, f
                          uint32_t n);
 void wsk_state_split(hipStream_t s, const uint32_t *all, const uint32_t *cnt, uint32_t world, uint32_t max_n, size_t stride_words,
                      uint32_t n_global, float *pos, float *vel);
+// per-particle attributes (ws_paint_attributes / ws_diffuse_attributes / ws_sample_attribute_*).  attr: one float4 per
+// particle BY ID (ws_handle::attr).  Paint: the brushes by value, as the emitters; painted = k device words the kernel
+// adds the per-brush counts to, or nullptr; xyz = the positions by id.  Diffusion over the sampler's binning: the gather
+// of attr into spos' order and the scatter back, pass A (srho: the IEEE densities in spos' order) and one iteration of
+// pass B from sa into out (both in spos' order; r4 = fl(rate * dt) per channel; affected = WS_COHESION_SLOTS partial
+// counts as WsCohesionArgs', or nullptr).  The field: wsk_velocity_sample with sa (spos' order) in place of svel and four
+// values per query (value or rho may be nullptr).
+struct WsBrushSet {
+    ws_brush e[WS_MAX_BRUSHES];
+};
+struct WsBrushArgs {
+    WsBrushSet bs;
+    uint32_t k;
+    uint32_t *painted;
+};
+void wsk_attr_paint(hipStream_t s, const WsBrushArgs &a, const float *xyz, float4 *attr, uint32_t n);
+void wsk_attr_gather(hipStream_t s, const float4 *spos, const float4 *attr, float4 *sa, uint32_t n);
+void wsk_attr_scatter(hipStream_t s, const float4 *spos, const float4 *sa, float4 *attr, uint32_t n);
+void wsk_attr_density(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, float *srho, uint32_t n);
+void wsk_attr_diffuse(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, const float *srho, const float4 *sa,
+                      const float *r4, float4 *out, uint32_t *affected, uint32_t n);
+void wsk_attr_sample(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, const float4 *sa, bool ieee,
+                     const float *xyz, uint32_t m, const float *grid6, const uint32_t *dims, bool bricks, float4 *value, float *rho);
 // bodies (ws_body_forces) over the velocity field's binning.  chunks: nchunks x {body, first sample, samples (1 .. the
 // workgroup size), 0}, a body's chunks consecutive and in order; cstart: the first chunk of every body, nb + 1 entries;
 // part: 8 words per chunk (written, then read by the finishing kernel).  One workgroup per chunk sweeps the field at the

@@ -3268,6 +3268,17 @@ __device__ __forceinline__ float4 field_node(const WsFieldGrid &g, uint32_t i, u
 struct FieldAcc {
     float rho, gx, gy, gz;
 };
+// The sums the two field kernels keep per query: FieldAcc, unless the source names an accumulator of its own (Src::Acc).
+template <class Src, class = void>
+struct field_acc {
+    using type = FieldAcc;
+};
+template <class Src>
+struct field_acc<Src, std::void_t<typename Src::Acc>> {
+    using type = typename Src::Acc;
+};
+template <class Src>
+using field_acc_t = typename field_acc<Src>::type;
 
 // One accepted pair.  (ex, ey, ez) = x_p - o (K4's e), d2 its squared length.  Gradient term (o - x_p) * W'(d) / d:
 // IEEE = ((o - x_p) / d) * W'(d) with correctly rounded sqrt and division; default = (o - x_p) * (W'(d) * rcp(d)) with
@@ -3550,7 +3561,7 @@ __global__ void __launch_bounds__(WS_BLOCK) k_field_points(WsDev d, const uint32
 {
     const uint32_t t = blockIdx.x * WS_BLOCK + threadIdx.x;
     if (t >= query.count()) return;
-    store.template put<GRAD>(field_sweep<IEEE, GRAD>(d, start, src, query.at(t)), t);
+    store.template put<GRAD>(field_sweep<IEEE, GRAD, Src, field_acc_t<Src>>(d, start, src, query.at(t)), t);
 }
 
 // Grid form (the hot path): one wave per brick of 4 x 4 x 4 nodes, lane l = node (l & 3, (l >> 2) & 3, l >> 4) of the
@@ -3592,9 +3603,9 @@ __global__ void __launch_bounds__(64) k_field_bricks(WsDev d, const uint32_t *__
     const int ny_c = y1 - y0 + 1;
     const int ncol = (x1 - x0 + 1) * ny_c;
     const size_t at = ((size_t)k * g.ny + j) * g.nx + i;
-    FieldAcc a = {0.f, 0.f, 0.f, 0.f};
+    field_acc_t<Src> a = {};
     if (ncol > FB_COLS) {  // (a spacing the host would not send here: take the points form, lane by lane)
-        if (valid) a = field_sweep<IEEE, GRAD>(d, start, src, o);
+        if (valid) a = field_sweep<IEEE, GRAD, Src, field_acc_t<Src>>(d, start, src, o);
         if constexpr (Store::plain) {
             if (valid) store.template put<GRAD>(a, at);
             return;
@@ -3941,6 +3952,236 @@ void wsk_cohesion_unpack(hipStream_t s, const float4 *dvc, const float4 *nrho, f
                          uint32_t n)
 {
     hipLaunchKernelGGL(k_cohesion_unpack, dim3(cdiv(n, WS_BLOCK)), dim3(WS_BLOCK), 0, s, dvc, nrho, normal, rho, dv, nb, n);
+}
+
+// ---------------------------------------------------------------------------------
+// per-particle attributes (ws_paint_attributes / ws_diffuse_attributes / ws_sample_attribute_*; never inside ws_step)
+//
+// include/wsfluid.h pins every operation.  The attributes live BY ID, one float4 per particle (ws_handle::attr).  Paint is
+// a streaming pass by id with the brushes as a by-value kernel argument (768 B, scalar loads in the wave-uniform loop, as
+// ws_apply_forces carries its emitters).  Diffusion is the cohesion stage's shape: one lane per particle in the sampler's
+// cell order, one field_sweep each, no LDS.  k_attr_density (pass A): the density sampler's IEEE sum at x_i, no gradient.
+// k_attr_diffuse (pass B): positions, densities and attributes IN CELL ORDER, so that a wave's gathers stay inside its
+// neighbourhood -- per contributing candidate two 16-byte loads (position, attribute) and one 4-byte load (density).  The
+// iterations ping-pong between two cell-ordered arrays; one scatter by id follows the last.
+// ---------------------------------------------------------------------------------
+template <bool COUNTS>
+__global__ void __launch_bounds__(WS_BLOCK) k_attr_paint(WsBrushArgs a, const float *__restrict__ xyz, float4 *__restrict__ attr,
+                                                         uint32_t n)
+{
+    const uint32_t i = blockIdx.x * WS_BLOCK + threadIdx.x;
+    const bool active = i < n;
+    float px = 0.f, py = 0.f, pz = 0.f;
+    float4 A = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (active) {
+        px = xyz[3 * (size_t)i];
+        py = xyz[3 * (size_t)i + 1];
+        pz = xyz[3 * (size_t)i + 2];
+        A = attr[i];
+    }
+    bool hit = false;
+    for (uint32_t e = 0; e < a.k; e++) {
+        const ws_brush &b = a.bs.e[e];
+        const float qx = px - b.centre[0], qy = py - b.centre[1], qz = pz - b.centre[2];
+        const float dst = sqrtf(qx * qx + qy * qy + qz * qz);
+        const bool in = active && dst < b.radius;
+        if constexpr (COUNTS) {
+            const uint32_t c = (uint32_t)__popcll(__ballot(in));
+            if (c && (threadIdx.x & 63u) == 0u) atomicAdd(&a.painted[e], c);
+        }
+        if (!in) continue;
+        hit = true;
+        const float t = dst / b.radius;
+        const float w = 1.f - b.falloff * t;
+        const float s = b.strength * w;
+        const float keep = 1.f - s;
+        const bool mix = b.kind == WS_BRUSH_MIX;
+        const auto channel = [&](float &x, uint32_t c) {
+            if (!((b.channels >> c) & 1u)) return;
+            const float add = s * b.value[c];
+            x = mix ? keep * x + add : x + add;
+        };
+        channel(A.x, 0u);
+        channel(A.y, 1u);
+        channel(A.z, 2u);
+        channel(A.w, 3u);
+    }
+    if (hit) attr[i] = A;
+}
+
+void wsk_attr_paint(hipStream_t s, const WsBrushArgs &a, const float *xyz, float4 *attr, uint32_t n)
+{
+    if (!n) return;
+    ws_dispatch([&](auto counts) {
+        hipLaunchKernelGGL(k_attr_paint<counts()>, dim3(cdiv(n, WS_BLOCK)), dim3(WS_BLOCK), 0, s, a, xyz, attr, n);
+    }, a.painted != nullptr);
+}
+
+// sa[j] = the attribute of the particle at sorted slot j (its id rides in spos[j].w)
+__global__ void __launch_bounds__(WS_BLOCK) k_attr_gather(const float4 *__restrict__ spos, const float4 *__restrict__ attr,
+                                                          float4 *__restrict__ sa, uint32_t n)
+{
+    const uint32_t j = blockIdx.x * WS_BLOCK + threadIdx.x;
+    if (j >= n) return;
+    sa[j] = attr[__float_as_uint(spos[j].w)];
+}
+
+void wsk_attr_gather(hipStream_t s, const float4 *spos, const float4 *attr, float4 *sa, uint32_t n)
+{
+    hipLaunchKernelGGL(k_attr_gather, dim3(cdiv(n, WS_BLOCK)), dim3(WS_BLOCK), 0, s, spos, attr, sa, n);
+}
+
+// ... and back: attr[id of slot j] = sa[j]
+__global__ void __launch_bounds__(WS_BLOCK) k_attr_scatter(const float4 *__restrict__ spos, const float4 *__restrict__ sa,
+                                                           float4 *__restrict__ attr, uint32_t n)
+{
+    const uint32_t j = blockIdx.x * WS_BLOCK + threadIdx.x;
+    if (j >= n) return;
+    attr[__float_as_uint(spos[j].w)] = sa[j];
+}
+
+void wsk_attr_scatter(hipStream_t s, const float4 *spos, const float4 *sa, float4 *attr, uint32_t n)
+{
+    hipLaunchKernelGGL(k_attr_scatter, dim3(cdiv(n, WS_BLOCK)), dim3(WS_BLOCK), 0, s, spos, sa, attr, n);
+}
+
+// pass A: srho[i] = the density sampler's IEEE sum at x_i (i's own term included: > 0), in spos' order
+__global__ void __launch_bounds__(WS_BLOCK) k_attr_density(WsDev d, const uint32_t *__restrict__ start,
+                                                           const float4 *__restrict__ spos, float *__restrict__ srho, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * WS_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    srho[i] = field_sweep<true, false>(d, start, FieldIso{spos}, spos[i]).rho;
+}
+
+void wsk_attr_density(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, float *srho, uint32_t n)
+{
+    hipLaunchKernelGGL(k_attr_density, dim3(cdiv(n, WS_BLOCK)), dim3(WS_BLOCK), 0, s, d, start, spos, srho, n);
+}
+
+// Pass B's five-word accumulator and candidate source: the query particle's own attribute and density beside the arrays.
+struct AttrAcc {
+    float s0, s1, s2, s3;
+    uint32_t c;
+};
+struct FieldAttr {
+    const float4 *__restrict__ spos;
+    const float *__restrict__ srho;
+    const float4 *__restrict__ sa;
+    float4 ai;
+    float rhoi;
+    __device__ __forceinline__ float4 at(uint32_t j) const { return spos[j]; }
+    template <bool IEEE, bool GRAD>
+    __device__ __forceinline__ void pair(const WsDev &d, uint32_t j, float, float, float, float d2, AttrAcc &a) const
+    {
+        const float dst = sqrtf(d2);
+        if (!(dst > 0.f)) return;  // i itself, a coincident particle
+        const float4 aj = sa[j];
+        const float q = 2.f / (rhoi + srho[j]);
+        const float g = sk_density(d, dst) * q;
+        a.s0 = a.s0 + (aj.x - ai.x) * g;
+        a.s1 = a.s1 + (aj.y - ai.y) * g;
+        a.s2 = a.s2 + (aj.z - ai.z) * g;
+        a.s3 = a.s3 + (aj.w - ai.w) * g;
+        a.c++;
+    }
+};
+
+// one iteration, cell order in and out; r = fl(rate * dt) per channel (0: the channel keeps its bits).  affected: the
+// WS_COHESION_SLOTS partial counts the first iteration of a call adds to (c_i does not change between iterations), or nullptr.
+__global__ void __launch_bounds__(WS_BLOCK) k_attr_diffuse(WsDev d, const uint32_t *__restrict__ start,
+                                                           const float4 *__restrict__ spos, const float *__restrict__ srho,
+                                                           const float4 *__restrict__ sa, float4 r, float4 *__restrict__ out,
+                                                           uint32_t *__restrict__ affected, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * WS_BLOCK + threadIdx.x;
+    const bool active = i < n;
+    float4 A = make_float4(0.f, 0.f, 0.f, 0.f);
+    AttrAcc a = {};
+    if (active) {
+        A = sa[i];
+        const FieldAttr src = {spos, srho, sa, A, srho[i]};
+        a = field_sweep<true, false, FieldAttr, AttrAcc>(d, start, src, spos[i]);
+    }
+    const bool hit = a.c > 0u;
+    if (affected) {  // (kernel-uniform)
+        const uint32_t k = (uint32_t)__popcll(__ballot(hit));
+        const uint32_t slot = (i >> 6) % WS_COHESION_SLOTS;
+        if (k && (threadIdx.x & 63u) == 0u) atomicAdd(affected + slot * WS_COHESION_SLOT_WORDS, k);
+    }
+    if (!active) return;
+    if (hit) {
+        if (r.x != 0.f) A.x = A.x + r.x * a.s0;
+        if (r.y != 0.f) A.y = A.y + r.y * a.s1;
+        if (r.z != 0.f) A.z = A.z + r.z * a.s2;
+        if (r.w != 0.f) A.w = A.w + r.w * a.s3;
+    }
+    out[i] = A;
+}
+
+void wsk_attr_diffuse(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, const float *srho, const float4 *sa,
+                      const float *r4, float4 *out, uint32_t *affected, uint32_t n)
+{
+    hipLaunchKernelGGL(k_attr_diffuse, dim3(cdiv(n, WS_BLOCK)), dim3(WS_BLOCK), 0, s, d, start, spos, srho, sa,
+                       make_float4(r4[0], r4[1], r4[2], r4[3]), out, affected, n);
+}
+
+// The attribute field's source and store: FieldVel's shape with four moment sums beside rho (an accumulator of its own,
+// AttrFieldAcc) and a store of four quotients.  GRAD = the values are wanted.  A staged candidate is 32 B (position + cell
+// code, and the attribute): FieldVel's chunk and residency.  rho takes the density sampler's operations on the same
+// candidates in the same order: the same bits.
+struct AttrFieldAcc {
+    float rho, m0, m1, m2, m3;
+};
+struct FieldAttrValue {
+    const float4 *__restrict__ spos;
+    const float4 *__restrict__ sa;
+    using Acc = AttrFieldAcc;
+    static constexpr uint32_t chunk = 256;
+    using Payload = float4;
+    template <bool GRAD>
+    static constexpr bool staged = GRAD;
+    __device__ __forceinline__ float4 at(uint32_t j) const { return spos[j]; }
+    __device__ __forceinline__ float4 payload(uint32_t j) const { return sa[j]; }
+    template <bool IEEE, bool GRAD>
+    __device__ __forceinline__ void term(const WsDev &d, float, float, float, float d2, const float4 &v, AttrFieldAcc &a) const
+    {
+        const float w = sk_density(d, ws_sqrt<IEEE>(d2));
+        a.rho += w;
+        if constexpr (GRAD) {
+            a.m0 += w * v.x;
+            a.m1 += w * v.y;
+            a.m2 += w * v.z;
+            a.m3 += w * v.w;
+        }
+    }
+    template <bool IEEE, bool GRAD>
+    __device__ __forceinline__ void pair(const WsDev &d, uint32_t j, float ex, float ey, float ez, float d2, AttrFieldAcc &a) const
+    {
+        term<IEEE, GRAD>(d, ex, ey, ez, d2, GRAD ? sa[j] : float4{}, a);
+    }
+};
+// value = M / rho (correctly rounded whatever the handle's flags) where rho > 0, else four +0: one 16-byte store
+struct StoreAttr {
+    float4 *__restrict__ value;
+    float *__restrict__ rho;
+    static constexpr bool plain = false;
+    template <bool GRAD>
+    __device__ __forceinline__ void put(const AttrFieldAcc &a, size_t at) const
+    {
+        if (rho) rho[at] = a.rho;
+        if constexpr (GRAD) {
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (a.rho > 0.f) v = make_float4(a.m0 / a.rho, a.m1 / a.rho, a.m2 / a.rho, a.m3 / a.rho);
+            value[at] = v;
+        }
+    }
+};
+
+void wsk_attr_sample(hipStream_t s, const WsDev &d, const uint32_t *start, const float4 *spos, const float4 *sa, bool ieee,
+                     const float *xyz, uint32_t m, const float *grid6, const uint32_t *dims, bool bricks, float4 *value, float *rho)
+{
+    field_launch(s, d, start, FieldAttrValue{spos, sa}, StoreAttr{value, rho}, ieee, value != nullptr, xyz, m, grid6, dims, bricks);
 }
 
 // The gathered state records of slab handles (state_record) as positions and velocities by id: what field_source leaves

@@ -57,6 +57,8 @@ ABI_SYMBOLS = [
     "ws_default_whitewater_emit_params", "ws_default_whitewater_step_params", "ws_read_whitewater", "ws_emit_whitewater",
     "ws_step_whitewater", "ws_apply_forces", "ws_default_body_params", "ws_body_forces", "ws_collide_solids",
     "ws_volume_upload", "ws_collide_volumes", "ws_default_cohesion_params", "ws_read_cohesion", "ws_apply_cohesion",
+    "ws_default_diffuse_params", "ws_write_attributes", "ws_read_attributes", "ws_paint_attributes", "ws_diffuse_attributes",
+    "ws_sample_attribute_grid", "ws_sample_attribute_points",
 ]
 
 
@@ -222,6 +224,35 @@ class WsCohesionParams(C.Structure):
     ]
 
 
+WS_BRUSH_MIX, WS_BRUSH_ADD = 0, 1
+WS_MAX_BRUSHES = 16
+
+
+class WsBrush(C.Structure):
+    """ws_brush: one brush of ws_paint_attributes -- a sphere that mixes a value into, or adds it to, the painted channels
+    of the particles in reach (include/wsfluid.h)."""
+
+    _fields_ = [
+        ("kind", C.c_uint32),
+        ("centre", C.c_float * 3),
+        ("radius", C.c_float),
+        ("falloff", C.c_float),
+        ("strength", C.c_float),
+        ("channels", C.c_uint32),
+        ("value", C.c_float * 4),
+    ]
+
+
+class WsDiffuseParams(C.Structure):
+    """ws_diffuse_params: the per-channel rates and the iteration count of ws_diffuse_attributes (include/wsfluid.h)."""
+
+    _fields_ = [
+        ("rate", C.c_float * 4),
+        ("iterations", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
 class WsCamera(C.Structure):
     """ws_camera: pixel (i, j) looks along forward + u * right + w * up from eye (include/wsfluid.h)."""
 
@@ -344,6 +375,13 @@ def bind_library(path):
     L.ws_default_cohesion_params.argtypes = [vp]
     L.ws_read_cohesion.argtypes = [vp, vp, C.c_float, vp, vp, vp, vp]
     L.ws_apply_cohesion.argtypes = [vp, vp, C.c_float, vp]
+    L.ws_default_diffuse_params.argtypes = [vp]
+    L.ws_write_attributes.argtypes = [vp, vp]
+    L.ws_read_attributes.argtypes = [vp, vp]
+    L.ws_paint_attributes.argtypes = [vp, vp, u32, vp]
+    L.ws_diffuse_attributes.argtypes = [vp, vp, C.c_float, vp]
+    L.ws_sample_attribute_grid.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.ws_sample_attribute_points.argtypes = [vp, vp, u32, vp, vp]
     L.ws_default_body_params.argtypes = [vp]
     L.ws_collide_solids.argtypes = [vp, vp, u32, vp, vp, vp]
     L.ws_volume_upload.argtypes = [vp, u32, vp, vp, vp, vp]
@@ -643,6 +681,89 @@ def apply_cohesion(L, h, check, params, dt, count=True):
     out = C.c_uint32(0)
     check(L.ws_apply_cohesion(h, C.byref(params), dt, C.byref(out) if count else None))
     return int(out.value) if count else None
+
+
+def brush(kind, centre, radius, value, strength=1.0, falloff=0.0, channels=15):
+    """One ws_brush: kind = WS_BRUSH_MIX / _ADD (or "mix" / "add"); value = four floats; channels = a bit mask (bit c =
+    channel c is painted) or a sequence of channel numbers."""
+    kind = {"mix": WS_BRUSH_MIX, "add": WS_BRUSH_ADD}.get(kind, kind)
+    if not isinstance(channels, (int, np.integer)):
+        channels = sum(1 << int(c) for c in set(channels))
+    return WsBrush(kind, (C.c_float * 3)(*(float(x) for x in centre)), float(radius), float(falloff), float(strength),
+                   int(channels), (C.c_float * 4)(*(float(x) for x in value)))
+
+
+def diffuse_params(**fields):
+    """ws_default_diffuse_params with the given fields replaced (rate=(r0, r1, r2, r3), iterations=8)."""
+    return _whitewater_params(WsDiffuseParams, load_library().ws_default_diffuse_params, fields)
+
+
+def write_attributes(L, h, check, n, values):
+    """ws_write_attributes: values (n, 4) float32 by id, or None for all +0."""
+    if values is None:
+        check(L.ws_write_attributes(h, None))
+        return
+    a = np.ascontiguousarray(values, np.float32)
+    assert a.size == n * 4, (a.shape, n)
+    check(L.ws_write_attributes(h, a.ctypes.data))
+
+
+def read_attributes(L, h, check, n, want=True):
+    """ws_read_attributes: (n, 4) float32 in original-id order.  want=False (slab handles): return None."""
+    if not want:
+        check(L.ws_read_attributes(h, None))
+        return None
+    out = np.empty((n, 4), np.float32)
+    check(L.ws_read_attributes(h, out.ctypes.data))
+    return out
+
+
+def paint_attributes(L, h, check, brushes, counts=True):
+    """ws_paint_attributes: the brushes (a WsBrush or a sequence of them), in order, on every particle in their reach.
+    Returns the per-brush counts of painted particles (k,) uint32, or None with counts=False."""
+    brushes = [brushes] if isinstance(brushes, WsBrush) else list(brushes)
+    arr = (WsBrush * max(len(brushes), 1))(*brushes)
+    out = np.zeros(max(len(brushes), 1), np.uint32) if counts else None
+    check(L.ws_paint_attributes(h, C.byref(arr), len(brushes), out.ctypes.data if counts else None))
+    return out[:len(brushes)] if counts else None
+
+
+def diffuse_attributes(L, h, check, params, dt, count=True):
+    """ws_diffuse_attributes: params.iterations kernel-weighted exchanges between neighbours at params.rate * dt per
+    channel.  Returns how many particles have a contributing neighbour, or None with count=False."""
+    out = C.c_uint32(0)
+    check(L.ws_diffuse_attributes(h, C.byref(params), dt, C.byref(out) if count else None))
+    return int(out.value) if count else None
+
+
+def sample_attribute_grid(L, h, check, origin, spacing, dims, density=True, want=True):
+    """ws_sample_attribute_grid: (value (nz, ny, nx, 4), density (nz, ny, nx) or None); dims = (nx, ny, nz).
+    want=False (slab handles): contribute to the collective call and return (None, None)."""
+    o = np.ascontiguousarray(origin, np.float32).reshape(3)
+    sp = np.ascontiguousarray(spacing, np.float32).reshape(3)
+    d = np.ascontiguousarray(dims, np.uint32).reshape(3)
+    if not want:
+        check(L.ws_sample_attribute_grid(h, o.ctypes.data, sp.ctypes.data, d.ctypes.data, None, None))
+        return None, None
+    nx, ny, nz = (int(v) for v in d)
+    val = np.empty((nz, ny, nx, 4), np.float32)
+    rho = np.empty((nz, ny, nx), np.float32) if density else None
+    check(L.ws_sample_attribute_grid(h, o.ctypes.data, sp.ctypes.data, d.ctypes.data, val.ctypes.data,
+                                     rho.ctypes.data if density else None))
+    return val, rho
+
+
+def sample_attribute_points(L, h, check, xyz, density=True, want=True):
+    """ws_sample_attribute_points: (value (m, 4), density (m,) or None)."""
+    q = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    m = q.shape[0]
+    if not want:
+        check(L.ws_sample_attribute_points(h, q.ctypes.data, m, None, None))
+        return None, None
+    val = np.empty((m, 4), np.float32)
+    rho = np.empty(m, np.float32) if density else None
+    check(L.ws_sample_attribute_points(h, q.ctypes.data, m, val.ctypes.data, rho.ctypes.data if density else None))
+    return val, rho
 
 
 def solid(kind, centre, size, rot=(1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0), hollow=False, velocity=(0.0, 0.0, 0.0),
@@ -1072,6 +1193,36 @@ class FluidWorker:
         cohesion_params(...), applied to the velocities as one explicit step of dt.  The number of affected particles,
         or None with count=False (the call then only enqueues)."""
         return apply_cohesion(self._L, self._h, self._check, params, dt, count)
+
+    def write_attributes(self, values):
+        """Give every particle its four attribute floats -- dye, temperature, whatever the host means by them: values
+        (n, 4) by id, or None for all +0.  Nothing of the physics reads them; the steps carry them along."""
+        write_attributes(self._L, self._h, self._check, self.n, values)
+
+    def read_attributes(self):
+        """The attributes of every particle, (n, 4) float32 by id."""
+        return read_attributes(self._L, self._h, self._check, self.n)
+
+    def paint_attributes(self, brushes, counts=True):
+        """Paint the particles inside up to 16 spheres: brushes = brush(...) or a list, applied in order.  The per-brush
+        counts of painted particles, or None with counts=False."""
+        return paint_attributes(self._L, self._h, self._check, brushes, counts)
+
+    def diffuse_attributes(self, params, dt, count=True):
+        """Mix the attributes between neighbours: params = diffuse_params(rate=..., iterations=...).  The number of
+        particles with a contributing neighbour, or None with count=False."""
+        return diffuse_attributes(self._L, self._h, self._check, params, dt, count)
+
+    def sample_attribute_grid(self, origin, spacing, dims, density=False):
+        """The attribute field on a grid: value (nz, ny, nx, 4), with density=True (value, density)."""
+        val, rho = sample_attribute_grid(self._L, self._h, self._check, origin, spacing, dims, density)
+        return (val, rho) if density else val
+
+    def sample_attribute_points(self, xyz, density=False):
+        """The attribute field at points -- the vertices of extract_surface, to colour the mesh: value (m, 4), with
+        density=True (value, density)."""
+        val, rho = sample_attribute_points(self._L, self._h, self._check, xyz, density)
+        return (val, rho) if density else val
 
     def collide_solids(self, solids, reaction=True):
         """Put solid things in the water between two steps: solids = solid(...) or a list of up to 16.  Particles nearer

@@ -432,6 +432,43 @@ class FluidWorker {
         return affected;
     }
 
+    // What the fluid carries (include/wsfluid.h ws_write_attributes .. ws_sample_attribute_points): four floats per
+    // particle, by id, kept on the device -- dye, temperature, whatever the host means by them.  Paint them with up to
+    // WS_MAX_BRUSHES spheres, mix them between neighbours, sample them where the mesh's vertices are.
+    void write_attributes(const std::vector<float> &a) { check(ws_write_attributes(h_, a.empty() ? nullptr : a.data())); }
+    std::vector<float> read_attributes()
+    {
+        std::vector<float> out((size_t)n_ * 4);
+        check(ws_read_attributes(h_, out.data()));
+        return out;
+    }
+    std::vector<uint32_t> paint_attributes(const std::vector<ws_brush> &brushes)
+    {
+        std::vector<uint32_t> painted(brushes.size());
+        if (!brushes.empty()) check(ws_paint_attributes(h_, brushes.data(), (uint32_t)brushes.size(), painted.data()));
+        return painted;
+    }
+    uint32_t diffuse_attributes(const ws_diffuse_params &p, float dt)
+    {
+        uint32_t affected = 0;
+        check(ws_diffuse_attributes(h_, &p, dt, &affected));
+        return affected;
+    }
+    // xyz: m * 3 floats; returns m * 4
+    std::vector<float> sample_attribute_points(const std::vector<float> &xyz)
+    {
+        std::vector<float> out(xyz.size() / 3 * 4);
+        if (!out.empty()) check(ws_sample_attribute_points(h_, xyz.data(), (uint32_t)(xyz.size() / 3), out.data(), nullptr));
+        return out;
+    }
+    // dims[0] * dims[1] * dims[2] nodes, x fastest; returns 4 floats per node
+    std::vector<float> sample_attribute_grid(const float origin[3], const float spacing[3], const uint32_t dims[3])
+    {
+        std::vector<float> out((size_t)dims[0] * dims[1] * dims[2] * 4);
+        check(ws_sample_attribute_grid(h_, origin, spacing, dims, out.data(), nullptr));
+        return out;
+    }
+
     std::vector<float> read_speeds()
     {
         std::vector<float> out(n_);

@@ -459,6 +459,35 @@ class SlabWorker:
         parameters); the count is global.  count=False: this rank applies without asking for it (None)."""
         return fluid.apply_cohesion(self._L, self._h, self._check, params, dt, count)
 
+    def write_attributes(self, values):
+        """FluidWorker.write_attributes for the GLOBAL particle set (COLLECTIVE: every rank passes the same (n_global, 4)
+        array, by global id; the attributes are replicated on every rank)."""
+        fluid.write_attributes(self._L, self._h, self._check, self.n_global, values)
+
+    def read_attributes(self, want=True):
+        """FluidWorker.read_attributes of the GLOBAL particle set (COLLECTIVE); want=False: None."""
+        return fluid.read_attributes(self._L, self._h, self._check, self.n_global, want)
+
+    def paint_attributes(self, brushes, counts=True):
+        """FluidWorker.paint_attributes on the GLOBAL particle set (COLLECTIVE: every rank makes the same call with the same
+        brushes); the counts are global.  counts=False: this rank paints its replica without asking for them (None)."""
+        return fluid.paint_attributes(self._L, self._h, self._check, brushes, counts)
+
+    def diffuse_attributes(self, params, dt, count=True):
+        """FluidWorker.diffuse_attributes on the GLOBAL particle set (COLLECTIVE: every rank makes the same call with the
+        same parameters); the count is global.  count=False: this rank mixes its replica without asking for it (None)."""
+        return fluid.diffuse_attributes(self._L, self._h, self._check, params, dt, count)
+
+    def sample_attribute_grid(self, origin, spacing, dims, density=False, want=True):
+        """FluidWorker.sample_attribute_grid over the GLOBAL particle set (COLLECTIVE); want=False: only contribute."""
+        val, rho = fluid.sample_attribute_grid(self._L, self._h, self._check, origin, spacing, dims, density, want)
+        return (val, rho) if density else val
+
+    def sample_attribute_points(self, xyz, density=False, want=True):
+        """FluidWorker.sample_attribute_points over the GLOBAL particle set (COLLECTIVE); want=False: only contribute."""
+        val, rho = fluid.sample_attribute_points(self._L, self._h, self._check, xyz, density, want)
+        return (val, rho) if density else val
+
     def collide_solids(self, solids, reaction=True):
         """FluidWorker.collide_solids on the GLOBAL particle set (COLLECTIVE: every rank makes the same call with the same
         solids); the outputs are global.  reaction=False: this rank applies without asking for them (None)."""
