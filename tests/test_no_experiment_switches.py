@@ -21,8 +21,12 @@ def test_product_sources_have_no_experiment_switches():
         text = open(os.path.join(CSRC, f), errors="replace").read()
         for m in EXPERIMENT_MACROS:
             assert m not in text, "%s mentions %s" % (f, m)
-    # the only conditional compilation left in the kernels: six tuning defaults and the test-only build's include
-    conds = re.findall(r"^#\s*(?:if|ifdef|ifndef)\s+(\w+)", open(os.path.join(CSRC, "ws_kernels.hip")).read(), flags=re.M)
+    # the only conditional compilation left in the kernels -- every .hip file and the device header they share, taken
+    # together: six tuning defaults and the test-only build's include
+    kernel_files = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip")) + ["ws_device.h"]
+    assert "ws_kernels.hip" in kernel_files and len(kernel_files) > 2, kernel_files  # (no file, no check)
+    conds = [c for f in kernel_files
+             for c in re.findall(r"^#\s*(?:if|ifdef|ifndef)\s+(\w+)", open(os.path.join(CSRC, f)).read(), flags=re.M)]
     assert sorted(conds) == sorted(["ND_P", "ND_K", "ND_MASK_WORDS", "NF_WORDSYNC_MAX", "NF_WORDSYNC_MAX_BIG", "NF_WORDSYNC_BIG_TILES", "NF_WORDSYNC_MAX_IEEE", "NF_WORDSYNC_MAX_TINY", "NF_WORDSYNC_TINY_TILES", "NF_P", "NF_P_SMALL", "NF_SMALL_BELOW", "WS_REORDER_BLOCK", "WS_WITH_REFCHECK"]), conds
 
 
@@ -82,6 +86,23 @@ def test_product_build_defines_nothing():
     assert not [f for f in b.HIPCC_FLAGS if f.startswith("-D")], b.HIPCC_FLAGS
     src = open(os.path.join(ROOT, "water-sandbox_amd", "build.py")).read()
     assert re.findall(r'"-D(\w+)', src) == ["WS_WITH_REFCHECK", "WS_DEV_HOOKS"]  # the two test-only libraries alone
+
+
+def test_build_names_every_file_of_csrc():
+    """build.SOURCES names every .hip and .cpp of csrc/ and build.HEADERS covers every .h and .inc there: a file added
+    later cannot be left out of the library, nor out of the staleness rule (build._stale)."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("ws_build", os.path.join(ROOT, "water-sandbox_amd", "build.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    files = sorted(os.listdir(CSRC))
+    assert sorted(b.SOURCES) == [f for f in files if f.endswith((".hip", ".cpp"))], b.SOURCES
+    headers = {os.path.realpath(h) for h in b.HEADERS}
+    for f in files:
+        assert f.endswith((".hip", ".cpp", ".h", ".inc")), "%s: neither a source nor a header" % f
+        if f.endswith((".h", ".inc")):
+            assert os.path.realpath(os.path.join(CSRC, f)) in headers, "%s is not in build.HEADERS" % f
 
 
 def test_host_code_allocates_and_frees_through_the_two_owner_forms_only():

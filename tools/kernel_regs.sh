@@ -1,9 +1,12 @@
 #!/bin/bash
-# Registers / LDS / scratch of every kernel in ws_kernels.hip (device-only assembly, no GPU needed).
-# usage: tools/kernel_regs.sh [extra hipcc flags]   -> /tmp/ws_kernels.s + a table on stdout
+# Registers / LDS / scratch of every kernel in one .hip file of csrc/ (device-only assembly, no GPU needed).
+# usage: tools/kernel_regs.sh [file.hip] [extra hipcc flags]   -> /tmp/ws_kernels.s + a table on stdout
+#   the file defaults to ws_kernels.hip (the step); ws_edits.hip, ws_views.hip and ws_fields.hip are the others
 cd "$(dirname "$0")/.."
+file=ws_kernels.hip
+case "$1" in *.hip) file=$(basename "$1"); shift;; esac
 /opt/rocm/bin/hipcc -x hip --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize --cuda-device-only -S \
-  -Iinclude -Iwater-sandbox_amd/csrc "$@" -o /tmp/ws_kernels.s water-sandbox_amd/csrc/ws_kernels.hip || exit 1
+  -Iinclude -Iwater-sandbox_amd/csrc "$@" -o /tmp/ws_kernels.s water-sandbox_amd/csrc/$file || exit 1
 python3 - <<'PY'
 import re
 txt = open('/tmp/ws_kernels.s').read()

@@ -1,15 +1,20 @@
 """Build libwsfluid.so (HIP kernels + C ABI) in-tree for gfx950 with hipcc."""
 import os
 import subprocess
+import tempfile
+from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libwsfluid.so")
 
-SOURCES = ["ws_kernels.hip", "ws_api.cpp", "ws_rccl.cpp", "ws_local.cpp"]
-HEADERS = [os.path.join(CSRC, "ws_internal.h"), os.path.join(CSRC, "ws_devhooks.h"), os.path.join(CSRC, "ws_slab.inc"),
-           os.path.join(CSRC, "ws_field.inc"), os.path.join(ROOT, "include", "wsfluid.h")]
+# The kernels by call family: the step (ws_kernels.hip -- what the K4 / K5 tools and tests compile), the between-step
+# edits, the read-backs and id-ordered views, the field calls; ws_device.h is what they share.  Every file of csrc/ is
+# named here or in HEADERS (tests/test_no_experiment_switches.py), so none escapes the staleness rule.
+SOURCES = ["ws_kernels.hip", "ws_edits.hip", "ws_views.hip", "ws_fields.hip", "ws_api.cpp", "ws_rccl.cpp", "ws_local.cpp"]
+HEADERS = [os.path.join(CSRC, "ws_internal.h"), os.path.join(CSRC, "ws_device.h"), os.path.join(CSRC, "ws_devhooks.h"),
+           os.path.join(CSRC, "ws_slab.inc"), os.path.join(CSRC, "ws_field.inc"), os.path.join(ROOT, "include", "wsfluid.h")]
 # Test-only build of the same sources plus the reference-order validation mode (tests/refcheck/: a literal HIP
 # restatement of the reference's six WGSL passes and its host glue, used by the tests as a second, independent
 # restatement).  Sources and binary live under tests/; it is built by __graft_entry__.build() and is never loaded by the
@@ -51,13 +56,29 @@ def needs_build():
     return _stale(LIB)
 
 
-def _compile(lib, defines, verbose):
-    cmd = [hipcc()] + HIPCC_FLAGS + defines + [
-        "-I", os.path.join(ROOT, "include"), "-I", CSRC, "-o", lib,
-    ] + [os.path.join(CSRC, s) for s in SOURCES] + ["-ldl"]
+LINK_ONLY = ("-shared",)  # of HIPCC_FLAGS, what a compile to an object leaves out ...
+SOURCE_ONLY = ("-x", "hip")  # ... and what the link of the objects leaves out
+
+
+def _run(cmd, verbose):
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
+
+
+def _compile(lib, defines, verbose):
+    """One library: its sources to objects side by side (every translation unit parses the HIP headers again, so one
+    after the other would cost more than the single file did), then the link.  The objects live in a directory of this
+    call's own: no flavour sees another's."""
+    compile_flags = [f for f in HIPCC_FLAGS if f not in LINK_ONLY] + defines + ["-I", os.path.join(ROOT, "include"), "-I", CSRC]
+    with tempfile.TemporaryDirectory(prefix="wsfluid_obj_") as tmp:
+        objs = [os.path.join(tmp, s + ".o") for s in SOURCES]
+        with ThreadPoolExecutor(max_workers=min(len(SOURCES), 16)) as pool:
+            jobs = [pool.submit(_run, [hipcc()] + compile_flags + ["-c", "-o", o, os.path.join(CSRC, s)], verbose)
+                    for s, o in zip(SOURCES, objs)]
+            for j in jobs:
+                j.result()
+        _run([hipcc()] + [f for f in HIPCC_FLAGS if f not in SOURCE_ONLY] + ["-o", lib] + objs + ["-ldl"], verbose)
     return lib
 
 

@@ -1,6 +1,6 @@
 // ws_api.cpp -- the C ABI of include/wsfluid.h: handle lifetime, device buffers, the
 // per-step launch sequence and the readback paths.  Host-only logic; all device work is
-// in ws_kernels.hip.  The role played here is the one bevy_app_compute's
+// in the .hip files.  The role played here is the one bevy_app_compute's
 // AppComputeWorker plays in the reference (src/fluid_compute.rs:277-366,:393-397).
 #include <math.h>
 #include <stdio.h>
@@ -1532,36 +1532,27 @@ float solids_reach2(const ws_solid &o)
     return reach2_of(reach);
 }
 
-struct SolidsCall {
-    const ws_solid *s;
-    uint32_t k;
+// The reaction of ws_collide_solids and ws_collide_volumes, one part for both: the caller's three outputs, the device
+// accumulator words (the handle's solid_sums) and the host's copy of them.
+struct Reaction {
     uint32_t *out_contacts;
     double *out_impulse, *out_angular;
-    const char *tag = "solids", *things = "solids";
-    WsSolidArgs args{};
+    static_assert(WS_MAX_SOLIDS == WS_MAX_VOLUME_POSES, "one array of sums serves the solids and the poses");
     unsigned long long sums[WS_MAX_SOLIDS * WS_SOLID_WORDS];  // fetch()'s copy of the accumulator words
     bool react() const { return out_contacts || out_impulse || out_angular; }
-    const char *refuse() const { return solids_refusal(s, k); }
-    ws_status prepare(ws_handle *h, const WsGathered *)  // the solids' bytes as given, and each one's reach
+    // the kernel's `sums` argument: nullptr if nobody asks, else the scratch grown and zeroed on the handle's stream
+    // (`what` names it in an allocation error)
+    ws_status prepare(ws_handle *h, const char *what, unsigned long long **args_sums)
     {
-        memcpy(args.ss.e, s, (size_t)k * sizeof(ws_solid));
-        for (uint32_t e = 0; e < k; e++) args.ss.reach2[e] = solids_reach2(s[e]);
-        args.k = k;
         if (!react()) return WS_OK;
-        const ws_status st = scratch_zeroed(h, h->solid_sums, sizeof sums, "solid reaction sums");
-        args.sums = h->solid_sums.p;
+        const ws_status st = scratch_zeroed(h, h->solid_sums, sizeof sums, what);
+        *args_sums = h->solid_sums.p;
         return st;
-    }
-    template <class M>
-    void mix(M m, bool valid) const
-    {
-        m(&k, 4);
-        if (valid) m(s, (size_t)k * sizeof(ws_solid));
     }
     hipError_t fetch(ws_handle *h) { return react() ? copy_now(h, sums, h->solid_sums.p, sizeof sums, hipMemcpyDeviceToHost) : hipSuccess; }
     // the accumulator words as the caller's outputs: counts, and the fixed-point sums as (double)sum * 2^-24.  Only after
     // the whole call has succeeded -- on slab handles after the edit has been agreed on: a refused call writes nothing.
-    void outputs() const
+    void outputs(uint32_t k) const
     {
         for (uint32_t e = 0; react() && e < k; e++) {
             const unsigned long long *w = sums + (size_t)e * WS_SOLID_WORDS;
@@ -1574,6 +1565,30 @@ struct SolidsCall {
     }
 };
 
+struct SolidsCall {
+    const ws_solid *s;
+    uint32_t k;
+    Reaction reaction;
+    const char *tag = "solids", *things = "solids";
+    WsSolidArgs args{};
+    const char *refuse() const { return solids_refusal(s, k); }
+    ws_status prepare(ws_handle *h, const WsGathered *)  // the solids' bytes as given, and each one's reach
+    {
+        memcpy(args.ss.e, s, (size_t)k * sizeof(ws_solid));
+        for (uint32_t e = 0; e < k; e++) args.ss.reach2[e] = solids_reach2(s[e]);
+        args.k = k;
+        return reaction.prepare(h, "solid reaction sums", &args.sums);
+    }
+    template <class M>
+    void mix(M m, bool valid) const
+    {
+        m(&k, 4);
+        if (valid) m(s, (size_t)k * sizeof(ws_solid));
+    }
+    hipError_t fetch(ws_handle *h) { return reaction.fetch(h); }
+    void outputs() const { reaction.outputs(k); }
+};
+
 }  // namespace
 
 extern "C" {
@@ -1581,7 +1596,7 @@ extern "C" {
 ws_status ws_collide_solids(ws_handle *h, const ws_solid *s, uint32_t k, uint32_t *out_contacts, double *out_impulse,
                             double *out_angular)
 {
-    SolidsCall call{s, k, out_contacts, out_impulse, out_angular};
+    SolidsCall call{s, k, {out_contacts, out_impulse, out_angular}};
     const ws_status st = edit_fluid(h, call);
     if (!st) call.outputs();
     return st;
@@ -1671,12 +1686,9 @@ struct VolumesCall {
     const ws_handle *owner;  // whose slots the poses name
     const ws_volume_pose *v;
     uint32_t k;
-    uint32_t *out_contacts;
-    double *out_impulse, *out_angular;
+    Reaction reaction;
     const char *tag = "volumes", *things = "poses or volumes";
     WsVolumeArgs args{};
-    unsigned long long sums[WS_MAX_VOLUME_POSES * WS_SOLID_WORDS];  // fetch()'s copy of the accumulator words
-    bool react() const { return out_contacts || out_impulse || out_angular; }
     const char *refuse() const { return volumes_refusal(owner, v, k); }
     ws_status prepare(ws_handle *h, const WsGathered *)  // the slots as they are now, the poses' bytes as given, and each one's reach
     {
@@ -1684,10 +1696,7 @@ struct VolumesCall {
         memcpy(args.vs.e, v, (size_t)k * sizeof(ws_volume_pose));
         for (uint32_t e = 0; e < k; e++) args.vs.reach2[e] = volumes_reach2(v[e], h->volume_desc[v[e].slot]);
         args.k = k;
-        if (!react()) return WS_OK;
-        const ws_status st = scratch_zeroed(h, h->solid_sums, sizeof sums, "volume reaction sums");
-        args.sums = h->solid_sums.p;
-        return st;
+        return reaction.prepare(h, "volume reaction sums", &args.sums);
     }
     // (valid: every slot the poses name is below WS_MAX_VOLUMES and holds a volume)
     template <class M>
@@ -1702,18 +1711,8 @@ struct VolumesCall {
             if (used) m(&owner->volume_hash[s], 8);  // (covers dims, origin, spacing and the array: ws_volume_upload)
         }
     }
-    hipError_t fetch(ws_handle *h) { return react() ? copy_now(h, sums, h->solid_sums.p, sizeof sums, hipMemcpyDeviceToHost) : hipSuccess; }
-    void outputs() const  // (SolidsCall::outputs: only after the whole call has succeeded)
-    {
-        for (uint32_t e = 0; react() && e < k; e++) {
-            const unsigned long long *w = sums + (size_t)e * WS_SOLID_WORDS;
-            if (out_contacts) out_contacts[e] = (uint32_t)w[0];
-            for (int c = 0; c < 3; c++) {
-                if (out_impulse) out_impulse[3 * e + c] = (double)(long long)w[1 + c] * 0x1p-24;
-                if (out_angular) out_angular[3 * e + c] = (double)(long long)w[4 + c] * 0x1p-24;
-            }
-        }
-    }
+    hipError_t fetch(ws_handle *h) { return reaction.fetch(h); }
+    void outputs() const { reaction.outputs(k); }  // (Reaction::outputs: only after the whole call has succeeded)
 };
 
 }  // namespace
@@ -1759,7 +1758,7 @@ ws_status ws_volume_upload(ws_handle *h, uint32_t slot, const float origin[3], c
 ws_status ws_collide_volumes(ws_handle *h, const ws_volume_pose *v, uint32_t k, uint32_t *out_contacts, double *out_impulse,
                              double *out_angular)
 {
-    VolumesCall call{h, v, k, out_contacts, out_impulse, out_angular};
+    VolumesCall call{h, v, k, {out_contacts, out_impulse, out_angular}};
     const ws_status st = edit_fluid(h, call);
     if (!st) call.outputs();
     return st;

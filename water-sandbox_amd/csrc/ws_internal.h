@@ -562,7 +562,7 @@ struct WsSlab {
 // ws_rccl.cpp (not part of the public header): no-op for a transport that is not the library's own
 extern "C" void ws_rccl_transport_bind_stream(const ws_transport *t, void *stream);
 
-// ---- kernel launchers (ws_kernels.hip) -------------------------------------------
+// ---- kernel launchers (ws_kernels.hip: the step; ws_edits.hip, ws_views.hip, ws_fields.hip: the calls around it) ----
 void wsk_upload_positions(hipStream_t s, const float *xyz_dev, WsSoA cur, uint32_t n);
 void wsk_upload_particles(hipStream_t s, const ws_particle80 *in_dev, WsSoA cur, uint32_t n);
 void wsk_bin(hipStream_t s, const WsDev &d, WsSoA cur, uint32_t *cid, uint32_t *count);  // (cur / cid from the first particle to bin)
@@ -574,7 +574,7 @@ void wsk_scatter(hipStream_t s, const uint32_t *keys, uint32_t *cursor, uint32_t
 void wsk_reorder(hipStream_t s, const WsDev &d, const uint32_t *slot_tmp, const uint32_t *cid_cur, const uint32_t *start, WsSoA cur,
                  WsSorted srt, uint32_t *cid_srt, WsXYZ sxyz, bool recompute_pred);
 void wsk_refresh_pred(hipStream_t s, const WsDev &d, WsSoA cur);
-// The between-step edits (ws_apply_forces, ws_collide_solids): what a call hands its kernel, ONE by-value kernel argument
+// The between-step edits (ws_apply_forces, ws_collide_solids; ws_edits.hip): what a call hands its kernel, ONE by-value kernel argument
 // whose objects the wave-uniform loop reads through scalar loads.  outputs(): whether the call wants the kernel's sums.
 // Forces: affected = k device words the kernel adds the per-emitter counts to, or nullptr.
 // Solids: each solid with its squared reach -- the squared distance from its centre beyond which no particle can be in
@@ -661,7 +661,7 @@ void wsk_gather_speeds(hipStream_t s, WsSoA cur, float *out, uint32_t n);
 void wsk_gather_velocities(hipStream_t s, WsSoA cur, float *out_xyz, uint32_t n);
 void wsk_gather_particles(hipStream_t s, WsSoA cur, WsSorted srt, const float4 *accel, bool have_step,
                           const WsPressureParams &pp, ws_particle80 *out, uint32_t n);
-// reference-layout view
+// reference-layout view (ws_views.hip, as the read-backs above it)
 void wsk_view_keys(hipStream_t s, const WsDev &d, WsSorted srt, uint32_t *keys_by_id, uint32_t *count);
 void wsk_view_count(hipStream_t s, const uint32_t *keys, uint32_t *count, uint32_t n);
 void wsk_view_fix(hipStream_t s, const uint32_t *tmp, const uint32_t *keys, const uint32_t *start,
@@ -669,7 +669,7 @@ void wsk_view_fix(hipStream_t s, const uint32_t *tmp, const uint32_t *keys, cons
 void wsk_view_offsets(hipStream_t s, const uint32_t *start, uint32_t *off, uint32_t n);
 void wsk_iota(hipStream_t s, uint32_t *p, uint32_t n);
 void wsk_set_words4(hipStream_t s, uint32_t *p, uint32_t a, uint32_t b, uint32_t c, uint32_t d);
-// density field sampler (ws_sample_density_*)
+// density field sampler (ws_sample_density_*; from here to the surface extraction: ws_fields.hip)
 void wsk_field_keys(hipStream_t s, const WsDev &d, const float *xyz, uint32_t *keys, uint32_t n);
 void wsk_field_gather(hipStream_t s, const uint32_t *perm, const float *xyz, float4 *spos, uint32_t n);
 // grid6 = origin xyz, spacing xyz (nullptr: the m points of xyz); bricks: the brick kernel (grid only); smf = nullptr:
@@ -801,7 +801,7 @@ void wsk_halo_unpack(hipStream_t s, const WsDev &d, uint32_t *start, WsSorted sr
 void wsk_gather_slab(hipStream_t s, const WsDev &d, WsSoA cur, WsSorted srt, const float4 *accel, bool have_step,
                      const WsPressureParams &pp, ws_particle80 *out, uint32_t *ids);
 void wsk_upload_positions_ids(hipStream_t s, const float *xyz_dev, const uint32_t *ids_dev, WsSoA cur, uint32_t n);
-// id-ordered global views / loads of slab handles (ws_kernels.hip "slab handles: the id-ordered GLOBAL views")
+// id-ordered global views / loads of slab handles (ws_views.hip "slab handles: the id-ordered GLOBAL views")
 enum { WS_PACK_POS_H = 0, WS_PACK_SPEED_H = 1, WS_PACK_RECORD_H = 2, WS_PACK_STATE_H = 3, WS_PACK_KEY_H = 4, WS_PACK_POSVEL_H = 5 };
 uint32_t wsk_pack_words(int kind);  // payload words per record (the record carries one more: the particle id)
 void wsk_slab_pack(hipStream_t s, const WsDev &d, int kind, WsSoA cur, WsSorted srt, const float4 *accel, bool have_step,
