@@ -1166,6 +1166,73 @@ ws_status ws_body_forces(ws_handle *h, const ws_body_params *p, const float *sam
                          uint32_t nb, float *out_force, float *out_torque, float *out_volume, uint32_t *out_wet,
                          float *out_sample_force, float *out_sample_fraction);
 
+/* ---- pouring water in and draining it: the particle count as a variable (no reference counterpart) -----
+ * ws_create fixes a handle's particle count n and its CAPACITY, the particles its arrays hold, at the same value.  The
+ * three count-changing calls below add particles at the end of the id range or remove some and renumber the rest, on the
+ * device, between two steps: stream-ordered after the steps enqueued so far, before the next ws_step, and SYNCHRONOUS --
+ * each returns with the new count visible in ws_num_particles (a removal waits for one 4-byte readback, the survivor
+ * count, next to the per-sink counts; an addition may wait too).  x, v are what ws_read_positions / ws_read_velocities
+ * return; fl() is a rounding to float; arithmetic is IEEE whatever the handle's flags: every operation is rounded once,
+ * sqrt is correctly rounded, nothing is contracted; dot() is ws_apply_forces'.
+ * ws_remove_particles, per particle, for the sinks e = 0 .. k-1 in the order given (c = centre):
+ *   1. q_a = x_a - c_a.  WS_SINK_SPHERE contains the particle iff d < R with d = sqrt(dot(q, q)) and R = half[0] -- step 1
+ *      of ws_apply_forces, operation for operation.  WS_SINK_BOX contains it iff fabsf(q_a) <= half_a on all three axes (a
+ *      particle exactly on a face is inside; one at d == R of a sphere is outside).  A particle with a NaN coordinate is
+ *      contained by nothing and stays.
+ *   2. The FIRST sink that contains the particle claims it: n_e += 1 for that sink alone, and the particle is removed.
+ *   out_removed, if not NULL, receives the k counts n_e.
+ * ws_remove_particle_ids removes the m particles named in ids; an id may be named more than once and counts once.
+ * Renumbering, for both: ids stay dense.  A survivor's new id is its rank among the survivors by old id; its position and
+ * velocity keep their bits and its four attributes move with it.  out_new_id, if not NULL, receives n words (n = the count
+ * BEFORE the call): out_new_id[old id] = new id, or 0xFFFFFFFF for a removed particle, so that a host can remap its own
+ * per-particle data.
+ * ws_add_particles: the m new particles get the ids n .. n+m-1 in the order given, position and velocity as given (vel_xyz
+ * == NULL: at rest, +0) and the attributes of attr (m*4 floats), or +0 with attr == NULL.  With attr given on a handle whose
+ * attribute array does not exist yet, the array is created and every old particle's attributes are +0.
+ * A count change is an EDIT: afterwards the predicted position of EVERY particle is the library's own rule, pred_a =
+ * fl(x_a + fl(v_a * 0.02f)), exactly as after ws_apply_forces -- predictions a preceding ws_write_particles supplied are
+ * dropped, as any edit drops them.  The views of the LAST STEP's fields behave between the count change and the next
+ * ws_step as they do between ws_write_particles and the next ws_step (ws_read_particles: zero density, pressure and
+ * acceleration; ws_read_sort_view: the identity), but ws_steps_done keeps counting.  The next step hashes with the NEW
+ * count (the reference's num_particles in hash_cell), and is bit for bit the step of a fresh handle created at the new
+ * count and loaded, with ws_write_particles, with the records ws_read_particles returns after the change.  A captured
+ * step (WS_FLAG_GRAPH) is dropped and captured again; with WS_FLAG_PROFILE a count change counts one WS_K_BIN launch.
+ * NO-OPS -- m == 0 on the two calls that take m, and a ws_remove_particles whose sinks claim nothing -- return WS_OK and
+ * leave the handle exactly as it was: the last-step views stay valid, a captured step is kept, nothing is binned again.
+ * The no-op removal still writes its outputs: all counts 0, the id map the identity.
+ * A removal that would leave NO particle is WS_ERR_INVALID_ARG: decided after the scan and before anything is moved, the
+ * handle and the outputs untouched.
+ * Capacity: ws_reserve_particles raises it to at least `capacity` and never lowers it (state, views and results are
+ * unchanged; a captured step is captured again).  An addition beyond the capacity grows it to n' + n'/2 for the new count
+ * n', capped at 2^27 - 16, the largest count ws_create accepts; the new arrays are allocated before the old ones are given
+ * up, so a failure is WS_ERR_OUT_OF_MEMORY with state and count as they were.  An addition within the capacity allocates no
+ * particle array.  Removals never shrink it.  ws_particle_capacity answers on every handle (a slab: the owned capacity; a
+ * NULL handle: 0).
+ * Slab handles are OUT OF SCOPE of these calls: ids and attributes are replicated on every rank, so a count change would
+ * have to be collective.  They, and WS_FLAG_REFERENCE_ORDER handles, return WS_ERR_UNSUPPORTED from the three
+ * count-changing calls and from ws_reserve_particles.
+ * Errors: WS_ERR_INVALID_ARG, with nothing touched -- a NULL handle; a ws_read_positions_begin in flight (call
+ * ws_read_positions_end first); sinks: s NULL, k outside 1 .. WS_MAX_SINKS, a kind > 1, a non-zero reserved word, a
+ * non-finite centre or half or a magnitude above 1e15, a box half extent or sphere radius not > 0, a sphere with half[1]
+ * or half[2] not 0; ids: NULL with m > 0, an id >= n (checked on the host); an addition: pos_xyz NULL with m > 0, any
+ * float of pos_xyz, vel_xyz or attr not finite or above 1e15 in magnitude, a count beyond 2^27 - 16; a removal that would
+ * empty the handle; ws_reserve_particles beyond 2^27 - 16.  WS_ERR_UNSUPPORTED as above.  WS_ERR_OUT_OF_MEMORY (growth or
+ * scratch: the handle stays usable, unless the cell tables of the new count could not be rebuilt after the old ones were
+ * given up: then the handle is unusable, as after a failed re-grid).  WS_ERR_HIP on an unusable handle. */
+#define WS_MAX_SINKS 16u
+enum { WS_SINK_SPHERE = 0, WS_SINK_BOX = 1 };
+typedef struct ws_sink {      /* 32 bytes */
+    uint32_t kind;            /* offset 0: WS_SINK_* */
+    uint32_t reserved;        /* 4: must be 0 */
+    float centre[3];          /* 8 */
+    float half[3];            /* 20: box: half extents, each > 0.  sphere: half[0] = radius > 0, half[1] = half[2] = 0 */
+} ws_sink;
+ws_status ws_reserve_particles(ws_handle *h, uint32_t capacity);
+uint32_t ws_particle_capacity(ws_handle *h);
+ws_status ws_add_particles(ws_handle *h, const float *pos_xyz, const float *vel_xyz, const float *attr, uint32_t m);
+ws_status ws_remove_particles(ws_handle *h, const ws_sink *s, uint32_t k, uint32_t *out_removed, uint32_t *out_new_id);
+ws_status ws_remove_particle_ids(ws_handle *h, const uint32_t *ids, uint32_t m, uint32_t *out_new_id);
+
 /* ---- introspection ------------------------------------------------------------- */
 const char *ws_last_error(ws_handle *h);
 uint32_t ws_num_particles(ws_handle *h);
@@ -1189,7 +1256,8 @@ const char *ws_kernel_name(uint32_t kernel_id);
  * launch per kernel id: a slab step that runs K4 and K5 as an early and a late range
  * contributes ONE launch and the SUM of its two ranges' times.  WS_K_BIN counts the
  * stand-alone binning of ws_create, ws_reset, ws_write_particles and a ws_set_params that
- * re-grids on a single-GPU handle.  A WS_FLAG_GRAPH handle records nothing: all zeros.
+ * re-grids on a single-GPU handle, and every count change (ws_add_particles, ws_remove_particles,
+ * ws_remove_particle_ids).  A WS_FLAG_GRAPH handle records nothing: all zeros.
  * Either output pointer may be NULL; kernel_id >= WS_K_COUNT is WS_ERR_INVALID_ARG. */
 ws_status ws_profile_read(ws_handle *h, uint32_t kernel_id, double *total_ms, uint64_t *launches);
 ws_status ws_profile_reset(ws_handle *h);

@@ -65,6 +65,17 @@ extern "C" {
     fn ws_reset(h: *mut WsHandle, pos_xyz: *const f32) -> c_int;
     fn ws_last_error(h: *mut WsHandle) -> *const c_char;
     fn ws_abi_version() -> u32;
+    // the particle count as a variable (a tap, a drain): declared for hosts that want them, no system here uses them yet
+    #[allow(dead_code)]
+    fn ws_reserve_particles(h: *mut WsHandle, capacity: u32) -> c_int;
+    #[allow(dead_code)]
+    fn ws_particle_capacity(h: *mut WsHandle) -> u32;
+    #[allow(dead_code)]
+    fn ws_add_particles(h: *mut WsHandle, pos_xyz: *const f32, vel_xyz: *const f32, attr: *const f32, m: u32) -> c_int;
+    #[allow(dead_code)]
+    fn ws_remove_particles(h: *mut WsHandle, s: *const c_void, k: u32, out_removed: *mut u32, out_new_id: *mut u32) -> c_int;
+    #[allow(dead_code)]
+    fn ws_remove_particle_ids(h: *mut WsHandle, ids: *const u32, m: u32, out_new_id: *mut u32) -> c_int;
 }
 
 // include/wsfluid.h WS_ABI_VERSION as this file was written against it (2: round 5 -- ws_transport.struct_size, flags

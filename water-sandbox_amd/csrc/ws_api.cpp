@@ -37,6 +37,7 @@ ws_status global_grid(const ws_params *params, uint32_t n_global, WsDev *out);
 // ws_field.inc
 void free_field(ws_handle *h);
 const char *cohesion_refusal(const ws_cohesion_params *p, float dt);
+ws_status attr_ensure(ws_handle *h);
 ws_status cohesion_prepare(ws_handle *h, const WsGathered *g, const ws_cohesion_params *p, float dt, WsCohesionArgs *args);
 
 ws_status fail(ws_handle *h, ws_status st, const char *what, hipError_t e = hipSuccess)
@@ -648,6 +649,7 @@ ws_status upload_positions(ws_handle *h, const float *pos_xyz)
     // the caller's buffer must not be referenced after return
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->steps = 0;
+    h->have_step = false;
     h->last_pressure = {};
     return WS_OK;
 }
@@ -692,6 +694,42 @@ void free_particle_arrays(ws_handle *h)
     h->mask.stride = 0;
 }
 
+// A single-GPU handle's particle arrays at a larger capacity, every byte of the old ones carried over: the state, the
+// binned state and the last step's sorted copy, masks and accelerations all stay what they were (ws_reserve_particles, an
+// addition beyond the capacity).  The new arrays are allocated FIRST: a failure leaves the handle as it was.  The copies
+// go by the order in which alloc_particle_arrays allocates (WsGroup::fields keeps it); the accept masks are rows of
+// `stride` words and move row by row.  Captured steps hold the old pointers and are dropped.
+ws_status grow_particle_arrays(ws_handle *h, uint32_t cap)
+{
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (h->sched_stream) HIP_TRY(h, hipStreamSynchronize(h->sched_stream));
+    const uint32_t old_stride = h->mask.stride;
+    const size_t o16 = ((size_t)h->cap + 16) * 16, o4 = (size_t)h->cap * 4;
+    // (alloc_particle_arrays' sizes, in its order; the masks follow)
+    const size_t old_bytes[12] = {2 * o16, o16, o4, o16, 2 * o16, o16 / 4, o16 / 4, o16 / 4, o4, o4, o16, o4};
+    const bool masks = h->variant == WS_VARIANT_LISTED;
+    if (h->particles.fields.size() != 12u + (masks ? 1u : 0u)) return fail(h, WS_ERR_HIP, "particle arrays: unexpected layout");
+    WsGroup::Held held = h->particles.take();
+    ws_status st = alloc_particle_arrays(h, cap, cap);
+    hipError_t e = hipSuccess;
+    for (size_t i = 0; i < 12 && !st && e == hipSuccess; i++)
+        e = hipMemcpyAsync(*held.fields[i], held.bufs[i], old_bytes[i], hipMemcpyDeviceToDevice, h->stream);
+    if (!st && e == hipSuccess && masks)
+        e = hipMemcpy2DAsync(h->mask.words, (size_t)cap * 4, held.bufs[12], (size_t)old_stride * 4, (size_t)old_stride * 4,
+                             wsk_mask_words(), hipMemcpyDeviceToDevice, h->stream);
+    if (!st && e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (!st && e != hipSuccess) st = fail(h, WS_ERR_HIP, "particle arrays: copy into the larger arrays", e);
+    if (st) {  // the new arrays go, the old ones are the handle's again
+        h->particles.restore(held);
+        h->mask.stride = old_stride;
+        return st;
+    }
+    drop_graphs(h);
+    WsGroup::drop(held);
+    h->cap = cap;
+    return WS_OK;
+}
+
 void free_all(ws_handle *h)
 {
     if (h->stream) hipStreamSynchronize(h->stream);
@@ -708,7 +746,7 @@ void free_all(ws_handle *h)
     free_grid(h);
     free_particle_arrays(h);
     release_all(h->fixed, h->stage_mem, h->force_cnt, h->solid_sums, h->v_keys, h->v_perm, h->v_tmp, h->v_count, h->v_cursor, h->v_start, h->v_bsum,
-                h->v_off);
+                h->v_off, h->pop_words);
     for (auto &volume : h->volume) release_all(volume);
     release_all(h->attr);
     free_field(h);
@@ -858,6 +896,7 @@ ws_status ws_create(const ws_params *params, const float *pos_xyz, uint32_t n, c
     h->device = device;
     h->flags = cfg ? cfg->flags : 0;
     h->n = n;
+    h->cap = n;
     h->params = *params;
     configure_kernels(h);
     if (h->flags & WS_FLAG_GRAPH) h->flags &= ~(uint32_t)WS_FLAG_PROFILE;  // event brackets are not part of a captured step
@@ -949,6 +988,7 @@ ws_status ws_step(ws_handle *h)
             HIP_TRY(h, hipEventRecord(h->done, s));
             h->done_recorded = true;
             h->steps++;
+            h->have_step = true;
             return WS_OK;
         }
     }
@@ -957,6 +997,7 @@ ws_status ws_step(ws_handle *h)
     HIP_TRY(h, hipEventRecord(h->done, s));
     h->done_recorded = true;
     h->steps++;
+    h->have_step = true;
     return WS_OK;
 }
 
@@ -1242,7 +1283,7 @@ ws_status ws_read_particles(ws_handle *h, ws_particle80 *out)
     refresh_pred(h, h->dev);
     st = refresh_accel(h);
     if (st) return st;
-    wsk_gather_particles(h->stream, h->cur, h->srt, h->accel, h->steps > 0, h->last_pressure, (ws_particle80 *)h->stage, h->n);
+    wsk_gather_particles(h->stream, h->cur, h->srt, h->accel, h->have_step, h->last_pressure, (ws_particle80 *)h->stage, h->n);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipMemcpyAsync(out, h->stage, bytes, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -1281,6 +1322,7 @@ ws_status ws_write_particles(ws_handle *h, const ws_particle80 *in)
     if (st) return st;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->steps = 0;
+    h->have_step = false;
     h->last_pressure = {};
     return WS_OK;
 }
@@ -1765,6 +1807,251 @@ ws_status ws_collide_volumes(ws_handle *h, const ws_volume_pose *v, uint32_t k, 
 }
 
 // ======================================================================================
+// pouring water in and draining it: the particle count as a variable (kernels: ws_population.hip)
+// ======================================================================================
+}  // extern "C"
+
+namespace {
+
+constexpr uint32_t kMaxParticles = WS_MAX_SLOTS - 16u;  // ws_create's limit
+
+// What the three count-changing calls and ws_reserve_particles refuse before they look at their arguments.
+ws_status population_enter(ws_handle *h, const char *tag)
+{
+    if (!h) return WS_ERR_INVALID_ARG;
+    WS_DEAD_CHECK(h);
+    if (h->slab)
+        return fail(h, WS_ERR_UNSUPPORTED, (std::string(tag) + ": slab handles keep their particle count (ids and attributes are replicated on every rank: the change would be collective)").c_str());
+    if (h->flags & WS_FLAG_REFERENCE_ORDER)
+        return fail(h, WS_ERR_UNSUPPORTED, (std::string(tag) + ": not in the reference-order validation mode").c_str());
+    if (h->rb_inflight)
+        return fail(h, WS_ERR_INVALID_ARG, (std::string(tag) + ": a position readback is in flight (call ws_read_positions_end first)").c_str());
+    HIP_TRY(h, hipSetDevice(h->device));
+    return WS_OK;
+}
+
+// The attribute array at a larger capacity (it exists): the new one first, all +0 behind the n attributes carried over.
+ws_status grow_attributes(ws_handle *h, uint32_t cap)
+{
+    WsScratch<float4> bigger;
+    const ws_status st = bigger.alloc(h, (size_t)cap * 16, "attribute array");
+    if (st) return st;
+    hipError_t e = hipMemsetAsync(bigger.p, 0, (size_t)cap * 16, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(bigger.p, h->attr.p, (size_t)h->n * 16, hipMemcpyDeviceToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) {
+        bigger.release();
+        return ws_alloc_failed(h, "attribute array", e);
+    }
+    h->attr.release();
+    h->attr = bigger;  // (the one owner again: `bigger` is a plain pair of pointer and size)
+    return WS_OK;
+}
+
+// A single-GPU handle at capacity `cap` > h->cap: attributes first, then the particle arrays (either failure leaves the
+// handle as it was, but for an attribute array that may already be the larger one -- it holds the same n attributes).
+ws_status grow_capacity(ws_handle *h, uint32_t cap)
+{
+    if (h->attr.p) {
+        const ws_status st = grow_attributes(h, cap);
+        if (st) return st;
+    }
+    return grow_particle_arrays(h, cap);
+}
+
+// "The count is now n_new": what every count change ends in, after `cur` holds the n_new records of the new set (in any
+// order, ids dense).  Modelled on the re-grid of ws_set_params: nd = derive_dev(params, n_new), made by the caller BEFORE
+// it touched anything (the cell budget follows n).  The cell tables are rebuilt (start's tail holds n), the alias
+// multiplicities follow the new hash_n, the tile schedule exists only for 2^18 <= n < 2^20, the sort view's scratch is
+// keyed by n; then the set is binned.  A failure once the old tables have been given up leaves a dead handle.
+ws_status population_commit(ws_handle *h, uint32_t n_new, const WsDev &nd)
+{
+    drop_graphs(h);
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    h->dev = nd;
+    h->n = n_new;
+    ws_status st = alloc_grid(h);
+    if (!st) st = upload_mult(h);
+    if (!st) {
+        free_schedule(h);
+        st = alloc_schedule(h);
+    }
+    release_all(h->v_keys, h->v_perm, h->v_tmp, h->v_count, h->v_cursor, h->v_start, h->v_bsum, h->v_off);
+    // an edit: every predicted position from the library's own rule; the last step's fields describe another set
+    h->pred_stale = true;
+    h->accel_stale = false;
+    h->have_step = false;
+    h->last_pressure = {};
+    if (!st) st = bin_current(h);
+    if (!st && hipStreamSynchronize(h->stream) != hipSuccess) st = fail(h, WS_ERR_HIP, "count change: binning");
+    if (st) {
+        h->dead = true;
+        h->err = "count change failed after the old cell tables were given up (" + h->err + "); the handle is unusable";
+        return st;
+    }
+    h->pred_stale = true;  // (cur.pred is the rule's, and the next step recomputes it: a captured step replays from here)
+    return WS_OK;
+}
+
+// the argument errors of ws_remove_particles (nullptr = acceptable)
+const char *sinks_refusal(const ws_sink *s, uint32_t k)
+{
+    if (!s) return "sinks: s is NULL";
+    if (k < 1u || k > WS_MAX_SINKS) return "sinks: k outside 1 .. WS_MAX_SINKS";
+    for (uint32_t e = 0; e < k; e++) {
+        if (s[e].kind > WS_SINK_BOX) return "sinks: unknown kind";
+        if (s[e].reserved) return "sinks: reserved must be 0";
+        for (int c = 0; c < 3; c++)
+            if (ws_bad_float(s[e].centre[c]) || ws_bad_float(s[e].half[c])) return "sinks: centre and half must be finite and at most 1e15 in magnitude";
+        if (s[e].kind == WS_SINK_BOX) {
+            for (int c = 0; c < 3; c++)
+                if (!(s[e].half[c] > 0.f)) return "sinks: a box's half extents must be > 0";
+        } else {
+            if (!(s[e].half[0] > 0.f)) return "sinks: a sphere's radius half[0] must be > 0";
+            if (s[e].half[1] != 0.f || s[e].half[2] != 0.f) return "sinks: a sphere's half[1] and half[2] must be 0";
+        }
+    }
+    return nullptr;
+}
+
+// words of ws_handle::pop_words: the per-sink counts, the survivor count, the scan's tile sums
+constexpr uint32_t kPopTotal = WS_MAX_SINKS, kPopSums = WS_MAX_SINKS + 1u;
+
+// Both removals.  ids == nullptr: the sinks of `sinks` mark; else the m ids (validated).  The marks live in slot_tmp,
+// which only a step's own sort phase reads and writes, so until the survivor count is known nothing of the handle has
+// changed.
+ws_status remove_marked(ws_handle *h, const WsSinkArgs *sinks, const uint32_t *ids, uint32_t m, uint32_t *out_removed,
+                        uint32_t *out_new_id)
+{
+    const uint32_t n = h->n, k = sinks ? sinks->k : 0u;
+    hipStream_t s = h->stream;
+    ws_status st = h->pop_words.grow(h, ((size_t)kPopSums + wsk_pop_tiles(n)) * 4, "count change scratch");
+    if (!st && (ids || out_new_id)) st = ensure_stage(h, (size_t)std::max(n, m) * 4);
+    if (st) return st;
+    uint32_t *const map = h->slot_tmp, *const words = h->pop_words.p;
+    HIP_TRY(h, hipMemsetAsync(words, 0, (size_t)kPopSums * 4, s));
+    if (ids) {
+        HIP_TRY(h, hipMemcpyAsync(h->stage, ids, (size_t)m * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(map), 1, n, s));
+        wsk_pop_clear_ids(s, (const uint32_t *)h->stage, m, map);
+    } else {
+        WsSinkArgs a = *sinks;
+        a.removed = words;
+        wsk_pop_mark_sinks(s, h->cur, n, a, map);
+    }
+    wsk_pop_scan(s, map, n, words + kPopSums, words + kPopTotal);
+    HIP_TRY(h, hipGetLastError());
+    uint32_t got[kPopSums];
+    HIP_TRY(h, copy_now(h, got, words, sizeof got, hipMemcpyDeviceToHost));  // (the one wait of a removal)
+    const uint32_t left = got[kPopTotal];
+    if (left > n) return fail(h, WS_ERR_HIP, "count change: the scan counted more survivors than particles");
+    if (left == 0u) return fail(h, WS_ERR_INVALID_ARG, "count change: the removal would leave no particle");
+    if (left == n) {  // nothing claimed: the handle stays exactly as it was
+        if (out_removed) memset(out_removed, 0, (size_t)k * 4);
+        if (out_new_id)
+            for (uint32_t i = 0; i < n; i++) out_new_id[i] = i;
+        return WS_OK;
+    }
+    WsDev nd;
+    if ((st = derive_dev(h, h->params, left, &nd))) return st;
+    if (out_new_id) wsk_pop_new_ids(s, map, n, (uint32_t *)h->stage);
+    // survivors to slot `new id` of the sorted copy's records -- the last step's views are given up anyway -- which then
+    // becomes `cur`; the attributes through the sorted positions and back
+    wsk_pop_compact(s, h->cur.pv, n, map, h->srt.pv);
+    if (h->attr.p) {
+        wsk_pop_compact_attr(s, h->attr.p, n, map, h->srt.pos);
+        HIP_TRY(h, hipMemcpyAsync(h->attr.p, h->srt.pos, (size_t)left * 16, hipMemcpyDeviceToDevice, s));
+    }
+    HIP_TRY(h, hipGetLastError());
+    std::swap(h->cur.pv, h->srt.pv);  // (both belong to the `particles` group, which frees whatever the two fields hold)
+    if ((st = population_commit(h, left, nd))) return st;
+    if (out_new_id) HIP_TRY(h, copy_now(h, out_new_id, h->stage, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (out_removed) memcpy(out_removed, got, (size_t)k * 4);
+    drain_profile(h);
+    return WS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint32_t ws_particle_capacity(ws_handle *h)
+{
+    if (!h) return 0;
+    if (h->slab) return h->slab->cap;
+    return (h->flags & WS_FLAG_REFERENCE_ORDER) ? h->n : h->cap;
+}
+
+ws_status ws_reserve_particles(ws_handle *h, uint32_t capacity)
+{
+    const ws_status st = population_enter(h, "reserve");
+    if (st) return st;
+    if (capacity > kMaxParticles) return fail(h, WS_ERR_INVALID_ARG, "reserve: more than 2^27 - 16 particles on one device");
+    if (capacity <= h->cap) return WS_OK;
+    return grow_capacity(h, capacity);
+}
+
+ws_status ws_remove_particles(ws_handle *h, const ws_sink *s, uint32_t k, uint32_t *out_removed, uint32_t *out_new_id)
+{
+    const ws_status st = population_enter(h, "sinks");
+    if (st) return st;
+    if (const char *why = sinks_refusal(s, k)) return fail(h, WS_ERR_INVALID_ARG, why);
+    WsSinkArgs a{};
+    memcpy(a.ss.e, s, (size_t)k * sizeof(ws_sink));
+    a.k = k;
+    return remove_marked(h, &a, nullptr, 0, out_removed, out_new_id);
+}
+
+ws_status ws_remove_particle_ids(ws_handle *h, const uint32_t *ids, uint32_t m, uint32_t *out_new_id)
+{
+    const ws_status st = population_enter(h, "remove ids");
+    if (st) return st;
+    if (m == 0u) {  // a no-op: the id map is the identity
+        if (out_new_id)
+            for (uint32_t i = 0; i < h->n; i++) out_new_id[i] = i;
+        return WS_OK;
+    }
+    if (!ids) return fail(h, WS_ERR_INVALID_ARG, "remove ids: ids is NULL");
+    for (uint32_t j = 0; j < m; j++)
+        if (ids[j] >= h->n) return fail(h, WS_ERR_INVALID_ARG, "remove ids: an id is not below the particle count");
+    return remove_marked(h, nullptr, ids, m, nullptr, out_new_id);
+}
+
+ws_status ws_add_particles(ws_handle *h, const float *pos_xyz, const float *vel_xyz, const float *attr, uint32_t m)
+{
+    ws_status st = population_enter(h, "add");
+    if (st) return st;
+    if (m == 0u) return WS_OK;
+    if (!pos_xyz) return fail(h, WS_ERR_INVALID_ARG, "add: pos_xyz is NULL");
+    if ((uint64_t)h->n + m > kMaxParticles) return fail(h, WS_ERR_INVALID_ARG, "add: more than 2^27 - 16 particles on one device");
+    for (size_t t = 0; t < (size_t)m * 3; t++)
+        if (ws_bad_float(pos_xyz[t]) || (vel_xyz && ws_bad_float(vel_xyz[t])))
+            return fail(h, WS_ERR_INVALID_ARG, "add: positions and velocities must be finite and at most 1e15 in magnitude");
+    for (size_t t = 0; attr && t < (size_t)m * 4; t++)
+        if (ws_bad_float(attr[t])) return fail(h, WS_ERR_INVALID_ARG, "add: attributes must be finite and at most 1e15 in magnitude");
+    const uint32_t n0 = h->n, n1 = n0 + m;
+    WsDev nd;
+    if ((st = derive_dev(h, h->params, n1, &nd))) return st;
+    // everything that allocates, before anything is written: the staging (positions | velocities | attributes), the
+    // capacity, the attribute array if the new particles are the first to carry any
+    const size_t off_vel = (size_t)m * 12, off_attr = (2 * off_vel + 15) & ~(size_t)15;  // (the attributes are read 16 bytes at a time)
+    if ((st = ensure_stage(h, off_attr + (size_t)m * 16))) return st;
+    if (n1 > h->cap && (st = grow_capacity(h, (uint32_t)std::min<uint64_t>((uint64_t)n1 + n1 / 2u, kMaxParticles)))) return st;
+    if (attr && (st = attr_ensure(h))) return st;
+    hipStream_t s = h->stream;
+    char *const stage = (char *)h->stage;
+    HIP_TRY(h, hipMemcpyAsync(stage, pos_xyz, (size_t)m * 12, hipMemcpyHostToDevice, s));
+    if (vel_xyz) HIP_TRY(h, hipMemcpyAsync(stage + off_vel, vel_xyz, (size_t)m * 12, hipMemcpyHostToDevice, s));
+    if (attr) HIP_TRY(h, hipMemcpyAsync(stage + off_attr, attr, (size_t)m * 16, hipMemcpyHostToDevice, s));
+    wsk_pop_append(s, (const float *)stage, vel_xyz ? (const float *)(stage + off_vel) : nullptr,
+                   attr ? (const float4 *)(stage + off_attr) : nullptr, m, n0, h->cur, h->attr.p);
+    HIP_TRY(h, hipGetLastError());
+    if ((st = population_commit(h, n1, nd))) return st;  // (it waits: the caller's arrays are not referenced after return)
+    drain_profile(h);
+    return WS_OK;
+}
+
+// ======================================================================================
 // reference-layout sort view
 // ======================================================================================
 ws_status ws_read_sort_view(ws_handle *h, uint32_t *keys_by_id, uint32_t *perm, uint32_t *cell_offsets)
@@ -1774,7 +2061,7 @@ ws_status ws_read_sort_view(ws_handle *h, uint32_t *keys_by_id, uint32_t *perm, 
     HIP_TRY(h, hipSetDevice(h->device));
     // a slab handle answers for the WHOLE domain (collective: the keys of every rank's particles are gathered by id)
     const uint32_t n = h->slab ? h->slab->n_global : h->n;
-    const bool stepped = h->slab ? h->steps > h->slab->t0 : h->steps > 0;
+    const bool stepped = h->slab ? h->steps > h->slab->t0 : h->have_step;
     hipStream_t s = h->stream;
     WS_REF_DISPATCH(h, ref_read_sort_view(h, keys_by_id, perm, cell_offsets));
     if (!h->v_bsum.p) {  // (allocated last: it is there only if all eight are)

@@ -1,7 +1,7 @@
 // ws_device.h -- what more than one of the .hip files needs on the device side, and nothing else: the block size, the
 // XCD tile map, the cell of a position, the wave scans, the smoothing kernels, the two sqrt / division forms and the
 // bool-to-template dispatch.  Included by the .hip files only (ws_kernels.hip: the step; ws_edits.hip: the between-step
-// edits; ws_views.hip: read-backs and id-ordered views; ws_fields.hip: the field calls); a helper that one file uses
+// edits; ws_population.hip: the count changes; ws_views.hip: read-backs and id-ordered views; ws_fields.hip: the field calls); a helper that one file uses
 // stays in that file.  The arithmetic contract is the one stated at the top of ws_kernels.hip.
 #pragma once
 

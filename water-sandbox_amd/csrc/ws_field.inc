@@ -939,11 +939,12 @@ ws_status body_forces(ws_handle *h, const ws_body_params *p, const float *xyz, c
 // The array lives in ws_handle::attr, by id: n float4, on slab handles n_global (replicated).
 uint32_t attr_count(const ws_handle *h) { return h->slab ? h->slab->n_global : h->n; }
 
-// the array, all +0, on the first call that needs it
+// the array, all +0, on the first call that needs it (a single handle: of its capacity, so that ws_add_particles within
+// the capacity allocates nothing; the calls work on the first attr_count(h) entries)
 ws_status attr_ensure(ws_handle *h)
 {
     if (h->attr.p) return WS_OK;
-    const size_t bytes = (size_t)attr_count(h) * 16;
+    const size_t bytes = (size_t)(h->slab ? h->slab->n_global : h->cap) * 16;
     const ws_status st = h->attr.alloc(h, bytes, "attribute array");
     if (st) return st;
     if (hipMemsetAsync(h->attr.p, 0, bytes, h->stream) != hipSuccess) {

@@ -278,6 +278,34 @@ struct WsGroup {
         }
         fields.clear();
     }
+    // For a lifetime that is rebuilt at another size BEFORE its buffers are given up (ws_api.cpp grow_particle_arrays):
+    // take() empties the group and hands its buffers out -- the fields keep pointing at them until the group allocates into
+    // them again; restore() releases what the group has allocated since and makes the held buffers the group's again;
+    // drop() frees them.  Exactly one of the two ends a take().
+    struct Held {
+        std::vector<void **> fields;
+        std::vector<void *> bufs;
+    };
+    Held take()
+    {
+        Held k;
+        k.fields.swap(fields);
+        for (void **f : k.fields) k.bufs.push_back(*f);
+        return k;
+    }
+    void restore(Held &k)
+    {
+        release();
+        for (size_t i = 0; i < k.fields.size(); i++) *k.fields[i] = k.bufs[i];
+        fields.swap(k.fields);
+        k.bufs.clear();
+    }
+    static void drop(Held &k)
+    {
+        for (void *q : k.bufs) (void)hipFree(q);
+        k.bufs.clear();
+        k.fields.clear();
+    }
 };
 
 // ws_handle::field: the scratch of the derived-field calls -- their own counting sort of the CURRENT positions, allocated
@@ -360,7 +388,10 @@ struct ws_handle {
     uint32_t flags = 0;
     uint32_t prof_mask = 0xFFFFFFFFu;
     uint32_t n = 0;
+    uint32_t cap = 0;  // single-GPU handles: particles the particle arrays and the attribute array hold (>= n; ws_reserve_particles)
     uint64_t steps = 0;
+    bool have_step = false;  // single-GPU handles: the sorted copy holds the last step's fields of the CURRENT particle set
+                             // (false after a load and after a count change, which leaves `steps` counting)
     ws_params params{};
     ws_smoothing_kernel sk{};
     WsDev dev{};
@@ -396,6 +427,9 @@ struct ws_handle {
     // the per-particle attributes: one float4 per particle BY ID (n; on slab handles n_global, replicated on every rank),
     // allocated all +0 by the first attribute call (p == nullptr: every attribute is +0), zeroed by ws_reset
     WsScratch<float4> attr;
+    // ws_remove_particles / _ids: the per-sink counts, the survivor count and the scan's tile sums (ws_population.hip;
+    // allocated by the first removal, a word per 2048 particles)
+    WsScratch<uint32_t> pop_words;
     bool alias = false;
     size_t grid_alloc_cells = 0;  // cells that count / cursor hold
     // The owners of the arrays above, one per lifetime (ws_api.cpp):
@@ -562,7 +596,7 @@ struct WsSlab {
 // ws_rccl.cpp (not part of the public header): no-op for a transport that is not the library's own
 extern "C" void ws_rccl_transport_bind_stream(const ws_transport *t, void *stream);
 
-// ---- kernel launchers (ws_kernels.hip: the step; ws_edits.hip, ws_views.hip, ws_fields.hip: the calls around it) ----
+// ---- kernel launchers (ws_kernels.hip: the step; ws_edits.hip, ws_population.hip, ws_views.hip, ws_fields.hip: the calls around it) ----
 void wsk_upload_positions(hipStream_t s, const float *xyz_dev, WsSoA cur, uint32_t n);
 void wsk_upload_particles(hipStream_t s, const ws_particle80 *in_dev, WsSoA cur, uint32_t n);
 void wsk_bin(hipStream_t s, const WsDev &d, WsSoA cur, uint32_t *cid, uint32_t *count);  // (cur / cid from the first particle to bin)
@@ -737,6 +771,29 @@ struct WsBrushArgs {
     uint32_t k;
     uint32_t *painted;
 };
+// count changes (ws_remove_particles / ws_remove_particle_ids / ws_add_particles; ws_population.hip).  map: one word per
+// particle id.  Mark: the sinks by value, as the emitters (removed = WS_MAX_SINKS device words the kernel adds the
+// per-sink claims to), or a map filled with 1 and the named ids cleared.  wsk_pop_scan: map[id] = rank among the survivors
+// << 1 | stays, through wsk_pop_tiles(n) words of sums; *total = the survivors.  Compact: the surviving 32-byte records of
+// src to slot `new id` of dst, the attributes by id likewise; wsk_pop_new_ids: the host's id map.  Append: m staged
+// particles at the slots and ids n0 .. (vel / attr_in / attr may be nullptr).
+struct WsSinkSet {
+    ws_sink e[WS_MAX_SINKS];
+};
+struct WsSinkArgs {
+    WsSinkSet ss;
+    uint32_t k;
+    uint32_t *removed;
+};
+uint32_t wsk_pop_tiles(uint32_t n);
+void wsk_pop_mark_sinks(hipStream_t s, WsSoA cur, uint32_t n, const WsSinkArgs &a, uint32_t *map);
+void wsk_pop_clear_ids(hipStream_t s, const uint32_t *ids, uint32_t m, uint32_t *map);
+void wsk_pop_scan(hipStream_t s, uint32_t *map, uint32_t n, uint32_t *sums, uint32_t *total);
+void wsk_pop_compact(hipStream_t s, const float4 *src, uint32_t n, const uint32_t *map, float4 *dst);
+void wsk_pop_compact_attr(hipStream_t s, const float4 *attr, uint32_t n, const uint32_t *map, float4 *out);
+void wsk_pop_new_ids(hipStream_t s, const uint32_t *map, uint32_t n, uint32_t *out);
+void wsk_pop_append(hipStream_t s, const float *pos, const float *vel, const float4 *attr_in, uint32_t m, uint32_t n0, WsSoA cur,
+                    float4 *attr);
 void wsk_attr_paint(hipStream_t s, const WsBrushArgs &a, const float *xyz, float4 *attr, uint32_t n);
 void wsk_attr_gather(hipStream_t s, const float4 *spos, const float4 *attr, float4 *sa, uint32_t n);
 void wsk_attr_scatter(hipStream_t s, const float4 *spos, const float4 *sa, float4 *attr, uint32_t n);

@@ -59,6 +59,7 @@ ABI_SYMBOLS = [
     "ws_volume_upload", "ws_collide_volumes", "ws_default_cohesion_params", "ws_read_cohesion", "ws_apply_cohesion",
     "ws_default_diffuse_params", "ws_write_attributes", "ws_read_attributes", "ws_paint_attributes", "ws_diffuse_attributes",
     "ws_sample_attribute_grid", "ws_sample_attribute_points",
+    "ws_reserve_particles", "ws_particle_capacity", "ws_add_particles", "ws_remove_particles", "ws_remove_particle_ids",
 ]
 
 
@@ -243,6 +244,22 @@ class WsBrush(C.Structure):
     ]
 
 
+WS_SINK_SPHERE, WS_SINK_BOX = 0, 1
+WS_MAX_SINKS = 16
+REMOVED = 0xFFFFFFFF  # out_new_id of a removed particle
+
+
+class WsSink(C.Structure):
+    """ws_sink: a region ws_remove_particles drains (32 bytes)."""
+
+    _fields_ = [
+        ("kind", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("centre", C.c_float * 3),
+        ("half", C.c_float * 3),
+    ]
+
+
 class WsDiffuseParams(C.Structure):
     """ws_diffuse_params: the per-channel rates and the iteration count of ws_diffuse_attributes (include/wsfluid.h)."""
 
@@ -387,6 +404,12 @@ def bind_library(path):
     L.ws_volume_upload.argtypes = [vp, u32, vp, vp, vp, vp]
     L.ws_collide_volumes.argtypes = [vp, vp, u32, vp, vp, vp]
     L.ws_body_forces.argtypes = [vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, vp]
+    L.ws_reserve_particles.argtypes = [vp, u32]
+    L.ws_particle_capacity.argtypes = [vp]
+    L.ws_particle_capacity.restype = u32
+    L.ws_add_particles.argtypes = [vp, vp, vp, vp, u32]
+    L.ws_remove_particles.argtypes = [vp, vp, u32, vp, vp]
+    L.ws_remove_particle_ids.argtypes = [vp, vp, u32, vp]
     return L
 
 
@@ -656,6 +679,51 @@ def apply_forces(L, h, check, forces, dt, counts=True):
     out = np.zeros(max(len(forces), 1), np.uint32) if counts else None
     check(L.ws_apply_forces(h, C.byref(arr), len(forces), dt, out.ctypes.data if counts else None))
     return out[:len(forces)] if counts else None
+
+
+def sink(kind, centre, half):
+    """One ws_sink: kind = WS_SINK_SPHERE / _BOX (or "sphere" / "box"); half = the box's three half extents, or the
+    sphere's radius (a number, or (R, 0, 0))."""
+    kind = {"sphere": WS_SINK_SPHERE, "box": WS_SINK_BOX}.get(kind, kind)
+    if np.ndim(half) == 0:
+        half = (float(half), 0.0, 0.0)
+    return WsSink(kind, 0, (C.c_float * 3)(*(float(x) for x in centre)), (C.c_float * 3)(*(float(x) for x in half)))
+
+
+def add_particles(L, h, check, positions, velocities=None, attributes=None):
+    """ws_add_particles: m new particles with the ids n .. n+m-1 (include/wsfluid.h has the definition).  positions (m, 3);
+    velocities (m, 3) or None (at rest); attributes (m, 4) or None (+0).  Returns m."""
+    pos = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+    m = pos.shape[0]
+    vel = None if velocities is None else np.ascontiguousarray(velocities, np.float32).reshape(-1, 3)
+    att = None if attributes is None else np.ascontiguousarray(attributes, np.float32).reshape(-1, 4)
+    assert vel is None or vel.shape[0] == m, (vel.shape, m)
+    assert att is None or att.shape[0] == m, (att.shape, m)
+    check(L.ws_add_particles(h, pos.ctypes.data if m else None, None if vel is None else vel.ctypes.data,
+                             None if att is None else att.ctypes.data, m))
+    return m
+
+
+def remove_particles(L, h, check, n, sinks, counts=True, new_ids=True):
+    """ws_remove_particles: every particle the sinks (a WsSink or a sequence of them) contain; n = the count before the
+    call.  Returns (per-sink counts (k,) uint32 or None, new id by old id (n,) uint32 -- REMOVED where the particle is
+    gone -- or None)."""
+    sinks = [sinks] if isinstance(sinks, WsSink) else list(sinks)
+    arr = (WsSink * max(len(sinks), 1))(*sinks)
+    removed = np.zeros(max(len(sinks), 1), np.uint32) if counts else None
+    ids = np.empty(n, np.uint32) if new_ids else None
+    check(L.ws_remove_particles(h, C.byref(arr), len(sinks), removed.ctypes.data if counts else None,
+                                ids.ctypes.data if new_ids else None))
+    return (removed[:len(sinks)] if counts else None), ids
+
+
+def remove_particle_ids(L, h, check, n, ids, new_ids=True):
+    """ws_remove_particle_ids: the particles named in ids (duplicates count once); n = the count before the call.  Returns
+    the new id by old id (n,) uint32 -- REMOVED where the particle is gone -- or None."""
+    ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+    out = np.empty(n, np.uint32) if new_ids else None
+    check(L.ws_remove_particle_ids(h, ids.ctypes.data if ids.size else None, ids.size, out.ctypes.data if new_ids else None))
+    return out
 
 
 def cohesion_params(**fields):
@@ -1247,6 +1315,35 @@ class FluidWorker:
         centres[b] per body.  params = body_params(...).  A BodyForces (force, torque, volume, wet, sample_force,
         sample_fraction; the last two with samples=True) -- include/wsfluid.h ws_body_forces has the definition."""
         return body_forces(self._L, self._h, self._check, params, xyz, velocity, volume, body_start, centres, samples)
+
+    # the particle count as a variable (include/wsfluid.h "pouring water in and draining it"): self.n follows the handle
+    def reserve(self, capacity):
+        """ws_reserve_particles: room for `capacity` particles, so that additions up to it allocate nothing."""
+        self._check(self._L.ws_reserve_particles(self._h, int(capacity)))
+
+    def capacity(self):
+        return int(self._L.ws_particle_capacity(self._h))
+
+    def _count_changed(self):
+        self.n = int(self._L.ws_num_particles(self._h))
+
+    def add_particles(self, positions, velocities=None, attributes=None):
+        """m new particles with the ids n .. n+m-1; returns the new count."""
+        add_particles(self._L, self._h, self._check, positions, velocities, attributes)
+        self._count_changed()
+        return self.n
+
+    def remove_particles(self, sinks, counts=True, new_ids=True):
+        """Drain the sinks; returns (per-sink counts, new id by old id), either None if not asked for."""
+        out = remove_particles(self._L, self._h, self._check, self.n, sinks, counts, new_ids)
+        self._count_changed()
+        return out
+
+    def remove_particle_ids(self, ids, new_ids=True):
+        """Remove the particles named in ids; returns the new id by old id, or None."""
+        out = remove_particle_ids(self._L, self._h, self._check, self.n, ids, new_ids)
+        self._count_changed()
+        return out
 
     def steps_done(self):
         return int(self._L.ws_steps_done(self._h))
