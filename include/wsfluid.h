@@ -1233,6 +1233,70 @@ ws_status ws_add_particles(ws_handle *h, const float *pos_xyz, const float *vel_
 ws_status ws_remove_particles(ws_handle *h, const ws_sink *s, uint32_t k, uint32_t *out_removed, uint32_t *out_new_id);
 ws_status ws_remove_particle_ids(ws_handle *h, const uint32_t *ids, uint32_t m, uint32_t *out_new_id);
 
+/* ---- gauges: measure and select the fluid inside regions (no reference counterpart) ---------------------
+ * How much water is in the bucket, how fast does it flow through the gate, where is its centre of mass, how high does it
+ * stand, what is the largest speed, which particles did the player lasso -- answered on the device, for up to
+ * WS_MAX_REGIONS regions in one pass over the particle records, instead of through ws_read_particles and a host loop.
+ * A REGION is a ws_sink by another name: the same 32 bytes, the same validation and the same containment as step 1 of
+ * ws_remove_particles.  x, v are what ws_read_positions / ws_read_velocities return; arithmetic is IEEE whatever the
+ * handle's flags: every operation is rounded once, sqrt is correctly rounded, nothing is contracted; dot() and the cross
+ * product are ws_apply_forces'.
+ * ws_measure, per region e = 0 .. k-1 (c = centre) and per particle:
+ *   Containment.  q_a = x_a - c_a.  A sphere contains the particle iff d < R with d = sqrt(dot(q, q)), R = half[0]; a box
+ *     iff fabsf(q_a) <= half_a on all three axes -- ws_remove_particles step 1 operation for operation (on a face: inside;
+ *     at d == R: outside; a NaN coordinate: contained by nothing).  Every region is independent: a particle counts in
+ *     EVERY region that contains it, there is no first claim.
+ *   Sums.  count += 1.  Each float t enters a sum as the 64-bit integer llrintf(fminf(fmaxf(t, -0x1p31f), 0x1p31f) *
+ *     0x1p24f) -- step 6 of ws_collide_solids -- and the sums wrap modulo 2^64, so they depend on no order.  Per contained
+ *     particle: x_a into sum_pos[a]; v_a into sum_vel[a]; the three components of q x v (q is containment's own value:
+ *     x = fl(fl(q_y*v_z) - fl(q_z*v_y)) and cyclically) into sum_ang[a]; dot(v, v) into sum_speed2; and with
+ *     WS_GAUGE_ATTRIBUTES on a handle that has attributes, the particle's four attribute floats into sum_attr[c] (else
+ *     sum_attr stays 0).  The host divides by 2^24, and by count for a mean.  A sum is free of wrap as long as the
+ *     magnitudes it adds up stay below 2^39 in total (2^63 / 2^24); a term beyond 2^31 in magnitude enters as 2^31.
+ *   Extremes.  min_pos[a], max_pos[a] over x_a and max_speed2 over dot(v, v) are taken under the TOTAL order of the key
+ *     bits ^ (bits >> 31 ? 0xFFFFFFFF : 0x80000000) of a float's bits, so that -0 < +0 and the result depends on no visit
+ *     order.  max_speed2 starts from +0 and skips a NaN, as fmaxf does.
+ *   An EMPTY region: count 0, every sum 0, min_pos = +inf, max_pos = -inf, max_speed2 = +0.  reserved is written 0.
+ * The call is stream-ordered after the steps enqueued so far and SYNCHRONOUS: it waits for its k * 152 bytes.  It is
+ * READ-ONLY: nothing is binned again, the predicted positions and the last step's views stay as they are, a captured step
+ * (WS_FLAG_GRAPH) is kept, ws_steps_done does not move, and with WS_FLAG_PROFILE no launch is counted under any WS_K_* id.
+ * It is allowed between ws_read_positions_begin and _end on a single-GPU handle (a slab handle's gather refuses there, as
+ * for every collective read).
+ * Slab handles: COLLECTIVE, by the velocity field's route (one gather of {position, velocity} by id); every rank measures
+ * the global set, attributes are replicated by id already, and every rank that passes out gets the single handle's bits
+ * (out may be NULL on a slab handle: this rank only contributes).  The verdict on the arguments is common, as in
+ * ws_collide_solids: ranks that refuse, or that were given different regions or flags, ALL return WS_ERR_INVALID_ARG.
+ * ws_select_particles: the ids of the particles that AT LEAST ONE of the k regions contains, in ascending id order.
+ * *out_total = how many there are; the first min(total, cap) are written to out_ids, which may be NULL with cap == 0 (a
+ * count only).  Read-only in the sense above, synchronous (the count is read back, then the min(total, cap) ids).  The list feeds
+ * ws_remove_particle_ids and a host's own per-particle data.  Single-GPU handles only: slab handles return
+ * WS_ERR_UNSUPPORTED.
+ * Errors, both calls: WS_ERR_INVALID_ARG with nothing written -- NULL h, r or out (single-GPU handles); k outside 1 ..
+ * WS_MAX_REGIONS; flag bits other than bit 0; every refusal ws_remove_particles has for a sink (a kind > 1, a non-zero
+ * reserved word, a non-finite centre or half or a magnitude above 1e15, a box half extent or sphere radius not > 0, a
+ * sphere with half[1] or half[2] not 0); ws_select_particles also: out_total NULL, out_ids NULL with cap > 0.
+ * WS_ERR_UNSUPPORTED on WS_FLAG_REFERENCE_ORDER handles.  WS_ERR_OUT_OF_MEMORY (scratch: the handle stays usable).
+ * WS_ERR_HIP on an unusable handle.
+ * Left out: density or pressure sums (they need the last step's sorted copy), oriented regions, an asynchronous form,
+ * ws_select_particles on slab handles, one id list per region. */
+typedef ws_sink ws_region;            /* the same 32 bytes, validation and containment as ws_remove_particles step 1 */
+#define WS_MAX_REGIONS 16u
+#define WS_GAUGE_ATTRIBUTES 1u        /* flags bit 0: also sum the four attributes (a gather by id) */
+typedef struct ws_gauge {             /* 152 bytes */
+    uint64_t count;                   /* offset 0 */
+    int64_t  sum_pos[3];              /* 8: fixed point, 2^-24 */
+    int64_t  sum_vel[3];              /* 32 */
+    int64_t  sum_ang[3];              /* 56: q x v, q = x - the region's centre */
+    int64_t  sum_speed2;              /* 80: dot(v, v) */
+    int64_t  sum_attr[4];             /* 88: 0 unless WS_GAUGE_ATTRIBUTES and the handle has attributes */
+    float    min_pos[3];              /* 120 */
+    float    max_pos[3];              /* 132 */
+    float    max_speed2;              /* 144 */
+    uint32_t reserved;                /* 148: written 0 */
+} ws_gauge;
+ws_status ws_measure(ws_handle *h, const ws_region *r, uint32_t k, uint32_t flags, ws_gauge *out);
+ws_status ws_select_particles(ws_handle *h, const ws_region *r, uint32_t k, uint32_t cap, uint32_t *out_ids, uint32_t *out_total);
+
 /* ---- introspection ------------------------------------------------------------- */
 const char *ws_last_error(ws_handle *h);
 uint32_t ws_num_particles(ws_handle *h);

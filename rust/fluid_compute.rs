@@ -52,6 +52,36 @@ pub struct WsHandle {
     _opaque: [u8; 0],
 }
 
+// ws_region (= ws_sink): a sphere (kind 0: half[0] = radius, half[1] = half[2] = 0) or an axis-aligned box (kind 1: the
+// three half extents) that ws_measure / ws_select_particles look into.  32 bytes.
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+#[allow(dead_code)]
+pub struct WsRegion {
+    pub kind: u32,
+    pub reserved: u32,
+    pub centre: [f32; 3],
+    pub half: [f32; 3],
+}
+
+// ws_gauge: what ws_measure reports of one region (152 bytes).  The sums are 64-bit fixed point: divide by 2^24, and by
+// `count` for a mean; the extremes are plain floats (an empty region: +inf / -inf / +0).
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+#[allow(dead_code)]
+pub struct WsGauge {
+    pub count: u64,
+    pub sum_pos: [i64; 3],
+    pub sum_vel: [i64; 3],
+    pub sum_ang: [i64; 3],
+    pub sum_speed2: i64,
+    pub sum_attr: [i64; 4],
+    pub min_pos: [f32; 3],
+    pub max_pos: [f32; 3],
+    pub max_speed2: f32,
+    pub reserved: u32,
+}
+
 extern "C" {
     fn ws_create(params: *const WsParams, pos_xyz: *const f32, n: u32, cfg: *const c_void, out: *mut *mut WsHandle) -> c_int;
     fn ws_destroy(h: *mut WsHandle) -> c_int;
@@ -76,6 +106,12 @@ extern "C" {
     fn ws_remove_particles(h: *mut WsHandle, s: *const c_void, k: u32, out_removed: *mut u32, out_new_id: *mut u32) -> c_int;
     #[allow(dead_code)]
     fn ws_remove_particle_ids(h: *mut WsHandle, ids: *const u32, m: u32, out_new_id: *mut u32) -> c_int;
+    // gauges (how much water is in the bucket, which particles are in the lasso): for hosts that want them -- no system
+    // here uses them, HipFluidWorker::measure / ::select_particles wrap them.  r: k WsRegion records
+    #[allow(dead_code)]
+    fn ws_measure(h: *mut WsHandle, r: *const c_void, k: u32, flags: u32, out: *mut WsGauge) -> c_int;
+    #[allow(dead_code)]
+    fn ws_select_particles(h: *mut WsHandle, r: *const c_void, k: u32, cap: u32, out_ids: *mut u32, out_total: *mut u32) -> c_int;
 }
 
 // include/wsfluid.h WS_ABI_VERSION as this file was written against it (2: round 5 -- ws_transport.struct_size, flags
@@ -158,6 +194,29 @@ impl Drop for HipFluidWorker {
             ws_unpin_host_buffer(self.handle, self.positions.as_mut_ptr() as *mut c_void);
             ws_destroy(self.handle);
         }
+    }
+}
+
+// Gauges for a host's own systems (none of this file's calls them): both are synchronous and read-only, so they may be
+// called between two steps from any system that holds the worker.
+#[allow(dead_code)]
+impl HipFluidWorker {
+    /// One WsGauge per region (at most 16): count, fixed-point sums (divide by 2^24), extremes.
+    pub fn measure(&mut self, regions: &[WsRegion], attributes: bool) -> Vec<WsGauge> {
+        let mut out = vec![WsGauge::default(); regions.len()];
+        let st = unsafe { ws_measure(self.handle, regions.as_ptr() as *const c_void, regions.len() as u32, attributes as u32, out.as_mut_ptr()) };
+        check(self.handle, st, "ws_measure");
+        out
+    }
+
+    /// The ids inside the union of the regions, ascending, at most `cap` of them, and how many there are in all.
+    pub fn select_particles(&mut self, regions: &[WsRegion], cap: u32) -> (Vec<u32>, u32) {
+        let mut ids = vec![0u32; cap as usize];
+        let mut total = 0u32;
+        let st = unsafe { ws_select_particles(self.handle, regions.as_ptr() as *const c_void, regions.len() as u32, cap, ids.as_mut_ptr(), &mut total) };
+        check(self.handle, st, "ws_select_particles");
+        ids.truncate(total.min(cap) as usize);
+        (ids, total)
     }
 }
 

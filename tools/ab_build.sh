@@ -19,6 +19,6 @@ done
 src=$work/water-sandbox_amd/csrc
 /opt/rocm/bin/hipcc -x hip --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize -fPIC -shared -Wno-unused-value -Wno-unused-result -DWS_DEV_HOOKS $flags \
   -I $work/include -I $src -o $root/tools/ab/lib$name.so \
-  $src/ws_kernels.hip $src/ws_edits.hip $src/ws_population.hip $src/ws_views.hip $src/ws_fields.hip $src/ws_api.cpp $src/ws_rccl.cpp $src/ws_local.cpp -ldl
+  $src/ws_kernels.hip $src/ws_edits.hip $src/ws_population.hip $src/ws_gauges.hip $src/ws_views.hip $src/ws_fields.hip $src/ws_api.cpp $src/ws_rccl.cpp $src/ws_local.cpp -ldl
 rm -rf $work
 echo built tools/ab/lib$name.so

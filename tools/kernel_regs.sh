@@ -1,7 +1,7 @@
 #!/bin/bash
 # Registers / LDS / scratch of every kernel in one .hip file of csrc/ (device-only assembly, no GPU needed).
 # usage: tools/kernel_regs.sh [file.hip] [extra hipcc flags]   -> /tmp/ws_kernels.s + a table on stdout
-#   the file defaults to ws_kernels.hip (the step); ws_edits.hip, ws_views.hip and ws_fields.hip are the others
+#   the file defaults to ws_kernels.hip (the step); ws_edits.hip, ws_population.hip, ws_gauges.hip, ws_views.hip and ws_fields.hip are the others
 cd "$(dirname "$0")/.."
 file=ws_kernels.hip
 case "$1" in *.hip) file=$(basename "$1"); shift;; esac

@@ -10,9 +10,9 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libwsfluid.so")
 
 # The kernels by call family: the step (ws_kernels.hip -- what the K4 / K5 tools and tests compile), the between-step
-# edits, the count changes, the read-backs and id-ordered views, the field calls; ws_device.h is what they share.  Every file of csrc/ is
+# edits, the count changes, the gauges, the read-backs and id-ordered views, the field calls; ws_device.h is what they share.  Every file of csrc/ is
 # named here or in HEADERS (tests/test_no_experiment_switches.py), so none escapes the staleness rule.
-SOURCES = ["ws_kernels.hip", "ws_edits.hip", "ws_population.hip", "ws_views.hip", "ws_fields.hip", "ws_api.cpp", "ws_rccl.cpp", "ws_local.cpp"]
+SOURCES = ["ws_kernels.hip", "ws_edits.hip", "ws_population.hip", "ws_gauges.hip", "ws_views.hip", "ws_fields.hip", "ws_api.cpp", "ws_rccl.cpp", "ws_local.cpp"]
 HEADERS = [os.path.join(CSRC, "ws_internal.h"), os.path.join(CSRC, "ws_device.h"), os.path.join(CSRC, "ws_devhooks.h"),
            os.path.join(CSRC, "ws_slab.inc"), os.path.join(CSRC, "ws_field.inc"), os.path.join(ROOT, "include", "wsfluid.h")]
 # Test-only build of the same sources plus the reference-order validation mode (tests/refcheck/: a literal HIP

@@ -746,7 +746,7 @@ void free_all(ws_handle *h)
     free_grid(h);
     free_particle_arrays(h);
     release_all(h->fixed, h->stage_mem, h->force_cnt, h->solid_sums, h->v_keys, h->v_perm, h->v_tmp, h->v_count, h->v_cursor, h->v_start, h->v_bsum,
-                h->v_off, h->pop_words);
+                h->v_off, h->pop_words, h->gauge_out, h->gauge_ids);
     for (auto &volume : h->volume) release_all(volume);
     release_all(h->attr);
     free_field(h);
@@ -2048,6 +2048,169 @@ ws_status ws_add_particles(ws_handle *h, const float *pos_xyz, const float *vel_
     HIP_TRY(h, hipGetLastError());
     if ((st = population_commit(h, n1, nd))) return st;  // (it waits: the caller's arrays are not referenced after return)
     drain_profile(h);
+    return WS_OK;
+}
+
+// ======================================================================================
+// gauges: measure and select the fluid inside regions (kernels: ws_gauges.hip)
+// ======================================================================================
+}  // extern "C"
+
+namespace {
+
+// the argument errors both gauge calls share (nullptr = acceptable); a region is a ws_sink, refused for what a sink is
+const char *regions_refusal(const ws_region *r, uint32_t k, uint32_t flags)
+{
+    if (!r) return "regions: r is NULL";
+    if (k < 1u || k > WS_MAX_REGIONS) return "regions: k outside 1 .. WS_MAX_REGIONS";
+    if (flags & ~WS_GAUGE_ATTRIBUTES) return "regions: unknown flag bits";
+    return sinks_refusal(r, k);
+}
+
+// what both gauge calls refuse before they look at their arguments
+ws_status gauges_enter(ws_handle *h, const char *tag)
+{
+    if (!h) return WS_ERR_INVALID_ARG;
+    WS_DEAD_CHECK(h);
+    if (h->flags & WS_FLAG_REFERENCE_ORDER)
+        return fail(h, WS_ERR_UNSUPPORTED, (std::string(tag) + ": not in the reference-order validation mode").c_str());
+    HIP_TRY(h, hipSetDevice(h->device));
+    return WS_OK;
+}
+
+// the device's words (wsk_gauge_measure's layout) as the caller's k gauges
+struct GaugeWords {
+    unsigned long long sums[WS_MAX_REGIONS][WS_GAUGE_SUMS];
+    uint32_t keys[WS_MAX_REGIONS][WS_GAUGE_KEYS];
+    static float unkey(uint32_t key)
+    {
+        const uint32_t bits = key ^ ((key >> 31) ? 0x80000000u : 0xFFFFFFFFu);
+        float x;
+        memcpy(&x, &bits, 4);
+        return x;
+    }
+    void outputs(ws_gauge *out, uint32_t k) const
+    {
+        for (uint32_t e = 0; e < k; e++) {
+            ws_gauge &g = out[e];
+            const unsigned long long *w = sums[e];
+            g.count = w[0];
+            for (int c = 0; c < 3; c++) {
+                g.sum_pos[c] = (int64_t)w[1 + c];
+                g.sum_vel[c] = (int64_t)w[4 + c];
+                g.sum_ang[c] = (int64_t)w[7 + c];
+                g.min_pos[c] = unkey(keys[e][c]);
+                g.max_pos[c] = unkey(keys[e][3 + c]);
+            }
+            g.sum_speed2 = (int64_t)w[10];
+            for (int c = 0; c < 4; c++) g.sum_attr[c] = (int64_t)w[11 + c];
+            g.max_speed2 = unkey(keys[e][6]);
+            g.reserved = 0u;
+        }
+    }
+};
+static_assert(sizeof(GaugeWords) == WS_GAUGE_OUT_BYTES, "the host's view of the gauge words is the kernel's layout");
+static_assert(sizeof(ws_gauge) == 152, "ws_gauge is 152 bytes (include/wsfluid.h)");
+
+// ws_measure on slab handles (COLLECTIVE): the velocity field's gather, then the verdict on the arguments made common --
+// bit 0 of the agreed word = this rank refuses (its arguments, or its scratch), the rest = a hash of k, flags and the
+// regions' bytes -- before this rank measures the global set by id.
+ws_status slab_measure(ws_handle *h, const ws_region *r, uint32_t k, uint32_t flags, ws_gauge *out)
+{
+    WsSlab *S = h->slab;
+    ws_status st = slab_gather_by_id(h, WS_PACK_POSVEL_H);
+    if (st) return st;
+    const char *why = regions_refusal(r, k, flags);
+    const ws_status mine = why ? WS_OK : h->gauge_out.grow(h, WS_GAUGE_OUT_BYTES, "gauge words");
+    const std::string mine_text = h->err;
+    if (S->world > 1) {
+        uint32_t word = 2166136261u;  // FNV-1a
+        auto mix = [&word](const void *p, size_t bytes) {
+            for (size_t b = 0; b < bytes; b++) word = (word ^ static_cast<const uint8_t *>(p)[b]) * 16777619u;
+        };
+        mix(&k, 4);
+        mix(&flags, 4);
+        if (!why) mix(r, (size_t)k * sizeof(ws_region));
+        word = (word << 1) | ((why || mine) ? 1u : 0u);
+        std::vector<uint32_t> tab;
+        if ((st = slab_agree_words(h, word, &tab))) return st;
+        bool anybody = false, differ = false;
+        for (uint32_t q = 0; q < S->world; q++) {
+            anybody = anybody || (tab[4 * q] & 1u);
+            differ = differ || (tab[4 * q] >> 1) != (word >> 1);
+        }
+        if (why) return fail(h, WS_ERR_INVALID_ARG, why);
+        if (mine) return fail(h, mine, mine_text.c_str());
+        if (anybody) return fail(h, WS_ERR_INVALID_ARG, "measure: another slab refused its arguments");
+        if (differ) return fail(h, WS_ERR_INVALID_ARG, "measure: the slabs were given different regions or flags");
+    }
+    if (why) return fail(h, WS_ERR_INVALID_ARG, why);
+    if (mine) return mine;
+    WsRegionSet rs{};
+    memcpy(rs.e, r, (size_t)k * sizeof(ws_region));
+    wsk_gauge_measure(h->stream, nullptr, reinterpret_cast<const float *>(S->g_out.p), (flags & WS_GAUGE_ATTRIBUTES) ? h->attr.p : nullptr,
+                      S->n_global, rs, k, h->gauge_out.p);
+    HIP_TRY(h, hipGetLastError());
+    GaugeWords words;
+    HIP_TRY(h, copy_now(h, &words, h->gauge_out.p, sizeof words, hipMemcpyDeviceToHost));
+    if (out) words.outputs(out, k);
+    return WS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// One streaming pass over `cur` behind the steps enqueued so far, and one wait for the gauges' words.  Nothing of the
+// handle is written but the call's own scratch: no array moves, nothing is binned, pred_stale and the last step's views
+// stay, a captured step is replayed as it is, and no profiling event is recorded.
+ws_status ws_measure(ws_handle *h, const ws_region *r, uint32_t k, uint32_t flags, ws_gauge *out)
+{
+    ws_status st = gauges_enter(h, "measure");
+    if (st) return st;
+    if (h->slab) return slab_measure(h, r, k, flags, out);  // collective: validated after the gather
+    if (!out) return fail(h, WS_ERR_INVALID_ARG, "measure: out is NULL");
+    if (const char *why = regions_refusal(r, k, flags)) return fail(h, WS_ERR_INVALID_ARG, why);
+    if ((st = h->gauge_out.grow(h, WS_GAUGE_OUT_BYTES, "gauge words"))) return st;
+    WsRegionSet rs{};
+    memcpy(rs.e, r, (size_t)k * sizeof(ws_region));
+    wsk_gauge_measure(h->stream, h->cur.pv, nullptr, (flags & WS_GAUGE_ATTRIBUTES) ? h->attr.p : nullptr, h->n, rs, k, h->gauge_out.p);
+    HIP_TRY(h, hipGetLastError());
+    GaugeWords words;
+    HIP_TRY(h, copy_now(h, &words, h->gauge_out.p, sizeof words, hipMemcpyDeviceToHost));
+    drain_profile(h);
+    words.outputs(out, k);
+    return WS_OK;
+}
+
+// The removal's route with the mark turned round: the selected ids marked in the id map (the step's sort slots, which
+// nothing reads between two steps), wsk_pop_scan, the first `cap` of them written in id order, and the readback.
+ws_status ws_select_particles(ws_handle *h, const ws_region *r, uint32_t k, uint32_t cap, uint32_t *out_ids, uint32_t *out_total)
+{
+    ws_status st = gauges_enter(h, "select");
+    if (st) return st;
+    if (h->slab) return fail(h, WS_ERR_UNSUPPORTED, "select: not on slab handles (every rank holds its own slab's records: the list would be collective)");
+    if (!out_total) return fail(h, WS_ERR_INVALID_ARG, "select: out_total is NULL");
+    if (!out_ids && cap) return fail(h, WS_ERR_INVALID_ARG, "select: out_ids is NULL with cap > 0");
+    if (const char *why = regions_refusal(r, k, 0u)) return fail(h, WS_ERR_INVALID_ARG, why);
+    const uint32_t n = h->n, room = std::min(cap, n);
+    if ((st = h->pop_words.grow(h, ((size_t)kPopSums + wsk_pop_tiles(n)) * 4, "selection scratch"))) return st;
+    if (room && (st = h->gauge_ids.grow(h, (size_t)room * 4, "selected ids"))) return st;
+    hipStream_t s = h->stream;
+    uint32_t *const map = h->slot_tmp, *const words = h->pop_words.p;
+    WsRegionSet rs{};
+    memcpy(rs.e, r, (size_t)k * sizeof(ws_region));
+    wsk_gauge_mark(s, h->cur, n, rs, k, map);
+    wsk_pop_scan(s, map, n, words + kPopSums, words + kPopTotal);
+    if (room) wsk_gauge_list(s, map, n, room, h->gauge_ids.p);
+    HIP_TRY(h, hipGetLastError());
+    uint32_t total = 0;
+    HIP_TRY(h, copy_now(h, &total, words + kPopTotal, 4, hipMemcpyDeviceToHost));
+    if (total > n) return fail(h, WS_ERR_HIP, "select: the scan counted more particles than there are");
+    const uint32_t wrote = std::min(total, room);
+    if (wrote) HIP_TRY(h, copy_now(h, out_ids, h->gauge_ids.p, (size_t)wrote * 4, hipMemcpyDeviceToHost));
+    drain_profile(h);
+    *out_total = total;
     return WS_OK;
 }
 

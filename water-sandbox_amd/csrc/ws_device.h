@@ -1,7 +1,7 @@
 // ws_device.h -- what more than one of the .hip files needs on the device side, and nothing else: the block size, the
 // XCD tile map, the cell of a position, the wave scans, the smoothing kernels, the two sqrt / division forms and the
 // bool-to-template dispatch.  Included by the .hip files only (ws_kernels.hip: the step; ws_edits.hip: the between-step
-// edits; ws_population.hip: the count changes; ws_views.hip: read-backs and id-ordered views; ws_fields.hip: the field calls); a helper that one file uses
+// edits; ws_population.hip: the count changes; ws_gauges.hip: the gauges; ws_views.hip: read-backs and id-ordered views; ws_fields.hip: the field calls); a helper that one file uses
 // stays in that file.  The arithmetic contract is the one stated at the top of ws_kernels.hip.
 #pragma once
 
@@ -89,6 +89,20 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v)
         if (lane >= o) v += t;
     }
     return v;
+}
+
+// A float as the 64-bit fixed-point term of an order-free sum (ws_collide_solids step 6, ws_measure): clamped to
+// +-2^31 -- a NaN comes out of fmaxf as -2^31 --, times 2^24, rounded to nearest even; and such terms summed across a wave.
+__device__ __forceinline__ long long solids_fixed(float x)
+{
+    return llrintf(fminf(fmaxf(x, -2147483648.f), 2147483648.f) * 16777216.f);
+}
+
+__device__ __forceinline__ long long wave_sum_i64(long long x)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+    return x;
 }
 
 // Wave-level aggregation of `atomicAdd(&table[key], 1)`: consecutive lanes with the same key form a

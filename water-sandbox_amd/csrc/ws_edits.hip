@@ -75,18 +75,8 @@ __device__ __forceinline__ bool forces_eval(const WsForceSet &fs, uint32_t k, fl
 // the wave with shuffles (only in waves that have a contact), per workgroup in LDS (acc: WS_SOLID_WORDS 64-bit words per
 // solid, zeroed by the caller), and from there at most one 64-bit atomic per workgroup, solid and word
 // (solids_flush).  Every lane of the wave must call.  Returns whether any solid touched the particle.
+// (solids_fixed and wave_sum_i64, step 6's fixed point and its sum across a wave: ws_device.h -- the gauges share them)
 // ---------------------------------------------------------------------------------
-__device__ __forceinline__ long long solids_fixed(float x)
-{
-    return llrintf(fminf(fmaxf(x, -2147483648.f), 2147483648.f) * 16777216.f);
-}
-
-__device__ __forceinline__ long long wave_sum_i64(long long x)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
 
 // Steps 3 to 6 of the definition, shared by every edit that collides (solids_eval, volumes_eval): given the signed distance
 // s and the outward unit normal n of one object at the running position -- `hit` = the particle is active and s < margin

@@ -430,6 +430,10 @@ struct ws_handle {
     // ws_remove_particles / _ids: the per-sink counts, the survivor count and the scan's tile sums (ws_population.hip;
     // allocated by the first removal, a word per 2048 particles)
     WsScratch<uint32_t> pop_words;
+    // ws_measure: the sums and keys of up to WS_MAX_REGIONS gauges (WS_GAUGE_OUT_BYTES); ws_select_particles: the ids it
+    // lists (ws_gauges.hip; each allocated by the first call that needs it)
+    WsScratch<unsigned long long> gauge_out;
+    WsScratch<uint32_t> gauge_ids;
     bool alias = false;
     size_t grid_alloc_cells = 0;  // cells that count / cursor hold
     // The owners of the arrays above, one per lifetime (ws_api.cpp):
@@ -794,6 +798,23 @@ void wsk_pop_compact_attr(hipStream_t s, const float4 *attr, uint32_t n, const u
 void wsk_pop_new_ids(hipStream_t s, const uint32_t *map, uint32_t n, uint32_t *out);
 void wsk_pop_append(hipStream_t s, const float *pos, const float *vel, const float4 *attr_in, uint32_t m, uint32_t n0, WsSoA cur,
                     float4 *attr);
+// gauges (ws_measure / ws_select_particles; ws_gauges.hip).  The regions by value, as the sinks.  Measure: the records of a
+// single handle's `cur` (pv) or, posvel != nullptr, a slab's gathered {position, velocity} by id (6 floats; the id is the
+// index); attr != nullptr: the attributes by id are summed too.  out: WS_MAX_REGIONS x WS_GAUGE_SUMS 64-bit words {count,
+// the 14 fixed-point sums in ws_gauge's order}, then WS_MAX_REGIONS x WS_GAUGE_KEYS 32-bit keys {min_pos[3], max_pos[3],
+// max_speed2} of the extremes' total order (WS_GAUGE_OUT_BYTES in all); the launcher sets the identities first, on s.
+// Select: map[id] = 1 if any region contains the particle, else 0 (then wsk_pop_scan), and the first cap selected ids in
+// ascending order to out.
+#define WS_GAUGE_SUMS 15u
+#define WS_GAUGE_KEYS 7u
+#define WS_GAUGE_OUT_BYTES (WS_MAX_REGIONS * (WS_GAUGE_SUMS * 8u + WS_GAUGE_KEYS * 4u))
+struct WsRegionSet {
+    ws_region e[WS_MAX_REGIONS];
+};
+void wsk_gauge_measure(hipStream_t s, const float4 *pv, const float *posvel, const float4 *attr, uint32_t n, const WsRegionSet &rs,
+                       uint32_t k, unsigned long long *out);
+void wsk_gauge_mark(hipStream_t s, WsSoA cur, uint32_t n, const WsRegionSet &rs, uint32_t k, uint32_t *map);
+void wsk_gauge_list(hipStream_t s, const uint32_t *map, uint32_t n, uint32_t cap, uint32_t *out);
 void wsk_attr_paint(hipStream_t s, const WsBrushArgs &a, const float *xyz, float4 *attr, uint32_t n);
 void wsk_attr_gather(hipStream_t s, const float4 *spos, const float4 *attr, float4 *sa, uint32_t n);
 void wsk_attr_scatter(hipStream_t s, const float4 *spos, const float4 *sa, float4 *attr, uint32_t n);

@@ -60,6 +60,7 @@ ABI_SYMBOLS = [
     "ws_default_diffuse_params", "ws_write_attributes", "ws_read_attributes", "ws_paint_attributes", "ws_diffuse_attributes",
     "ws_sample_attribute_grid", "ws_sample_attribute_points",
     "ws_reserve_particles", "ws_particle_capacity", "ws_add_particles", "ws_remove_particles", "ws_remove_particle_ids",
+    "ws_measure", "ws_select_particles",
 ]
 
 
@@ -260,6 +261,34 @@ class WsSink(C.Structure):
     ]
 
 
+WS_MAX_REGIONS = 16
+WS_GAUGE_ATTRIBUTES = 1  # ws_measure flags bit 0: also sum the four attributes
+GAUGE_FIXED = 24  # the sums are fixed point: sum / 2**24
+
+
+class WsGauge(C.Structure):
+    """ws_gauge: what ws_measure reports of one region (152 bytes)."""
+
+    _fields_ = [
+        ("count", C.c_uint64),
+        ("sum_pos", C.c_int64 * 3),
+        ("sum_vel", C.c_int64 * 3),
+        ("sum_ang", C.c_int64 * 3),
+        ("sum_speed2", C.c_int64),
+        ("sum_attr", C.c_int64 * 4),
+        ("min_pos", C.c_float * 3),
+        ("max_pos", C.c_float * 3),
+        ("max_speed2", C.c_float),
+        ("reserved", C.c_uint32),
+    ]
+
+
+GAUGE_DTYPE = np.dtype([("count", np.uint64), ("sum_pos", np.int64, 3), ("sum_vel", np.int64, 3), ("sum_ang", np.int64, 3),
+                        ("sum_speed2", np.int64), ("sum_attr", np.int64, 4), ("min_pos", np.float32, 3),
+                        ("max_pos", np.float32, 3), ("max_speed2", np.float32), ("reserved", np.uint32)])
+assert GAUGE_DTYPE.itemsize == C.sizeof(WsGauge) == 152
+
+
 class WsDiffuseParams(C.Structure):
     """ws_diffuse_params: the per-channel rates and the iteration count of ws_diffuse_attributes (include/wsfluid.h)."""
 
@@ -410,6 +439,8 @@ def bind_library(path):
     L.ws_add_particles.argtypes = [vp, vp, vp, vp, u32]
     L.ws_remove_particles.argtypes = [vp, vp, u32, vp, vp]
     L.ws_remove_particle_ids.argtypes = [vp, vp, u32, vp]
+    L.ws_measure.argtypes = [vp, vp, u32, u32, vp]
+    L.ws_select_particles.argtypes = [vp, vp, u32, u32, vp, vp]
     return L
 
 
@@ -724,6 +755,52 @@ def remove_particle_ids(L, h, check, n, ids, new_ids=True):
     out = np.empty(n, np.uint32) if new_ids else None
     check(L.ws_remove_particle_ids(h, ids.ctypes.data if ids.size else None, ids.size, out.ctypes.data if new_ids else None))
     return out
+
+
+region = sink  # a ws_region is a ws_sink by another name: the same 32 bytes, validation and containment
+
+
+class Gauges(dict):
+    """ws_measure's k gauges as numpy arrays with the raw integers: count (k,) uint64; sum_pos, sum_vel, sum_ang (k, 3),
+    sum_speed2 (k,), sum_attr (k, 4) int64, fixed point 2**-24; min_pos, max_pos (k, 3), max_speed2 (k,) float32."""
+
+    def total(self, name):
+        """The sum `name` ("pos", "vel", "ang", "speed2", "attr") as float64: the integers divided by 2**24."""
+        return self["sum_" + name].astype(np.float64) / 2.0 ** GAUGE_FIXED
+
+    def mean(self, name):
+        """total(name) / count per region: the centre of mass ("pos"), the mean velocity, ... (NaN for an empty region)."""
+        t = self.total(name)
+        c = self["count"].astype(np.float64).reshape((-1,) + (1,) * (t.ndim - 1))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return t / c
+
+
+def _regions(regions):
+    regions = [regions] if isinstance(regions, WsSink) else list(regions)
+    return regions, (WsSink * max(len(regions), 1))(*regions)
+
+
+def measure(L, h, check, regions, attributes=False, want=True):
+    """ws_measure: up to 16 gauges in one pass (include/wsfluid.h has the definition).  regions: a WsSink or a sequence of
+    them (region() / sink() builds one).  Returns a Gauges dict; want=False (a slab rank that only contributes): None."""
+    regions, arr = _regions(regions)
+    out = np.zeros(max(len(regions), 1), GAUGE_DTYPE)
+    check(L.ws_measure(h, C.byref(arr), len(regions), WS_GAUGE_ATTRIBUTES if attributes else 0, out.ctypes.data if want else None))
+    if not want:
+        return None
+    out = out[:len(regions)]
+    return Gauges((name, np.ascontiguousarray(out[name])) for name in GAUGE_DTYPE.names if name != "reserved")
+
+
+def select_particles(L, h, check, regions, cap):
+    """ws_select_particles: (ids (min(total, cap),) uint32 ascending, total) of the particles at least one region contains."""
+    regions, arr = _regions(regions)
+    cap = int(cap)
+    ids = np.empty(cap, np.uint32)
+    total = C.c_uint32(0)
+    check(L.ws_select_particles(h, C.byref(arr), len(regions), cap, ids.ctypes.data if cap else None, C.byref(total)))
+    return ids[:min(cap, total.value)].copy(), int(total.value)
 
 
 def cohesion_params(**fields):
@@ -1344,6 +1421,15 @@ class FluidWorker:
         out = remove_particle_ids(self._L, self._h, self._check, self.n, ids, new_ids)
         self._count_changed()
         return out
+
+    # gauges (include/wsfluid.h "gauges"): read-only, synchronous
+    def measure(self, regions, attributes=False):
+        """Up to 16 gauges in one pass: a Gauges dict of numpy arrays (raw integers; .total() / .mean() divide)."""
+        return measure(self._L, self._h, self._check, regions, attributes)
+
+    def select_particles(self, regions, cap=None):
+        """(ids ascending, total) of the particles inside the union of the regions; cap defaults to the particle count."""
+        return select_particles(self._L, self._h, self._check, regions, self.n if cap is None else cap)
 
     def steps_done(self):
         return int(self._L.ws_steps_done(self._h))

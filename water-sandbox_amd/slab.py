@@ -493,6 +493,11 @@ class SlabWorker:
         solids); the outputs are global.  reaction=False: this rank applies without asking for them (None)."""
         return fluid.collide_solids(self._L, self._h, self._check, solids, reaction)
 
+    def measure(self, regions, attributes=False, want=True):
+        """FluidWorker.measure of the GLOBAL particle set (COLLECTIVE: every rank makes the same call with the same
+        regions and flags); every rank gets the single handle's bits.  want=False: only contribute (None)."""
+        return fluid.measure(self._L, self._h, self._check, regions, attributes, want)
+
     def upload_volume(self, slot, origin, spacing, sdf):
         """FluidWorker.upload_volume into THIS rank's slot (LOCAL: no communication; every rank uploads its own copy)."""
         fluid.upload_volume(self._L, self._h, self._check, slot, origin, spacing, sdf)
