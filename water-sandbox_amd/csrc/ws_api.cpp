@@ -8,6 +8,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <functional>
 #include <new>
 
 #include "ws_internal.h"
@@ -30,7 +31,19 @@ ws_status slab_reset(ws_handle *h, const float *pos_xyz);
 ws_status slab_write_particles(ws_handle *h, const ws_particle80 *in);
 ws_status slab_regrid(ws_handle *h, const ws_params *params, bool rebalance);
 ws_status slab_field_positions(ws_handle *h, const float **xyz, WsDev *global, bool with_vel);
-ws_status slab_agree_words(ws_handle *h, uint32_t mine, std::vector<uint32_t> *table);
+// 32-bit FNV-1a over bytes: a collective call's arguments in the slabs' agreement (slab_verdict)
+struct ArgHash {
+    uint32_t word = 2166136261u;
+    void operator()(const void *p, size_t bytes)
+    {
+        for (size_t b = 0; b < bytes; b++) word = (word ^ static_cast<const uint8_t *>(p)[b]) * 16777619u;
+    }
+};
+struct VerdictText {
+    const char *tag, *things;  // "<tag>: the slabs were given different <things>"
+    bool mutates;              // the call changes state: its refusals end in "; nothing was changed"
+};
+ws_status slab_verdict(ws_handle *h, const VerdictText &text, const char *why, ws_status mine, uint32_t hash);
 template <class Call>
 ws_status slab_edit_gathered(ws_handle *h, Call &call);
 ws_status global_grid(const ws_params *params, uint32_t n_global, WsDev *out);
@@ -54,11 +67,11 @@ ws_status fail(ws_handle *h, ws_status st, const char *what, hipError_t e = hipS
     return st;
 }
 
-#define HIP_TRY(h, expr)                                                                     \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return fail(h, e_ == hipErrorOutOfMemory ? WS_ERR_OUT_OF_MEMORY : WS_ERR_HIP, #expr, e_); \
+// (ws_hip_failed, below: the status a HIP error stands for, `what` and the error in ws_last_error)
+#define HIP_TRY(h, expr)                                          \
+    do {                                                          \
+        hipError_t e_ = (expr);                                   \
+        if (e_ != hipSuccess) return ws_hip_failed(h, #expr, e_); \
     } while (0)
 
 // The same inside ws_create / ws_slab_create, where a failure gives the half-built handle up through the function's `bail`.
@@ -67,11 +80,10 @@ ws_status fail(ws_handle *h, ws_status st, const char *what, hipError_t e = hipS
         ws_status s_ = (expr);            \
         if (s_) return bail(s_);          \
     } while (0)
-#define CREATE_HIP(expr)                                                                   \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return bail(fail(h, e_ == hipErrorOutOfMemory ? WS_ERR_OUT_OF_MEMORY : WS_ERR_HIP, #expr, e_)); \
+#define CREATE_HIP(expr)                                                \
+    do {                                                                \
+        hipError_t e_ = (expr);                                         \
+        if (e_ != hipSuccess) return bail(ws_hip_failed(h, #expr, e_)); \
     } while (0)
 
 // A host <-> device copy on the HANDLE'S OWN stream, complete on return.  Never the legacy (null) stream: it
@@ -124,8 +136,9 @@ float accept_threshold(float h)
 
 }  // namespace
 
-// what the two owner forms of ws_internal.h (WsScratch, WsGroup) report when HIP refuses them memory
-ws_status ws_alloc_failed(ws_handle *h, const char *what, hipError_t e)
+// A HIP call that failed, as the entry point's return value (HIP_TRY, and the two owner forms of ws_internal.h when HIP
+// refuses them memory): the sticky error cleared, the status, `what` and the error's name in ws_last_error.
+ws_status ws_hip_failed(ws_handle *h, const char *what, hipError_t e)
 {
     (void)hipGetLastError();
     return fail(h, e == hipErrorOutOfMemory ? WS_ERR_OUT_OF_MEMORY : WS_ERR_HIP, what, e);
@@ -338,6 +351,23 @@ ws_status ensure_stage(ws_handle *h, size_t bytes)
     do {                                                               \
         if ((h)->dead) return fail((h), WS_ERR_HIP, (h)->err.c_str()); \
     } while (0)
+
+// the refusal of the reference-order validation mode, by the calls that have no literal six-pass form (`tag` leads it)
+ws_status reference_order_refused(ws_handle *h, const char *tag)
+{
+    return fail(h, WS_ERR_UNSUPPORTED, (std::string(tag) + ": not in the reference-order validation mode").c_str());
+}
+
+// What a call between two steps refuses before it looks at its arguments, in this order: a NULL handle, a dead one, the
+// reference-order validation mode; then the handle's device is made current.
+ws_status enter(ws_handle *h, const char *tag)
+{
+    if (!h) return WS_ERR_INVALID_ARG;
+    WS_DEAD_CHECK(h);
+    if (h->flags & WS_FLAG_REFERENCE_ORDER) return reference_order_refused(h, tag);
+    HIP_TRY(h, hipSetDevice(h->device));
+    return WS_OK;
+}
 
 // The test-only build also contains a validation mode that runs the reference's six passes literally
 // (tests/refcheck/): its handles are handed over at the top of every entry point.  Nothing of it exists in the product.
@@ -1223,14 +1253,12 @@ ws_status ws_read_speeds(ws_handle *h, float *out_speed)
 ws_status ws_read_velocities(ws_handle *h, float *out_xyz)
 {
     if (!h || (!out_xyz && !h->slab)) return WS_ERR_INVALID_ARG;
-    WS_DEAD_CHECK(h);
-    if (h->flags & WS_FLAG_REFERENCE_ORDER) return fail(h, WS_ERR_UNSUPPORTED, "velocities: not in the reference-order validation mode");
-    HIP_TRY(h, hipSetDevice(h->device));
+    ws_status st = enter(h, "velocities");
+    if (st) return st;
     const uint32_t n = h->slab ? h->slab->n_global : h->n;
     const size_t bytes = (size_t)n * 12;
     if (h->slab) {
-        ws_status st = slab_gather_by_id(h, WS_PACK_POSVEL_H);
-        if (st) return st;
+        if ((st = slab_gather_by_id(h, WS_PACK_POSVEL_H))) return st;
         if (out_xyz) {
             if ((st = ensure_stage(h, bytes))) return st;
             wsk_field_split(h->stream, reinterpret_cast<const float *>(h->slab->g_out.p), nullptr, (float *)h->stage, n);
@@ -1240,8 +1268,7 @@ ws_status ws_read_velocities(ws_handle *h, float *out_xyz)
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         return WS_OK;
     }
-    ws_status st = ensure_stage(h, bytes);
-    if (st) return st;
+    if ((st = ensure_stage(h, bytes))) return st;
     wsk_gather_velocities(h->stream, h->cur, (float *)h->stage, n);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipMemcpyAsync(out_xyz, h->stage, bytes, hipMemcpyDeviceToHost, h->stream));
@@ -1352,15 +1379,11 @@ namespace {
 template <class Call>
 ws_status edit_fluid(ws_handle *h, Call &call)
 {
-    if (!h) return WS_ERR_INVALID_ARG;
-    WS_DEAD_CHECK(h);
-    if (h->flags & WS_FLAG_REFERENCE_ORDER)
-        return fail(h, WS_ERR_UNSUPPORTED, (std::string(call.tag) + ": not in the reference-order validation mode").c_str());
-    HIP_TRY(h, hipSetDevice(h->device));
+    ws_status st = enter(h, call.tag);
+    if (st) return st;
     if (h->slab) return slab_edit_gathered(h, call);  // collective: validated after the gather
     if (const char *why = call.refuse()) return fail(h, WS_ERR_INVALID_ARG, why);
-    const ws_status st = call.prepare(h, nullptr);
-    if (st) return st;
+    if ((st = call.prepare(h, nullptr))) return st;
     HIP_TRY(h, hipMemsetAsync(h->count, 0, (size_t)h->dev.ncells * 4, h->stream));
     wsk_edit_current(h->stream, h->dev, h->cur, h->cid_cur, h->count, call.args);
     HIP_TRY(h, hipGetLastError());
@@ -1764,24 +1787,20 @@ extern "C" {
 ws_status ws_volume_upload(ws_handle *h, uint32_t slot, const float origin[3], const float spacing[3], const uint32_t dims[3],
                            const float *sdf)
 {
-    if (!h) return WS_ERR_INVALID_ARG;
-    WS_DEAD_CHECK(h);
-    if (h->flags & WS_FLAG_REFERENCE_ORDER) return fail(h, WS_ERR_UNSUPPORTED, "volume: not in the reference-order validation mode");
+    ws_status st = enter(h, "volume");
+    if (st) return st;
     if (slot >= WS_MAX_VOLUMES) return fail(h, WS_ERR_INVALID_ARG, "volume: slot must be below WS_MAX_VOLUMES");
     if (sdf)
         if (const char *why = volume_refusal(origin, spacing, dims, sdf)) return fail(h, WS_ERR_INVALID_ARG, why);
-    HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));  // an enqueued edit may still be reading the old array
     volume_clear(h, slot);
     if (!sdf) return WS_OK;
     const size_t nodes = (size_t)dims[0] * dims[1] * dims[2];
-    ws_status st = h->volume[slot].alloc(h, nodes * 4, "signed-distance volume");
-    if (st) return st;
+    if ((st = h->volume[slot].alloc(h, nodes * 4, "signed-distance volume"))) return st;
     const hipError_t e = copy_now(h, h->volume[slot].p, sdf, nodes * 4, hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         volume_clear(h, slot);
-        (void)hipGetLastError();
-        return fail(h, e == hipErrorOutOfMemory ? WS_ERR_OUT_OF_MEMORY : WS_ERR_HIP, "volume: the copy to the device", e);
+        return ws_hip_failed(h, "volume: the copy to the device", e);
     }
     WsVolumeDesc &D = h->volume_desc[slot];
     D.sdf = h->volume[slot].p;
@@ -1818,15 +1837,12 @@ constexpr uint32_t kMaxParticles = WS_MAX_SLOTS - 16u;  // ws_create's limit
 // What the three count-changing calls and ws_reserve_particles refuse before they look at their arguments.
 ws_status population_enter(ws_handle *h, const char *tag)
 {
-    if (!h) return WS_ERR_INVALID_ARG;
-    WS_DEAD_CHECK(h);
+    const ws_status st = enter(h, tag);  // (a slab handle is never in the reference-order mode: ws_slab_create)
+    if (st) return st;
     if (h->slab)
         return fail(h, WS_ERR_UNSUPPORTED, (std::string(tag) + ": slab handles keep their particle count (ids and attributes are replicated on every rank: the change would be collective)").c_str());
-    if (h->flags & WS_FLAG_REFERENCE_ORDER)
-        return fail(h, WS_ERR_UNSUPPORTED, (std::string(tag) + ": not in the reference-order validation mode").c_str());
     if (h->rb_inflight)
         return fail(h, WS_ERR_INVALID_ARG, (std::string(tag) + ": a position readback is in flight (call ws_read_positions_end first)").c_str());
-    HIP_TRY(h, hipSetDevice(h->device));
     return WS_OK;
 }
 
@@ -1841,7 +1857,7 @@ ws_status grow_attributes(ws_handle *h, uint32_t cap)
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) {
         bigger.release();
-        return ws_alloc_failed(h, "attribute array", e);
+        return ws_hip_failed(h, "attribute array", e);
     }
     h->attr.release();
     h->attr = bigger;  // (the one owner again: `bigger` is a plain pair of pointer and size)
@@ -2067,17 +2083,6 @@ const char *regions_refusal(const ws_region *r, uint32_t k, uint32_t flags)
     return sinks_refusal(r, k);
 }
 
-// what both gauge calls refuse before they look at their arguments
-ws_status gauges_enter(ws_handle *h, const char *tag)
-{
-    if (!h) return WS_ERR_INVALID_ARG;
-    WS_DEAD_CHECK(h);
-    if (h->flags & WS_FLAG_REFERENCE_ORDER)
-        return fail(h, WS_ERR_UNSUPPORTED, (std::string(tag) + ": not in the reference-order validation mode").c_str());
-    HIP_TRY(h, hipSetDevice(h->device));
-    return WS_OK;
-}
-
 // the device's words (wsk_gauge_measure's layout) as the caller's k gauges
 struct GaugeWords {
     unsigned long long sums[WS_MAX_REGIONS][WS_GAUGE_SUMS];
@@ -2112,51 +2117,6 @@ struct GaugeWords {
 static_assert(sizeof(GaugeWords) == WS_GAUGE_OUT_BYTES, "the host's view of the gauge words is the kernel's layout");
 static_assert(sizeof(ws_gauge) == 152, "ws_gauge is 152 bytes (include/wsfluid.h)");
 
-// ws_measure on slab handles (COLLECTIVE): the velocity field's gather, then the verdict on the arguments made common --
-// bit 0 of the agreed word = this rank refuses (its arguments, or its scratch), the rest = a hash of k, flags and the
-// regions' bytes -- before this rank measures the global set by id.
-ws_status slab_measure(ws_handle *h, const ws_region *r, uint32_t k, uint32_t flags, ws_gauge *out)
-{
-    WsSlab *S = h->slab;
-    ws_status st = slab_gather_by_id(h, WS_PACK_POSVEL_H);
-    if (st) return st;
-    const char *why = regions_refusal(r, k, flags);
-    const ws_status mine = why ? WS_OK : h->gauge_out.grow(h, WS_GAUGE_OUT_BYTES, "gauge words");
-    const std::string mine_text = h->err;
-    if (S->world > 1) {
-        uint32_t word = 2166136261u;  // FNV-1a
-        auto mix = [&word](const void *p, size_t bytes) {
-            for (size_t b = 0; b < bytes; b++) word = (word ^ static_cast<const uint8_t *>(p)[b]) * 16777619u;
-        };
-        mix(&k, 4);
-        mix(&flags, 4);
-        if (!why) mix(r, (size_t)k * sizeof(ws_region));
-        word = (word << 1) | ((why || mine) ? 1u : 0u);
-        std::vector<uint32_t> tab;
-        if ((st = slab_agree_words(h, word, &tab))) return st;
-        bool anybody = false, differ = false;
-        for (uint32_t q = 0; q < S->world; q++) {
-            anybody = anybody || (tab[4 * q] & 1u);
-            differ = differ || (tab[4 * q] >> 1) != (word >> 1);
-        }
-        if (why) return fail(h, WS_ERR_INVALID_ARG, why);
-        if (mine) return fail(h, mine, mine_text.c_str());
-        if (anybody) return fail(h, WS_ERR_INVALID_ARG, "measure: another slab refused its arguments");
-        if (differ) return fail(h, WS_ERR_INVALID_ARG, "measure: the slabs were given different regions or flags");
-    }
-    if (why) return fail(h, WS_ERR_INVALID_ARG, why);
-    if (mine) return mine;
-    WsRegionSet rs{};
-    memcpy(rs.e, r, (size_t)k * sizeof(ws_region));
-    wsk_gauge_measure(h->stream, nullptr, reinterpret_cast<const float *>(S->g_out.p), (flags & WS_GAUGE_ATTRIBUTES) ? h->attr.p : nullptr,
-                      S->n_global, rs, k, h->gauge_out.p);
-    HIP_TRY(h, hipGetLastError());
-    GaugeWords words;
-    HIP_TRY(h, copy_now(h, &words, h->gauge_out.p, sizeof words, hipMemcpyDeviceToHost));
-    if (out) words.outputs(out, k);
-    return WS_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -2164,22 +2124,31 @@ extern "C" {
 // One streaming pass over `cur` behind the steps enqueued so far, and one wait for the gauges' words.  Nothing of the
 // handle is written but the call's own scratch: no array moves, nothing is binned, pred_stale and the last step's views
 // stay, a captured step is replayed as it is, and no profiling event is recorded.
+// Slab handles (COLLECTIVE): the velocity field's gather first, the arguments validated in common after it
+// (slab_verdict), and every rank measures the global set by id; out == NULL: this rank only contributes.
 ws_status ws_measure(ws_handle *h, const ws_region *r, uint32_t k, uint32_t flags, ws_gauge *out)
 {
-    ws_status st = gauges_enter(h, "measure");
+    ws_status st = enter(h, "measure");
     if (st) return st;
-    if (h->slab) return slab_measure(h, r, k, flags, out);  // collective: validated after the gather
-    if (!out) return fail(h, WS_ERR_INVALID_ARG, "measure: out is NULL");
-    if (const char *why = regions_refusal(r, k, flags)) return fail(h, WS_ERR_INVALID_ARG, why);
-    if ((st = h->gauge_out.grow(h, WS_GAUGE_OUT_BYTES, "gauge words"))) return st;
+    const WsSlab *S = h->slab;
+    if (!S && !out) return fail(h, WS_ERR_INVALID_ARG, "measure: out is NULL");
+    if (S && (st = slab_gather_by_id(h, WS_PACK_POSVEL_H))) return st;
+    const char *why = regions_refusal(r, k, flags);
+    const ws_status mine = why ? WS_OK : h->gauge_out.grow(h, WS_GAUGE_OUT_BYTES, "gauge words");
+    ArgHash hash;
+    hash(&k, 4);
+    hash(&flags, 4);
+    if (!why) hash(r, (size_t)k * sizeof(ws_region));
+    if ((st = slab_verdict(h, {"measure", "regions or flags", false}, why, mine, hash.word))) return st;
     WsRegionSet rs{};
     memcpy(rs.e, r, (size_t)k * sizeof(ws_region));
-    wsk_gauge_measure(h->stream, h->cur.pv, nullptr, (flags & WS_GAUGE_ATTRIBUTES) ? h->attr.p : nullptr, h->n, rs, k, h->gauge_out.p);
+    wsk_gauge_measure(h->stream, S ? nullptr : h->cur.pv, S ? reinterpret_cast<const float *>(S->g_out.p) : nullptr,
+                      (flags & WS_GAUGE_ATTRIBUTES) ? h->attr.p : nullptr, S ? S->n_global : h->n, rs, k, h->gauge_out.p);
     HIP_TRY(h, hipGetLastError());
     GaugeWords words;
     HIP_TRY(h, copy_now(h, &words, h->gauge_out.p, sizeof words, hipMemcpyDeviceToHost));
-    drain_profile(h);
-    words.outputs(out, k);
+    if (!S) drain_profile(h);
+    if (out) words.outputs(out, k);
     return WS_OK;
 }
 
@@ -2187,7 +2156,7 @@ ws_status ws_measure(ws_handle *h, const ws_region *r, uint32_t k, uint32_t flag
 // nothing reads between two steps), wsk_pop_scan, the first `cap` of them written in id order, and the readback.
 ws_status ws_select_particles(ws_handle *h, const ws_region *r, uint32_t k, uint32_t cap, uint32_t *out_ids, uint32_t *out_total)
 {
-    ws_status st = gauges_enter(h, "select");
+    ws_status st = enter(h, "select");
     if (st) return st;
     if (h->slab) return fail(h, WS_ERR_UNSUPPORTED, "select: not on slab handles (every rank holds its own slab's records: the list would be collective)");
     if (!out_total) return fail(h, WS_ERR_INVALID_ARG, "select: out_total is NULL");

@@ -177,8 +177,7 @@ struct FieldCtx {
 ws_status field_enter(ws_handle *h, const FieldCtx &c, const char *name, const char *none_msg)
 {
     WS_DEAD_CHECK(h);
-    if (h->flags & WS_FLAG_REFERENCE_ORDER)
-        return fail(h, WS_ERR_UNSUPPORTED, (std::string(name) + ": not in the reference-order validation mode").c_str());
+    if (h->flags & WS_FLAG_REFERENCE_ORDER) return reference_order_refused(h, name);
     if (none_msg && !c.want && !h->slab) return fail(h, WS_ERR_INVALID_ARG, none_msg);
     return WS_OK;
 }
@@ -963,41 +962,9 @@ ws_status attr_enter(ws_handle *h)
     return field_enter(h, c, "attributes", nullptr);
 }
 
-// FNV-1a over bytes: a call's arguments in the slabs' agreement (slab_edit_gathered's word)
-struct AttrHash {
-    uint32_t word = 2166136261u;
-    void mix(const void *p, size_t bytes)
-    {
-        for (size_t b = 0; b < bytes; b++) word = (word ^ static_cast<const uint8_t *>(p)[b]) * 16777619u;
-    }
-};
-
-// The verdict of a call that changes the attributes, before it has changed anything.  why: the argument error, or
-// nullptr; mine: a failure of this rank's own (an allocation), with its text in h->err.  A single handle answers for
-// itself.  Slab handles make the verdict common: bit 0 of the agreed word = this rank refuses, the rest = the hash of its
-// arguments; ranks that differ, or any of which refuses, ALL return WS_ERR_INVALID_ARG.
-ws_status attr_verdict(ws_handle *h, const char *why, ws_status mine, uint32_t hash)
-{
-    if (h->slab && h->slab->world > 1) {
-        const std::string mine_text = h->err;
-        const uint32_t word = (hash << 1) | ((why || mine) ? 1u : 0u);
-        std::vector<uint32_t> tab;
-        const ws_status st = slab_agree_words(h, word, &tab);
-        if (st) return st;
-        bool anybody = false, differ = false;
-        for (uint32_t r = 0; r < h->slab->world; r++) {
-            anybody = anybody || (tab[4 * r] & 1u);
-            differ = differ || (tab[4 * r] >> 1) != (word >> 1);
-        }
-        if (why) return fail(h, WS_ERR_INVALID_ARG, why);
-        if (mine) return fail(h, mine, mine_text.c_str());
-        if (anybody) return fail(h, WS_ERR_INVALID_ARG, "attributes: another slab refused its arguments; nothing was changed");
-        if (differ) return fail(h, WS_ERR_INVALID_ARG, "attributes: the slabs were given different arguments; nothing was changed");
-        return WS_OK;
-    }
-    if (why) return fail(h, WS_ERR_INVALID_ARG, why);
-    return mine;
-}
+// What the three calls that change the attributes say in the slabs' common verdict (slab_verdict: before anything is
+// changed; a single handle answers for itself).
+constexpr VerdictText kAttrVerdict = {"attributes", "arguments", true};
 
 // field_source for the calls that change the attributes: the positions by id and the grid they are binned on.  What a
 // slab's peers take part in (the gather) fails through the return value; what is this rank's alone (the scratch) comes
@@ -1034,7 +1001,7 @@ ws_status write_attributes(ws_handle *h, const float *in)
     uint64_t hash = 14695981039346656037ull;  // (volume_hash's form, folded to the agreement's word)
     if (in && h->slab) hash = volume_mix(hash, in, n * 4);
     const uint32_t given = in ? 1u : 0u;
-    if ((st = attr_verdict(h, nullptr, mine, ((uint32_t)(hash ^ (hash >> 32)) << 1) | given))) return st;
+    if ((st = slab_verdict(h, kAttrVerdict, nullptr, mine, ((uint32_t)(hash ^ (hash >> 32)) << 1) | given))) return st;
     if (in) HIP_TRY(h, hipMemcpyAsync(h->attr.p, in, n * 16, hipMemcpyHostToDevice, h->stream));
     else HIP_TRY(h, hipMemsetAsync(h->attr.p, 0, n * 16, h->stream));
     return field_finish(h, {});
@@ -1085,18 +1052,18 @@ ws_status paint_attributes(ws_handle *h, const ws_brush *b, uint32_t k, uint32_t
     if ((st = attr_positions(h, &c, &mine))) return st;
     if (!mine) mine = attr_ensure(h);
     WsBrushArgs args{};
-    AttrHash hash;
-    hash.mix(&k, 4);
+    ArgHash hash;
+    hash(&k, 4);
     if (!why) {
         memcpy(args.bs.e, b, (size_t)k * sizeof(ws_brush));
         args.k = k;
-        hash.mix(b, (size_t)k * sizeof(ws_brush));
+        hash(b, (size_t)k * sizeof(ws_brush));
         if (!mine && out_painted) {
             mine = scratch_zeroed(h, h->force_cnt, WS_MAX_BRUSHES * 4, "brush counters");
             args.painted = h->force_cnt.p;
         }
     }
-    if ((st = attr_verdict(h, why, mine, hash.word))) return st;
+    if ((st = slab_verdict(h, kAttrVerdict, why, mine, hash.word))) return st;
     wsk_attr_paint(h->stream, args, c.pos, h->attr.p, c.n);
     HIP_TRY(h, hipGetLastError());
     return field_finish(h, {{out_painted, h->force_cnt.p, (size_t)k * 4}});
@@ -1138,10 +1105,10 @@ ws_status diffuse_attributes(ws_handle *h, const ws_diffuse_params *p, float dt,
     if (!mine) mine = F.sattr[1].grow(h, n * 16, kFieldScratch);
     if (!mine) mine = F.srho.grow(h, n * 4, kFieldScratch);
     if (!mine && out_affected) mine = scratch_zeroed(h, h->force_cnt, sizeof partial, "diffusion counters");
-    AttrHash hash;
-    hash.mix(&dt, 4);
-    if (!why) hash.mix(p, sizeof *p);
-    if ((st = attr_verdict(h, why, mine, hash.word))) return st;
+    ArgHash hash;
+    hash(&dt, 4);
+    if (!why) hash(p, sizeof *p);
+    if ((st = slab_verdict(h, kAttrVerdict, why, mine, hash.word))) return st;
     if ((st = field_bin_particles(h, c))) return st;
     hipStream_t s = h->stream;
     wsk_attr_gather(s, F.spos.p, h->attr.p, F.sattr[0].p, c.n);

@@ -188,10 +188,10 @@ inline bool ws_bad_float(float x) { return !isfinite(x) || fabsf(x) > 1e15f; }
 // what).  Giving a lifetime up is one release() per owner, which cannot miss a member.  Nothing is freed by a destructor:
 // release is an explicit call, made with the handle's device current.
 //
-// A failed allocation (ws_api.cpp ws_alloc_failed) is WS_ERR_OUT_OF_MEMORY when HIP says so, else WS_ERR_HIP; `what`
+// A failed allocation (ws_api.cpp ws_hip_failed) is WS_ERR_OUT_OF_MEMORY when HIP says so, else WS_ERR_HIP; `what`
 // names the buffer in ws_last_error; the sticky HIP error is cleared (the next ws_step checks hipGetLastError), so a
 // handle whose call could not get its scratch stays usable.
-ws_status ws_alloc_failed(ws_handle *h, const char *what, hipError_t e);
+ws_status ws_hip_failed(ws_handle *h, const char *what, hipError_t e);
 
 // Outgrown buffers that could not be freed where they were replaced (WsScratch::grow_parked); freed with the handle.
 struct WsParked {
@@ -252,7 +252,7 @@ private:
         void *q = nullptr;
         const size_t real = want > 4 ? want : 4;
         const hipError_t e = PINNED ? hipHostMalloc(&q, real, hipHostMallocDefault) : hipMalloc(&q, real);
-        if (e != hipSuccess) return ws_alloc_failed(h, what, e);
+        if (e != hipSuccess) return ws_hip_failed(h, what, e);
         p = static_cast<T *>(q);
         bytes = want;
         return WS_OK;
@@ -503,10 +503,10 @@ ws_status WsGroup::alloc(ws_handle *h, T **field, size_t bytes, const char *what
 {
     void *q = nullptr;
     hipError_t e = hipMalloc(&q, bytes);
-    if (e != hipSuccess) return ws_alloc_failed(h, what, e);
+    if (e != hipSuccess) return ws_hip_failed(h, what, e);
     *field = static_cast<T *>(q);
     fields.push_back(reinterpret_cast<void **>(field));
-    if (zero && (e = hipMemsetAsync(q, 0, bytes, h->stream)) != hipSuccess) return ws_alloc_failed(h, what, e);
+    if (zero && (e = hipMemsetAsync(q, 0, bytes, h->stream)) != hipSuccess) return ws_hip_failed(h, what, e);
     return WS_OK;
 }
 

@@ -980,6 +980,64 @@ ws_status slab_agree(ws_handle *h, uint32_t mine, uint32_t *all)
     return WS_OK;
 }
 
+// THE COMMON VERDICT of a collective call on its arguments, before it has changed anything: every rank reaches it, a
+// rank that refuses included, and all refuse or go on alike -- a rank that left early would keep its peers waiting
+// inside the transport (ADVICE r4).  why: this rank's argument error, or nullptr; mine: a failure that is this rank's
+// alone (its scratch), with its text in h->err; hash: of its arguments (ArgHash).  One all-gather of one word, and no
+// other collective: bit 0 = this rank refuses, the rest = the hash.  A rank reports, in this order: its own argument
+// error, its own failure, a refusal elsewhere, a difference -- the last two as WS_ERR_INVALID_ARG in the call's words
+// (VerdictText).  A single handle, or a world of one, answers for itself without a transport call.
+ws_status slab_verdict(ws_handle *h, const VerdictText &text, const char *why, ws_status mine, uint32_t hash)
+{
+    const std::string mine_text = h->err;
+    bool anybody = false, differ = false;
+    if (h->slab && h->slab->world > 1) {
+        const uint32_t word = (hash << 1) | ((why || mine) ? 1u : 0u);
+        std::vector<uint32_t> tab;
+        const ws_status st = slab_agree_words(h, word, &tab);
+        if (st) return st;
+        for (uint32_t r = 0; r < h->slab->world; r++) {
+            anybody = anybody || (tab[4 * r] & 1u);
+            differ = differ || (tab[4 * r] >> 1) != (word >> 1);
+        }
+    }
+    if (why) return fail(h, WS_ERR_INVALID_ARG, why);
+    if (mine) return fail(h, mine, mine_text.c_str());
+    if (!anybody && !differ) return WS_OK;
+    const std::string what = anybody ? "another slab refused its arguments" : std::string("the slabs were given different ") + text.things;
+    return fail(h, WS_ERR_INVALID_ARG, (std::string(text.tag) + ": " + what + (text.mutates ? "; nothing was changed" : "")).c_str());
+}
+
+// A failure that is this rank's alone (`mine`, its text in h->err: an allocation, a copy) made common BEFORE the
+// mutation, so that no peer gives its arrays up and then waits for this rank in the next collective (ADVICE r4): one
+// agreement, and every rank returns -- its own failure as "<pre><text>; nothing was changed", one elsewhere as
+// WS_ERR_OUT_OF_MEMORY with `elsewhere`.
+ws_status slab_refuse_in_common(ws_handle *h, ws_status mine, const std::string &pre, const char *elsewhere)
+{
+    const std::string why = h->err;
+    uint32_t anybody = 0;
+    const ws_status st_agree = slab_agree(h, mine ? 1u : 0u, &anybody);
+    if (st_agree) return st_agree;
+    if (mine) return fail(h, mine, (pre + why + "; nothing was changed").c_str());
+    if (anybody) return fail(h, WS_ERR_OUT_OF_MEMORY, elsewhere);
+    return WS_OK;
+}
+
+// The same AFTER the mutation (st: this rank's reload, its text in h->err): one agreement, and if any rank failed every
+// handle is DEAD -- never half-built arrays under a handle that still steps.  failed: "<this rank's step> failed";
+// step: its name in a peer's message.
+ws_status slab_die_in_common(ws_handle *h, ws_status st, const std::string &failed, const char *step)
+{
+    const std::string why = h->err;
+    uint32_t anybody = 0;
+    const ws_status st_agree = slab_agree(h, st ? 1u : 0u, &anybody);
+    if (!st && !st_agree && !anybody) return WS_OK;
+    h->dead = true;
+    h->err = st ? failed + " after the old state was given up (" + why + "); the handle is unusable"
+                : std::string("another slab failed its ") + step + "; the handle is unusable";
+    return st ? st : (st_agree ? st_agree : WS_ERR_OUT_OF_MEMORY);
+}
+
 // Every rank must have chosen alike whatever fixes the step's collective sequence (how messages are sized, which
 // stream / communicator carries the halos, whether the step is captured), the record formats and the arithmetic: a
 // rank that differs would issue its size all-gathers or halos where its peers do not, and the run would hang inside
@@ -1020,9 +1078,7 @@ ws_status slab_layer_hist(ws_handle *h, const WsDev &d, const uint32_t *recs, ui
         wsk_slab_layer_hist(h->stream, d, recs, S->cnt_all.p, S->world, max_n, stride, S->hist.p);
         e = copy_now(h, hist->data(), S->hist.p, bytes, hipMemcpyDeviceToHost);
     }
-    if (e == hipSuccess) return WS_OK;
-    (void)hipGetLastError();
-    return fail(h, e == hipErrorOutOfMemory ? WS_ERR_OUT_OF_MEMORY : WS_ERR_HIP, "x-layer histogram", e);
+    return e == hipSuccess ? WS_OK : ws_hip_failed(h, "x-layer histogram", e);
 }
 
 ws_status slab_regrid(ws_handle *h, const ws_params *params, bool rebalance)
@@ -1042,15 +1098,9 @@ ws_status slab_regrid(ws_handle *h, const ws_params *params, bool rebalance)
     // the x-layer histogram of ALL particles on the NEW grid: the same on every rank
     const uint32_t nx = (uint32_t)geo.d.gdim_x;
     std::vector<uint32_t> hist(nx);
-    {
-        const ws_status mine = slab_layer_hist(h, geo.d, slab_gathered(S), max_n, stride, &hist);
-        const std::string why = h->err;
-        uint32_t anybody = 0;
-        const ws_status st_agree = slab_agree(h, mine ? 1u : 0u, &anybody);
-        if (st_agree) return st_agree;
-        if (mine) return fail(h, mine, ("re-grid: " + why + "; nothing was changed").c_str());
-        if (anybody) return fail(h, WS_ERR_OUT_OF_MEMORY, "re-grid: another slab could not build its layer histogram; nothing was changed");
-    }
+    st = slab_refuse_in_common(h, slab_layer_hist(h, geo.d, slab_gathered(S), max_n, stride, &hist), "re-grid: ",
+                               "re-grid: another slab could not build its layer histogram; nothing was changed");
+    if (st) return st;
     // cuts of equal particle counts where the host asked for them -- now (ws_slab_rebalance) or earlier (a re-grid
     // keeps the fluid balanced: the rule is re-applied on the new grid instead of falling back to equal layers)
     if (rebalance || S->balanced) {
@@ -1086,15 +1136,7 @@ ws_status slab_regrid(ws_handle *h, const ws_params *params, bool rebalance)
         if (hipGetLastError() != hipSuccess) st = fail(h, WS_ERR_HIP, "k_slab_select");
     }
     if (!st) st = slab_load_end(h);
-    const std::string why = h->err;
-    uint32_t anybody = 0;
-    const ws_status st_agree = slab_agree(h, st ? 1u : 0u, &anybody);
-    if (st || st_agree || anybody) {
-        h->dead = true;
-        h->err = st ? "re-grid failed after the old state was given up (" + why + "); the handle is unusable"
-                    : "another slab failed its re-grid; the handle is unusable";
-        return st ? st : (st_agree ? st_agree : WS_ERR_OUT_OF_MEMORY);
-    }
+    if ((st = slab_die_in_common(h, st, "re-grid failed", "re-grid"))) return st;
     if (rebalance) S->balanced = true;
     return WS_OK;
 }
@@ -1105,8 +1147,7 @@ ws_status slab_regrid(ws_handle *h, const ws_params *params, bool rebalance)
 // new predicted position, exactly as a host edit through ws_write_particles would have it.  No array is freed or
 // allocated.  (A kernel applied in place to the steady-state arrays would have to undo migration decisions the force
 // epilogue has already packed; the form that moves only the particles in reach is the scale-out follow-up: DESIGN.md 9.6.)
-// The call mutates state, so its verdict is made common before anything is touched: bit 0 of the agreed word = this rank
-// refuses, the rest = a hash of the arguments' bytes.
+// The call mutates state, so its verdict is made common before anything is touched (slab_verdict).
 // call: the description ws_api.cpp's edit_fluid documents (tag, things, refuse, prepare, mix, args, fetch).
 template <class Call>
 ws_status slab_edit_gathered(ws_handle *h, Call &call)
@@ -1125,49 +1166,24 @@ ws_status slab_edit_gathered(ws_handle *h, Call &call)
     // gathered and with no collective call of its own: a rank that refused skips it and keeps nobody waiting.)
     const WsGathered gathered = {slab_gathered(S), S->cnt_all.p, W, max_n, stride};
     const ws_status st_cnt = !why ? call.prepare(h, &gathered) : WS_OK;
-    uint32_t word = 2166136261u;  // FNV-1a
-    call.mix([&word](const void *p, size_t bytes) {
-        for (size_t b = 0; b < bytes; b++) word = (word ^ static_cast<const uint8_t *>(p)[b]) * 16777619u;
-    }, !why);
-    word = (word << 1) | ((why || st_cnt) ? 1u : 0u);
-    bool anybody = false, differ = false;
-    if (W > 1) {
-        std::vector<uint32_t> tab;
-        st = slab_agree_words(h, word, &tab);
-        if (st) return st;
-        for (uint32_t r = 0; r < W; r++) {
-            anybody = anybody || (tab[4 * r] & 1u);
-            differ = differ || (tab[4 * r] >> 1) != (word >> 1);
-        }
-    }
-    if (why) return fail(h, WS_ERR_INVALID_ARG, why);
-    if (st_cnt) return st_cnt;
-    if (anybody) return fail(h, WS_ERR_INVALID_ARG, (pre + "another slab refused its arguments; nothing was changed").c_str());
-    if (differ) return fail(h, WS_ERR_INVALID_ARG, (pre + "the slabs were given different " + call.things + "; nothing was changed").c_str());
+    ArgHash hash;
+    call.mix(std::ref(hash), !why);
+    if ((st = slab_verdict(h, {tag, call.things, true}, why, st_cnt, hash.word))) return st;
     uint32_t *recs = const_cast<uint32_t *>(slab_gathered(S));  // (scratch of the gather: nothing the step reads)
     // the edit, and the x-layer histogram of the edited set: every slab's owned count under the cuts against every slab's
     // capacity, all alike, before the old state is given up (slab_regrid).  A failure in here is this rank's alone and is
     // made common before anybody goes on.
     const uint32_t nx = (uint32_t)h->dev.gdim_x;
     std::vector<uint32_t> hist(nx);
-    {
-        wsk_edit_records(h->stream, h->dev, recs, S->cnt_all.p, W, max_n, stride, call.args);
-        ws_status mine = slab_layer_hist(h, h->dev, recs, max_n, stride, &hist);
-        if (!mine) {
-            hipError_t e = hipGetLastError();
-            if (e == hipSuccess) e = call.fetch(h);
-            if (e != hipSuccess) {
-                (void)hipGetLastError();
-                mine = fail(h, e == hipErrorOutOfMemory ? WS_ERR_OUT_OF_MEMORY : WS_ERR_HIP, "edit of the gathered state", e);
-            }
-        }
-        const std::string why_failed = h->err;
-        uint32_t failed = 0;
-        const ws_status st_agree = slab_agree(h, mine ? 1u : 0u, &failed);
-        if (st_agree) return st_agree;
-        if (mine) return fail(h, mine, (pre + why_failed + "; nothing was changed").c_str());
-        if (failed) return fail(h, WS_ERR_OUT_OF_MEMORY, (pre + "another slab could not edit the gathered state; nothing was changed").c_str());
+    wsk_edit_records(h->stream, h->dev, recs, S->cnt_all.p, W, max_n, stride, call.args);
+    ws_status mine = slab_layer_hist(h, h->dev, recs, max_n, stride, &hist);
+    if (!mine) {
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = call.fetch(h);
+        if (e != hipSuccess) mine = ws_hip_failed(h, "edit of the gathered state", e);
     }
+    st = slab_refuse_in_common(h, mine, pre, (pre + "another slab could not edit the gathered state; nothing was changed").c_str());
+    if (st) return st;
     for (uint32_t r = 0; r < W; r++) {
         uint64_t cnt = 0;
         for (uint32_t l = S->cuts[r]; l < S->cuts[r + 1] && l < nx; l++) cnt += hist[l];
@@ -1185,16 +1201,7 @@ ws_status slab_edit_gathered(ws_handle *h, Call &call)
         if (hipGetLastError() != hipSuccess) st = fail(h, WS_ERR_HIP, "k_slab_select");
     }
     if (!st) st = slab_load_end(h);
-    const std::string reason = h->err;
-    uint32_t failed = 0;
-    const ws_status st_agree = slab_agree(h, st ? 1u : 0u, &failed);
-    if (st || st_agree || failed) {
-        h->dead = true;
-        h->err = st ? pre + "the reload failed after the old state was given up (" + reason + "); the handle is unusable"
-                    : "another slab failed its reload; the handle is unusable";
-        return st ? st : (st_agree ? st_agree : WS_ERR_OUT_OF_MEMORY);
-    }
-    return WS_OK;
+    return slab_die_in_common(h, st, pre + "the reload failed", "reload");
 }
 
 // ws_sample_density_* on a slab handle (COLLECTIVE): every rank's current positions all-gathered by id into S->g_out
